@@ -8,9 +8,18 @@ the timed region.  N > 1: one process per GPU (torch.distributed.run), batch sha
 RCCL all-reduce of the flat gradient buffer in three buckets: the step is captured as hipGraph segments that end where a
 bucket completes, and each bucket's all-reduce is issued between two replays, under the next segment (viscy_amd/step.py).
 
-Prints ONE JSON line (rank 0) with the contract fields + "roofline" (dominant kernel class, timed
-live with HIP events on the launch stream inside the timed region) + "cpu_baseline" (the oracle —
-pure-torch fp32 restatement of the reference — timed on the host cores over a bounded sample).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run sets up, warms up, times --steps steps and prints; the
+other measurements run only under --full: "roofline" / "roofline_classes" (dominant kernel class, timed live with HIP events
+on the launch stream over eager replays behind the timed region), "fwd" (forward-only passes), "gate_shape" (B = 8, 2048^2),
+"fp32_parity" (the fp32 engine and its forward error against the oracle) and "cpu_baseline" (the oracle — pure-torch fp32
+restatement of the reference — timed on the host cores over a bounded sample).
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files: its loss, and a fixed sample
+(DUMP_SAMPLE elements at seeded positions) of the flat parameter buffer after it and of the flat gradient buffer it produced.
+The headline step does not train: its AdamW runs at learning rate 0 (every kernel still runs and moves the same bytes), so
+that every step starts from the same seeded parameters and two runs with the same arguments compute the same outputs up to
+the rounding of the kernels' fp32 atomics (see main()).  whole_path.final_loss is therefore the loss of the seeded model on
+the batch, and whole_path.loss_finite catches a non-finite value a kernel produced, not a divergence of training.
 """
 
 from __future__ import annotations
@@ -33,6 +42,7 @@ ALGO_MB_PER_PATCH = 226.5    # fwd+bwd two-pass-GRN floor, bf16 activations
 PROFILE_ROUND = "r06"        # prefix of this round's files under profiles/
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_BF16_PEAK_TFLOPS = 2500.0
+DUMP_SAMPLE = 1 << 22        # elements of the parameter / gradient buffers --dump-outputs writes (2 x 16 MB as float32)
 
 
 def source_hash() -> str:
@@ -507,6 +517,13 @@ def ranks_agree(flat: torch.Tensor) -> tuple[bool, float]:
     return bool(torch.equal(lo, hi)), float(fsum.item())
 
 
+def training_state_agree(flat: torch.Tensor, flat_grad: torch.Tensor, adam_m: torch.Tensor) -> bool:
+    """every rank holds the same parameters, the same (all-reduced) gradients of the last step and the same AdamW first moment
+    (ranks_agree on each; all three collectives run on every rank).  The gradients and the moment are what tell a missing or
+    broken all-reduce apart when the parameters cannot: at learning rate 0 they stay the seeded ones on every rank."""
+    return all([ranks_agree(t)[0] for t in (flat, flat_grad, adam_m)])
+
+
 def rank_times(elapsed_s: float, steps: int, device) -> dict:
     """per-rank ms / step of the timed region, gathered on every rank: min, max and the list"""
     import torch.distributed as dist
@@ -551,6 +568,26 @@ def resolve_world(gpus: int, env: dict, visible_devices: int) -> tuple[str, int]
     return "spawn", gpus
 
 
+def dump_outputs(out_dir: str, loss: torch.Tensor, flat: torch.Tensor, flat_grad: torch.Tensor, sample: int = DUMP_SAMPLE) -> dict:
+    """What the last training step handed back, as float32 .npy files under `out_dir`: `loss` (shape [1]), and the flat parameter
+    buffer after the step (`params`) and its gradient buffer (`grads`) at the same `sample` positions — drawn from a generator
+    seeded with 0 and sorted, so that every run of the same configuration writes the same elements.  Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = flat.numel()
+    if n > sample:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:sample].sort().values.to(flat.device)
+        flat, flat_grad = flat[idx], flat_grad[idx]
+    arrays = {"loss": loss.detach().float().reshape(1), "params": flat.detach().float(), "grads": flat_grad.detach().float()}
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     if "--cpu-baseline-child" in sys.argv:
         i = sys.argv.index("--cpu-baseline-child")
@@ -579,6 +616,13 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying the captured step")
     ap.add_argument("--profile-ops", action="store_true", help="print the per-op-class event-timing table to stderr")
     ap.add_argument("--force-dp", action="store_true", help="run the data-parallel collective path even with one rank (RCCL smoke test on a single GPU)")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("VSX_BENCH_FULL", "0") == "1",
+                    help="also run everything beyond the headline figure: the instrumented eager steps (roofline, roofline_classes), the "
+                         "forward-only passes (fwd), the gate-shape and fp32-parity sub-records and the CPU baseline (default: "
+                         "VSX_BENCH_FULL=1 in the environment, which scripts/refresh_profiles.sh and scripts/gpu_check.sh set; the result "
+                         "line says which mode made it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss, "
+                    "sampled parameters and gradients) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.dry_launch:
@@ -640,7 +684,13 @@ def main():
     model.grad_mode = "flat"
     eng = model.engine()
     total_steps = args.steps + args.warmup
-    opt = FlatAdamW(eng, lr=2e-4, schedule="WarmupCosine", warmup_steps=3, t_total=max(total_steps, 4), warmup_multiplier=1e-3)
+    # learning rate 0, so the headline step does not train: it repeats one training step from the seeded parameters.  Every
+    # kernel of the step runs, AdamW included (it reads and writes every parameter and both moments, and
+    # p * (1 - 0) - 0 * update leaves each parameter bit-identical), but the parameters stay the seeded ones.  With a
+    # learning rate, the fp32 atomics of the backward make each step's gradients differ in their last bits from run to run,
+    # AdamW turns such differences into learning-rate-sized parameter changes, and the runs drift apart step by step; this
+    # way every step of every run computes from the same parameters and the same batch (--dump-outputs compares builds).
+    opt = FlatAdamW(eng, lr=0.0, schedule="WarmupCosine", warmup_steps=3, t_total=max(total_steps, 4), warmup_multiplier=1e-3)
     ddp = FlatDataParallel(eng, opt, force=args.force_dp)
     crit = MixedLoss(0.5, 0.0, 0.5)
     B = args.batch
@@ -662,7 +712,22 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # ---- warmup (the last warmup step is instrumented per op class to find the dominant kernel)
+    def check_ranks():
+        # data parallel means an identical training state on every rank after every step: checked once, after the first steps.
+        # Every rank starts from the same seeded parameters, and at learning rate 0 they stay so whatever the gradients were,
+        # so the check covers what the all-reduce delivers too: the gradient buffer of the last step (each rank computed its
+        # share from a batch of its own, seed 42 + rank, and holds the sum after the all-reduce) and AdamW's first moment,
+        # which has accumulated the reduced gradients of every step so far.  A rank that diverged makes the whole line meaningless.
+        with Watchdog("training-state checksum all-reduce", args.collective_timeout, rank):
+            ok = training_state_agree(eng.flat, eng.flat_grad, opt.m)
+        if not ok:
+            raise SystemExit(f"bench.py: rank {rank}: parameters, reduced gradients or AdamW moments differ between ranks after "
+                             "the first optimisation steps")
+        return ok
+
+    # ---- warmup (--full / --profile-ops: two eager steps first, the second instrumented per op class to find the dominant kernel)
+    instrumented = args.full or args.profile_ops
+    l0, agree = None, None
     if args.profile_ops:
         with OpTimer(ops, by_shape=True) as tm:
             eager(x, tgt)
@@ -670,22 +735,23 @@ def main():
             for c, v in sorted(tm.summary().items(), key=lambda kv: -kv[1]["ms"])[:40]:
                 print(f"[shape] {c:58s} {v['launches']:3d}x {v['ms'] / v['launches'] * 1e3:9.1f} us  "
                       f"{v['bytes'] / max(v['ms'], 1e-9) / 1e6:8.1f} GB/s {v['flops'] / max(v['ms'], 1e-9) / 1e9:8.1f} TFLOP/s", file=sys.stderr)
-    with Watchdog("first training step", args.collective_timeout + 120, rank):
-        if not args.profile_ops:
-            eager(x, tgt)  # first launches load code objects / size workspaces: keep that out of the instrumented step
-        with OpTimer(ops) as tm:  # one eager, instrumented step: per-op-class times → dominant kernel class
-            l0 = eager(x, tgt)
-        table = tm.summary()
-    agree = None
-    if multi:
-        # data parallel means identical parameters on every rank after every step: checked once, after the first two steps
-        # (different batches per rank, all-reduced gradients, AdamW) — a rank that diverged makes the whole line meaningless
-        with Watchdog("parameter checksum all-reduce", args.collective_timeout, rank):
-            agree, _ = ranks_agree(eng.flat)
-        if not agree:
-            raise SystemExit(f"bench.py: rank {rank}: parameters differ between ranks after the first optimisation steps")
-    for _ in range(max(args.warmup, 1)):
-        step()
+    if instrumented:
+        with Watchdog("first training step", args.collective_timeout + 120, rank):
+            if not args.profile_ops:
+                eager(x, tgt)  # first launches load code objects / size workspaces: keep that out of the instrumented step
+            with OpTimer(ops) as tm:  # one eager, instrumented step: per-op-class times → dominant kernel class
+                l0 = eager(x, tgt)
+            table = tm.summary()
+        if multi:
+            agree = check_ranks()
+    for i in range(max(args.warmup, 1)):
+        if i == 0 and not instrumented:
+            with Watchdog("first training step", args.collective_timeout + 120, rank):  # (captures the graph)
+                step()
+        else:
+            step()
+    if multi and not instrumented:
+        agree = check_ranks()
     if args.profile_ops and rank == 0:
         tot = sum(v["ms"] for v in table.values())
         for c, v in sorted(table.items(), key=lambda kv: -kv[1]["ms"]):
@@ -700,44 +766,50 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    # dominant kernel class: average launch duration measured live with HIP events on the launch stream, over
-    # eager replays of the same step right behind the timed region (events cannot be recorded inside a graph replay)
-    REPLAYS = 3
-    with OpTimer(ops) as tm:
-        for _ in range(REPLAYS):
-            eager(x, tgt)
-    # the metric's second half, "fwd HBM GB/s": forward-only passes (inference schedule, one hipGraph replay each) priced at
-    # SURVEY §8(d)'s algorithmic two-pass floor of 75.5 MB per patch
-    from viscy_amd.step import InferStep
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else touches the training state
+        dumped = dump_outputs(args.dump_outputs, loss, eng.flat, eng.flat_grad)
+    fwd_s, fam_table, tmpl_table, dom = None, {}, {}, None
+    if args.full:
+        # dominant kernel class: average launch duration measured live with HIP events on the launch stream, over
+        # eager replays of the same step right behind the timed region (events cannot be recorded inside a graph replay)
+        REPLAYS = 3
+        with OpTimer(ops) as tm:
+            for _ in range(REPLAYS):
+                eager(x, tgt)
+        # the metric's second half, "fwd HBM GB/s": forward-only passes (inference schedule, one hipGraph replay each) priced at
+        # SURVEY §8(d)'s algorithmic two-pass floor of 75.5 MB per patch
+        from viscy_amd.step import InferStep
 
-    model.eval()
-    infer = InferStep(model)
-    nf = max(3, min(args.steps, 10))
-    infer(x)
-    barrier()
-    tf0 = time.perf_counter()
-    for _ in range(nf):
+        model.eval()
+        infer = InferStep(model)
+        nf = max(3, min(args.steps, 10))
         infer(x)
-    barrier()
-    fwd_s = (time.perf_counter() - tf0) / nf
-    model.train()
+        barrier()
+        tf0 = time.perf_counter()
+        for _ in range(nf):
+            infer(x)
+        barrier()
+        fwd_s = (time.perf_counter() - tf0) / nf
+        model.train()
     per_rank = None
     if multi:
         per_rank = rank_times(elapsed, args.steps, dev)
         elapsed = per_rank["max"] * args.steps / 1e3  # the contract: MAX over ranks
-    fam_table = tm.summary()
-    tmpl_table = tm.summary(templates=True)
-    # the dominant KERNEL: the template instantiation (kernel family + the template arguments / GEMM shape that select the code)
-    # with the largest summed launch time of the step; `roofline_classes` keeps the family view next to it
-    dominant = max(tmpl_table, key=lambda c: tmpl_table[c]["ms"]) if tmpl_table else None
-    dom = tmpl_table.get(dominant) if dominant else None
+    if args.full:
+        fam_table = tm.summary()
+        tmpl_table = tm.summary(templates=True)
+        # the dominant KERNEL: the template instantiation (kernel family + the template arguments / GEMM shape that select the code)
+        # with the largest summed launch time of the step; `roofline_classes` keeps the family view next to it
+        dominant = max(tmpl_table, key=lambda c: tmpl_table[c]["ms"]) if tmpl_table else None
+        dom = tmpl_table.get(dominant) if dominant else None
 
     binfo = build_info()
     cpu_leg = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_leg = CpuBaseline()  # writes the fp32 parity fixture now; its timing phase is released in result(), after the GPU sub-records
     gate, peak_main, parity = None, None, None
-    sub = rank == 0 and world == 1 and args.size == 256 and args.dtype == "bf16"
+    sub = args.full and rank == 0 and world == 1 and args.size == 256 and args.dtype == "bf16"
     want_gate, want_parity = sub and not args.no_gate, sub and not args.no_fp32_parity
     if want_gate or want_parity:
         # Sub-records measured in the same driver run.  The headline model / graph / batch are released first (the headline and
@@ -770,7 +842,7 @@ def main():
         # prescribes).  The file records the kernel-source hash and the flag set it was measured with; a file from other
         # sources / flags is refused (traffic stays null).
         tfam, tfam_k, trefused, tf_path = {}, {}, None, os.path.join(ROOT, "profiles", f"{PROFILE_ROUND}_pmc_traffic_b{B}.json")
-        if args.size == 256 and args.dtype == "bf16" and os.path.exists(tf_path):
+        if args.full and args.size == 256 and args.dtype == "bf16" and os.path.exists(tf_path):
             try:
                 tfj = json.load(open(tf_path))
                 if tfj.get("source_hash") == binfo["source_hash"] and tfj.get("flags") == binfo["flags"]:
@@ -849,25 +921,33 @@ def main():
             "whole_path": {
                 "hbm_frac_of_algorithmic_floor": round(value * ALGO_MB_PER_PATCH * scale * 1e6 / (world * HBM_PEAK_GBS * 1e9), 4),
                 "mfma_frac": round(value * 3 * FWD_GFLOP_PER_PATCH * scale * 1e9 / (world * MFMA_BF16_PEAK_TFLOPS * 1e12), 4),
-                "final_loss": round(float(loss.item()), 5), "first_loss": round(float(l0.item()), 5),
+                "final_loss": round(float(loss.item()), 5),
                 "loss_finite": bool(torch.isfinite(loss).item()),  # a non-finite loss invalidates the line
                 "peak_hbm_gb": round((peak_main if peak_main is not None else torch.cuda.max_memory_reserved()) / 1e9, 1),
             },
-            "roofline": roof,
-            "roofline_classes": roof_classes,
-            "gate_shape": gate,
-            "fp32_parity": parity,
             "build": binfo,
-            "fwd": {"ms_per_pass": round(fwd_s * 1e3, 3), "patches_per_s_per_gpu": round(B / fwd_s, 1),
-                    "algorithmic_hbm_GBps": round(B / fwd_s * FWD_MB_PER_PATCH * scale / 1e3, 1),
-                    "frac_hbm_peak": round(B / fwd_s * FWD_MB_PER_PATCH * scale * 1e6 / (HBM_PEAK_GBS * 1e9), 4),
-                    "tflops": round(B / fwd_s * FWD_GFLOP_PER_PATCH * scale / 1e3, 1)},
+            "full": args.full,
         }
+        if l0 is not None:  # the loss of the instrumented eager step (--full / --profile-ops)
+            res["whole_path"]["first_loss"] = round(float(l0.item()), 5)
+        if args.full:
+            res.update({
+                "roofline": roof,
+                "roofline_classes": roof_classes,
+                "gate_shape": gate,
+                "fp32_parity": parity,
+                "fwd": {"ms_per_pass": round(fwd_s * 1e3, 3), "patches_per_s_per_gpu": round(B / fwd_s, 1),
+                        "algorithmic_hbm_GBps": round(B / fwd_s * FWD_MB_PER_PATCH * scale / 1e3, 1),
+                        "frac_hbm_peak": round(B / fwd_s * FWD_MB_PER_PATCH * scale * 1e6 / (HBM_PEAK_GBS * 1e9), 4),
+                        "tflops": round(B / fwd_s * FWD_GFLOP_PER_PATCH * scale / 1e3, 1)},
+            })
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if not res["whole_path"]["loss_finite"]:
             print("bench.py: WARNING: the training loss is not finite after the timed steps — this measurement is INVALID",
                   file=sys.stderr)
         if multi:
-            res["ranks"] = {"ms_per_step": per_rank, "parameters_identical_across_ranks": agree}
+            res["ranks"] = {"ms_per_step": per_rank, "training_state_identical_across_ranks": agree}  # parameters, reduced gradients, AdamW m
         if cpu_leg is not None:  # the CPU leg is reported at N = 1 only (the other ranks would idle)
             res["cpu_baseline"] = cpu_leg.result()
     if multi:

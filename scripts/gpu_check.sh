@@ -3,6 +3,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+export VSX_BENCH_FULL=1  # bench.py --full: the bench stages record the whole line (roofline, sub-records, CPU baseline)
 STAGES="${1:-ops model smoke bench}"
 for s in $STAGES; do
   case $s in

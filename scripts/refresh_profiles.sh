@@ -6,6 +6,7 @@
 # Run through gpurun, then `bash scripts/refresh_profiles.sh --collect` locally copies gpurun_out/* into profiles/.
 cd "$(dirname "$0")/.."
 R=${ROUND:-r06}
+export VSX_BENCH_FULL=1  # bench.py --full: tools/roofline_table.py reads the roofline_classes of the full line
 if [ "$1" == "--collect" ]; then
   cp gpurun_out/kernel_stats.csv profiles/${R}_kernel_stats.csv
   cp gpurun_out/kernel_stats_train.csv profiles/${R}_kernel_stats_train.csv

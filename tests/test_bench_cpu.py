@@ -118,6 +118,32 @@ def test_rank_consistency_and_rank_times_world2_gloo(tmp_path, diverge):
     assert r[0]["times"]["per_rank"] == [10.0, 20.0] and r[0]["times"]["min"] == 10.0 and r[0]["times"]["max"] == 20.0
 
 
+def _state_worker(rank, world, init_file, out_dir, reduce):
+    import torch
+    import torch.distributed as dist
+
+    dist.init_process_group("gloo", init_method=f"file://{init_file}", rank=rank, world_size=world)
+    flat = torch.randn(1000, generator=torch.Generator().manual_seed(0))  # the same seeded parameters on every rank
+    grad = torch.randn(1000, generator=torch.Generator().manual_seed(1 + rank))  # each rank's share from a batch of its own
+    if reduce:
+        dist.all_reduce(grad)
+    m = 0.1 * grad  # AdamW's first moment after one step
+    with open(os.path.join(out_dir, f"s{rank}.json"), "w") as f:
+        json.dump({"agree": bench.training_state_agree(flat, grad, m)}, f)
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("reduce", [True, False])
+def test_training_state_check_catches_a_missing_all_reduce_world2_gloo(tmp_path, reduce):
+    """the parameters are identical on both ranks either way (learning rate 0 keeps them seeded): only the gradients and the
+    moment show whether the all-reduce happened"""
+    import torch.multiprocessing as mp
+
+    mp.spawn(_state_worker, args=(2, str(tmp_path / "init"), str(tmp_path), reduce), nprocs=2, join=True)
+    r = [json.load(open(tmp_path / f"s{i}.json")) for i in range(2)]
+    assert r[0]["agree"] == r[1]["agree"] == reduce
+
+
 def test_watchdog_names_rank_and_phase_and_exits_nonzero():
     code = ("import sys, time; sys.path.insert(0, %r); import bench\n"
             "with bench.Watchdog('first all-reduce', 0.5, 3):\n"
@@ -136,3 +162,34 @@ def test_mlp_mode_names_the_kernel_template():
     assert bench.mlp_mode("mlp_fc1_ln", {"store_h": False}) == 6 and bench.mlp_mode("mlp_fc1_ln", {}) == 2
     assert bench.mlp_mode("mlp_bwd_dh_ln", {}) == 7 and bench.mlp_mode("mlp_stats", {}) == 0
     assert bench.kernel_family("void mlp_fused_kernel_sf<224, 2, 8, 6>(MlpArgs)") == "mlp_fused"
+
+
+# ------------------------------------------------------------------ --dump-outputs / --full
+def test_dump_outputs_writes_float32_arrays_at_fixed_positions(tmp_path):
+    """the files --dump-outputs writes: float32 .npy, the loss as shape [1], parameters and gradients sampled at the same seeded
+    positions on every call (two builds dumped with the same arguments are compared element for element)"""
+    import numpy as np
+    import torch
+
+    n, k = 10_000, 1_000
+    flat, grad, loss = torch.arange(n, dtype=torch.float32), -torch.arange(n, dtype=torch.float32), torch.tensor(0.25)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), loss, flat, grad, sample=k)
+    bench.dump_outputs(str(tmp_path / "b"), loss, flat.clone(), grad.clone(), sample=k)
+    assert shapes == {"loss": [1], "params": [k], "grads": [k]}
+    a = {nm: np.load(tmp_path / "a" / f"{nm}.npy") for nm in shapes}
+    assert all(v.dtype == np.float32 for v in a.values()) and a["loss"][0] == 0.25
+    idx = a["params"].astype(np.int64)
+    assert len(np.unique(idx)) == k and np.all(np.diff(idx) > 0) and np.array_equal(a["grads"], -a["params"])
+    for nm in shapes:
+        assert np.array_equal(a[nm], np.load(tmp_path / "b" / f"{nm}.npy"))
+    # a buffer no larger than the sample is written whole
+    small = bench.dump_outputs(str(tmp_path / "c"), loss, flat[:50], grad[:50], sample=k)
+    assert small["params"] == [50] and np.array_equal(np.load(tmp_path / "c" / "params.npy"), np.arange(50, dtype=np.float32))
+    # the flagship's dump stays within 64 MB whatever the parameter count
+    assert 4 * (1 + 2 * bench.DUMP_SAMPLE) <= 64 * 2**20
+
+
+def test_full_and_dump_outputs_are_forwarded_to_the_ranks():
+    cmd = bench.launch_command(2, ["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "out", "--dry-launch"], port=29602)
+    tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:]
+    assert tail == ["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "out"]

@@ -68,8 +68,10 @@ def _datamodule(path):
                          normalize_on_device=False)
 
 
-def test_config1_one_training_step_on_cpu(plate_256, tmp_path):
+def test_config1_one_training_step_on_cpu(plate_256, tmp_path, monkeypatch):
     path, _ = plate_256
+    # configs[0] is the PyTorch-CPU case: the Trainer takes a visible GPU whenever there is one, so hide it
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     cfg = dict(in_channels=1, out_channels=1, num_blocks=2, num_filters=(8, 16, 32), task="reg")
     torch.manual_seed(3)
     module = VSUNet(architecture="2D", model_config=cfg, lr=2e-3, schedule="WarmupCosine", warmup_steps=0)
