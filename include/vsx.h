@@ -169,6 +169,53 @@ int32_t vsx_voxel_shuffle_fwd(const void* feat, float* out, int32_t B, int32_t h
 int32_t vsx_voxel_shuffle_bwd(const float* dout, void* dfeat, int32_t B, int32_t h, int32_t w, int32_t Cout, int32_t D,
     int32_t s, int32_t pool, int32_t dtype, vsx_stream_t stream);
 
+/* Narrow-channel family (csrc/narrow.hip): the 2x2-stem FCMAE (VSCyto2D).  Every reduction writes per-workgroup fp32 partials into
+ * `ws` (vsx_narrow_ws_floats(op, B, n, C, K) floats: n = pixels per sample for the block passes, rows M for the projection and the
+ * stem; C = channels (C0 for the stem); K = stem patch size / concatenated width) and sums them in a fixed order: the same bits from
+ * run to run.  Gradient outputs are ACCUMULATED (+=).  Block passes: C in {4, 8}, maps [B*H*W, C] channels-last, dtype storage,
+ * W1f [4C, C] / W2 [C, 4C] in dtype (the prepared fc operands, LayerNorm affine folded into fc1), everything else fp32. */
+#define VSX_NARROW_STEM 0
+#define VSX_NARROW_PROJ 1
+#define VSX_NARROW_FWD1 2
+#define VSX_NARROW_BWD_A 3
+#define VSX_NARROW_BWD_B 4
+#define VSX_NARROW_BWD_C 5
+int64_t vsx_narrow_ws_floats(int32_t op, int32_t B, int64_t n, int32_t C, int32_t K);
+/* stem, Z == kz: out[b*h*w, C0] = bias + W [C0, Cin*kz*ky*kx] . patch(x), x fp32 (B, Cin, Z, H, W) read directly */
+int32_t vsx_narrow_stem_fwd(const float* x, const float* W, const float* bias, void* out, int32_t B, int32_t Cin, int32_t Z,
+    int32_t H, int32_t Wd, int32_t kz, int32_t ky, int32_t kx, int32_t C0, int32_t dtype, vsx_stream_t stream);
+/* dW [C0, K] += df^T . patch(x), db [C0] += column sums of df */
+int32_t vsx_narrow_stem_wgrad(const float* x, const void* df, float* dW, float* db, float* ws, int64_t ws_floats, int32_t B,
+    int32_t Cin, int32_t Z, int32_t H, int32_t Wd, int32_t kz, int32_t ky, int32_t kx, int32_t C0, int32_t dtype, vsx_stream_t stream);
+/* out [M, C] = bp + Wp [C, Ccat] . (LN(cat) * gamma + beta), LN over the Ccat channels of a row (eps); mean / rstd [M] fp32 */
+int32_t vsx_narrow_proj_fwd(const void* cat, const float* gamma, const float* beta, const float* Wp, const float* bp, void* out,
+    float* mean, float* rstd, int64_t M, int32_t Ccat, int32_t C, float eps, int32_t dtype, vsx_stream_t stream);
+/* dxn [M, Ccat] = dout . Wp (gradient of the normalised affine rows); dW += dout^T . xn (xn re-formed from cat, mean, rstd);
+ * db += column sums of dout */
+int32_t vsx_narrow_proj_bwd(const void* dout, const void* cat, const float* mean, const float* rstd, const float* gamma,
+    const float* beta, const float* Wp, void* dxn, float* dW, float* db, float* ws, int64_t ws_floats, int64_t M, int32_t Ccat,
+    int32_t C, int32_t dtype, vsx_stream_t stream);
+/* block pass 1: y = dwconv7(x; dw_w [49, C], dw_b) (stored), colsq [B, 4C] += per-sample sum of gelu(fc1(LN(y)))^2 */
+int32_t vsx_narrow_block_fwd1(const void* x, const float* dw_w, const float* dw_b, const void* W1f, const float* b1f, void* y,
+    float* colsq, float* ws, int64_t ws_floats, int32_t B, int32_t H, int32_t Wd, int32_t C, int32_t dtype, vsx_stream_t stream);
+/* block pass 2: out = fc2(gelu(fc1(LN(y))) * s[b] + grn_b) + b2 + x */
+int32_t vsx_narrow_block_fwd2(const void* y, const void* x, const void* W1f, const float* b1f, const float* s, const float* grn_b,
+    const void* W2, const float* b2, void* out, int32_t B, int32_t H, int32_t Wd, int32_t C, int32_t dtype, vsx_stream_t stream);
+/* backward A: dW2 += dout^T z, db2 += sum dout, P [B, 4C] += per-sample sum dz * g, S [B, 4C] += per-sample sum dz (dz = dout . W2) */
+int32_t vsx_narrow_block_bwd_a(const void* dout, const void* y, const void* W1f, const float* b1f, const float* s, const float* grn_b,
+    const void* W2, float* dW2, float* db2, float* P, float* S, float* ws, int64_t ws_floats, int32_t B, int32_t H, int32_t Wd,
+    int32_t C, int32_t dtype, vsx_stream_t stream);
+/* backward B: dh = (dz * s + t * g) * gelu'(h); dy = LayerNorm backward of dh . W1f (stored); dW1f [4C, C] += dh^T xh, db1f += sum dh */
+int32_t vsx_narrow_block_bwd_b(const void* dout, const void* y, const void* W1f, const float* b1f, const float* s, const float* t,
+    const void* W2, void* dy, float* dW1f, float* db1f, float* ws, int64_t ws_floats, int32_t B, int32_t H, int32_t Wd, int32_t C,
+    int32_t dtype, vsx_stream_t stream);
+/* backward C: dx = dwconv7 adjoint of dy + dout (shortcut); ddw [49, C] += 7x7 weight gradient, ddb [C] += sum dy */
+int32_t vsx_narrow_block_bwd_c(const void* dy, const void* x, const void* dout, const float* dw_w, void* dx, float* ddw, float* ddb,
+    float* ws, int64_t ws_floats, int32_t B, int32_t H, int32_t Wd, int32_t C, int32_t dtype, vsx_stream_t stream);
+/* vsx_voxel_shuffle_bwd for any Cout*D*s*s (one element per thread: the pre-training head's 4 channels in bf16) */
+int32_t vsx_narrow_voxel_shuffle_bwd(const float* dout, void* dfeat, int32_t B, int32_t h, int32_t w, int32_t Cout, int32_t D,
+    int32_t s, int32_t pool, int32_t dtype, vsx_stream_t stream);
+
 /* out[m, :] = x[m, :] * scale[m / hw]  (rows of C elements, dtype): the gradient of a stochastic-depth branch
  * (timm DropPath in the ConvNeXt blocks, `drop_path_rate` / `encoder_drop_path_rate` of the reference models). */
 int32_t vsx_scale_rows_samples(const void* x, const float* scale, void* out, int64_t M, int32_t C, int32_t hw, int32_t dtype,

@@ -127,6 +127,17 @@ _SIGS = {
     "vsx_scale_weight_samples": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "vsx_voxel_shuffle_fwd": (_I32, [_P, _P] + [_I32] * 8 + [_P]),
     "vsx_voxel_shuffle_bwd": (_I32, [_P, _P] + [_I32] * 8 + [_P]),
+    "vsx_narrow_ws_floats": (_I64, [_I32, _I32, _I64, _I32, _I32]),
+    "vsx_narrow_stem_fwd": (_I32, [_P] * 4 + [_I32] * 10 + [_P]),
+    "vsx_narrow_stem_wgrad": (_I32, [_P] * 5 + [_I64] + [_I32] * 10 + [_P]),
+    "vsx_narrow_proj_fwd": (_I32, [_P] * 8 + [_I64, _I32, _I32, _F32, _I32, _P]),
+    "vsx_narrow_proj_bwd": (_I32, [_P] * 11 + [_I64, _I64, _I32, _I32, _I32, _P]),
+    "vsx_narrow_block_fwd1": (_I32, [_P] * 8 + [_I64] + [_I32] * 5 + [_P]),
+    "vsx_narrow_block_fwd2": (_I32, [_P] * 9 + [_I32] * 5 + [_P]),
+    "vsx_narrow_block_bwd_a": (_I32, [_P] * 12 + [_I64] + [_I32] * 5 + [_P]),
+    "vsx_narrow_block_bwd_b": (_I32, [_P] * 11 + [_I64] + [_I32] * 5 + [_P]),
+    "vsx_narrow_block_bwd_c": (_I32, [_P] * 8 + [_I64] + [_I32] * 5 + [_P]),
+    "vsx_narrow_voxel_shuffle_bwd": (_I32, [_P, _P] + [_I32] * 8 + [_P]),
     "vsx_layer_scale_fold": (_I32, [_P] * 5 + [_I32, _I32, _P]),
     "vsx_layer_scale_unfold": (_I32, [_P] * 8 + [_I32, _I32, _P]),
     "vsx_avgpool_rows_fwd": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P]),

@@ -197,7 +197,8 @@ class Engine:
         w.C, w.p = C, blk
         w.dw_w = torch.empty((49, C), dtype=torch.float32, device=self.device)
         o.transpose_f32(blk.conv_dw.weight, w.dw_w, C, 49, False)
-        w.W1f, w.W1fT = o.prep_weight(blk.mlp.fc1.weight, 4 * C, C, 1, dt, want=True, want_t=need_bwd,
+        need_t = need_bwd and C >= 16  # the narrow block kernels (C < 16) read W1f / W2 only
+        w.W1f, w.W1fT = o.prep_weight(blk.mlp.fc1.weight, 4 * C, C, 1, dt, want=True, want_t=need_t,
                                       gamma=blk.norm.weight)
         w.b1f = o.matvec(blk.mlp.fc1.weight, blk.norm.bias, blk.mlp.fc1.bias, 4 * C, C)
         w.dp = 0.0  # stochastic-depth rate of this block (set by prepare() from cfg["drop_path"])
@@ -214,7 +215,7 @@ class Engine:
         else:
             w.fc2_w, w.fc2_b = blk.mlp.fc2.weight, blk.mlp.fc2.bias
             w.grn_w, w.grn_b = blk.mlp.grn.weight, blk.mlp.grn.bias
-        w.W2, w.W2T = o.prep_weight(w.fc2_w, C, 4 * C, 1, dt, want=True, want_t=need_bwd)
+        w.W2, w.W2T = o.prep_weight(w.fc2_w, C, 4 * C, 1, dt, want=True, want_t=need_t)
         # fc2 bias with the GRN beta folded in (b2 + W2 . beta): what fc2 needs when the GRN scale lives in per-sample weights
         w.b2f = o.matvec(w.fc2_w, w.grn_b, w.fc2_b, C, 4 * C) if dt == torch.bfloat16 and C > 64 else None
         w.img2 = None  # image of (W2^T, W2) for the block backward without a stored dz
@@ -226,7 +227,10 @@ class Engine:
         cout, cin = conv.weight.shape[0], conv.weight.shape[1]
         taps = conv.weight.shape[2] * conv.weight.shape[3]
         w.cin, w.cout, w.taps, w.ln, w.conv = cin, cout, taps, ln, conv
-        w.W, w.WT = o.prep_weight(conv.weight, cout, cin, taps, dt, want=True, want_t=need_bwd)
+        if cout < 16:  # narrow stage: the fused projection reads the fp32 master weight itself
+            w.W = w.WT = None
+        else:
+            w.W, w.WT = o.prep_weight(conv.weight, cout, cin, taps, dt, want=True, want_t=need_bwd)
         return w
 
     def prepare(self, dt: torch.dtype, need_bwd: bool):
@@ -256,7 +260,12 @@ class Engine:
         sw = m.stem.conv.weight
         co3, K = sw.shape[0], sw[0].numel()
         Dp = cfg["ratio"]
-        if Dp == 1:
+        narrow_stem = cfg.get("head") == "shuffle" and tuple(cfg["stem_kernel"][1:]) == (2, 2)  # built only for the 2x2 FCMAE
+        if narrow_stem and K % 8 and Dp == 1:
+            # 2x2 stem (K = Cin * kz * 4): the patch is not a whole number of 16-byte bf16 vectors — the narrow stem reads the
+            # fp32 stack and the master weight directly (csrc/narrow.hip), no patch matrix, no GEMM operand
+            W["stem_W"], W["stem_b"] = None, m.stem.conv.bias
+        elif Dp == 1:
             W["stem_W"], _ = o.prep_weight(sw, co3, K, 1, dt)
             if dt == torch.bfloat16 and K % 32:
                 o.flush()  # pad_cols reads what the task list has yet to write
@@ -273,8 +282,10 @@ class Engine:
         s2 = getattr(m, "stem2d", None)
         if s2 is not None:  # FCMAE: Conv2d stem of Z == 1 inputs (fcmae.py:348-353,369-370) — the same patch GEMM with kz = 1
             K2 = s2.weight[0].numel()
-            W["stem2d_W"], _ = o.prep_weight(s2.weight, s2.weight.shape[0], K2, 1, dt)
-            if dt == torch.bfloat16 and K2 % 32:
+            W["stem2d_W"] = None
+            if not (narrow_stem and K2 % 8):
+                W["stem2d_W"], _ = o.prep_weight(s2.weight, s2.weight.shape[0], K2, 1, dt)
+            if W["stem2d_W"] is not None and dt == torch.bfloat16 and K2 % 32:
                 o.flush()
                 W["stem2d_W"] = o.pad_cols(W["stem2d_W"], (K2 + 31) // 32 * 32)
             W["stem2d_b"] = s2.bias
@@ -392,6 +403,8 @@ class Engine:
         masked path (fcmae.py:196-230): ``x`` arrives already multiplied by the mask, the depthwise convolution runs dense,
         LayerNorm / GRN-MLP run on the L kept tokens per sample only (compact rows), and the result is scattered back into
         zeros and added to the (masked) shortcut."""
+        if w.C < 16:
+            return self._block_fwd_narrow(x, w, B, H, Wd, save, rows)
         o = self.ops
         C, M = w.C, B * H * Wd
         blk = w.p
@@ -513,7 +526,46 @@ class Engine:
             save.append((x, xh, rstd, h, gact, colsq, s, rows, dpm))
         return out
 
+    def _block_fwd_narrow(self, x, w, B, H, Wd, save, rows):
+        """ConvNeXt-V2 block of C < 16 channels (the last decoder stage of a 2x2-stem FCMAE: C = 4 or 8) on the narrow family
+        (csrc/narrow.hip): pass 1 = depthwise 7x7 + LayerNorm + fc1 + GELU + GRN sums (stores only the C-wide depthwise output y),
+        pass 2 = the same recomputed from y + GRN + fc2 + bias + shortcut.  The 4C-wide hidden never goes to memory."""
+        o, C = self.ops, w.C
+        if rows is not None or w.v1 or (w.dp > 0.0 and self.model.training):
+            raise NotImplementedError("narrow ConvNeXt blocks are built for dense ConvNeXt-V2 decoder stages only")
+        colsq = self._za.take(B, 4 * C)
+        y = o.narrow_block_fwd1(x, w.dw_w, w.p.conv_dw.bias, w.W1f, w.b1f, colsq, B, H, Wd, C)
+        s = o.grn_scale(colsq, w.grn_w)
+        out = o.narrow_block_fwd2(y, x, w.W1f, w.b1f, s, w.grn_b, w.W2, w.fc2_b, B, H, Wd, C)
+        if save is not None:
+            save.append((x, y, colsq, s))
+        return out
+
+    def _block_bwd_narrow(self, dout, w, saved, B, H, Wd):
+        """backward of ``_block_fwd_narrow``: (A) fc2 weight / bias gradient and the GRN statistics, (B) GELU' + fc1 + LayerNorm
+        backward -> dy with the folded fc1 gradient, (C) depthwise data gradient + shortcut and the 7x7 weight / bias gradient;
+        the folded gradients are unfolded exactly as in the generic path"""
+        o, g = self.ops, self.g
+        C, blk = w.C, w.p
+        x, y, colsq, s = saved
+        PS = self._za.take(2, B, 4 * C)
+        o.narrow_block_bwd_a(dout, y, w.W1f, w.b1f, s, w.grn_b, w.W2, g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias), PS[0], PS[1],
+                             B, H, Wd, C)
+        t = o.grn_bwd_stats(colsq, PS[0], w.grn_w, g(blk.mlp.grn.weight), Sb=PS[1], dbeta=g(blk.mlp.grn.bias))
+        dW1f, db1f = self._za.take(4 * C, C), self._za.take(4 * C)
+        dy = o.narrow_block_bwd_b(dout, y, w.W1f, w.b1f, s, t, w.W2, dW1f, db1f, B, H, Wd, C)
+        o.unprep_grad(dW1f, g(blk.mlp.fc1.weight), 4 * C, C, 1, gamma=blk.norm.weight, W=blk.mlp.fc1.weight,
+                      dgamma=g(blk.norm.weight), u=db1f, beta=blk.norm.bias)
+        o.matvec_t_add(blk.mlp.fc1.weight, db1f, g(blk.norm.bias), 4 * C, C)
+        o.transpose_f32(db1f, g(blk.mlp.fc1.bias), 4 * C, 1, True)
+        ddw = self._za.take(49, C)
+        dx = o.narrow_block_bwd_c(dy, x, dout, w.dw_w, ddw, g(blk.conv_dw.bias), B, H, Wd, C)
+        o.transpose_f32(ddw, g(blk.conv_dw.weight), 49, C, True)
+        return dx
+
     def _block_bwd(self, dout, w, saved, B, H, Wd, dt):
+        if w.C < 16:
+            return self._block_bwd_narrow(dout, w, saved, B, H, Wd)
         o, g = self.ops, self.g
         C, M = w.C, B * H * Wd
         blk = w.p
@@ -715,15 +767,22 @@ class Engine:
             self._pending_bwd += 1
         # ---- stem: patch gather + projection GEMM, then encoder stem_1 LayerNorm2d
         stem_W, stem_b = (W["stem2d_W"], W["stem2d_b"]) if flat_stem else (W["stem_W"], W["stem_b"])
-        P = o.stem_im2col(x.contiguous(), (1 if flat_stem else kz, ky, kx), dt, ld=stem_W.shape[1])
-        M0, K0 = B * h * w, P.shape[1]
-        f = torch.empty((M0, C0), dtype=dt, device=x.device)
-        o.gemm("nt", P, stem_W, f, M0, C0, K0, K0, K0, C0, dtype=dt, epi=L.EPI_BIAS, bias=stem_b)
+        skern = (1 if flat_stem else kz, ky, kx)
+        M0 = B * h * w
+        if stem_W is None:  # narrow stem (K not a multiple of 8): no patch matrix; the backward re-reads the stack
+            P = x.contiguous()
+            f = o.narrow_stem_fwd(P, m.stem2d.weight if flat_stem else m.stem.conv.weight, stem_b, skern, dt)
+        else:
+            P = o.stem_im2col(x.contiguous(), skern, dt, ld=stem_W.shape[1])
+            K0 = P.shape[1]
+            f = torch.empty((M0, C0), dtype=dt, device=x.device)
+            o.gemm("nt", P, stem_W, f, M0, C0, K0, K0, K0, C0, dtype=dt, epi=L.EPI_BIAS, bias=stem_b)
         ln1 = m.encoder_stages.stem_1
         cur, mean, rstd = o.ln_fwd(f, ln1.weight, ln1.bias, M0, C0)
         if need_bwd:
             sv["stem"] = (P, f, mean, rstd)
             sv["flat_stem"] = flat_stem
+            sv["stem_narrow"] = skern if stem_W is None else None
         else:
             del P, f
         # ---- encoder
@@ -775,10 +834,15 @@ class Engine:
             cat = o.pixel_shuffle_cat_fwd(feat, skip, B, fh, fw, c_up, sc)
             fh, fw = sh, sw_
             Mk, ccat = B * fh * fw, c_up + sc
-            xn, mean, rstd = o.ln_fwd(cat, proj.ln.weight, proj.ln.bias, Mk, ccat)
-            cur = torch.empty((Mk, proj.cout), dtype=dt, device=x.device)
-            o.gemm("nt", xn, proj.W, cur, Mk, proj.cout, ccat, ccat, ccat, proj.cout, dtype=dt, epi=L.EPI_BIAS,
-                   bias=proj.conv.bias)
+            if proj.cout < 16:  # narrow stage (2x2 stem: C = 4 or 8): LayerNorm + 1x1 projection in one pass, xn not stored
+                cur, mean, rstd = o.narrow_proj_fwd(cat, proj.ln.weight, proj.ln.bias, proj.conv.weight, proj.conv.bias, Mk, ccat,
+                                                    proj.cout)
+                xn = None
+            else:
+                xn, mean, rstd = o.ln_fwd(cat, proj.ln.weight, proj.ln.bias, Mk, ccat)
+                cur = torch.empty((Mk, proj.cout), dtype=dt, device=x.device)
+                o.gemm("nt", xn, proj.W, cur, Mk, proj.cout, ccat, ccat, ccat, proj.cout, dtype=dt, epi=L.EPI_BIAS,
+                       bias=proj.conv.bias)
             st_sv = {"proj": (cat, xn, mean, rstd, c_up, sc), "blocks": [], "pre_in": low_in}
             for bw in blocks:
                 cur = self._block_fwd(cur, bw, B, fh, fw, dt, st_sv["blocks"] if need_bwd else None)
@@ -972,8 +1036,11 @@ class Engine:
                 d = self._embed_tail_bwd(sv, dout[0], dout[1], dt, B)
             elif cfg.get("head", "conv") == "shuffle":
                 fh, fw = sv["head"]
-                d = o.voxel_shuffle_bwd(dout.contiguous().float(), B, fh, fw, cfg["out_channels"], cfg["out_stack_depth"],
-                                        cfg["stem_kernel"][-1], True, dt)
+                sxy = cfg["stem_kernel"][-1]
+                vs = o.voxel_shuffle_bwd
+                if (cfg["out_channels"] * cfg["out_stack_depth"] * sxy * sxy) % (8 if dt == torch.bfloat16 else 4):
+                    vs = o.narrow_voxel_shuffle_bwd  # fewer channels than a 16-byte vector (2x2 pre-training head: 4)
+                d = vs(dout.contiguous().float(), B, fh, fw, cfg["out_channels"], cfg["out_stack_depth"], sxy, True, dt)
             else:
                 hdt = self._head_dtype(dt)
                 d = self._head_conv_bwd(sv, dout, hdt, B, dev)
@@ -989,10 +1056,14 @@ class Engine:
                 Mk, ccat = B * sh * sw_, c_up + sc
                 for bw, bsv in zip(reversed(blocks), reversed(st_sv["blocks"])):
                     d = self._block_bwd(d, bw, bsv, B, sh, sw_, dt)
-                o.gemm("tn", xn, d, g(proj.conv.weight), Mk, proj.cout, ccat, ccat, proj.cout, ccat, dtype=dt,
-                       colsum=g(proj.conv.bias))
-                dxn = torch.empty((Mk, ccat), dtype=dt, device=dev)
-                o.gemm("nt", d, proj.WT, dxn, Mk, ccat, proj.cout, proj.cout, proj.cout, ccat, dtype=dt)
+                if proj.cout < 16:
+                    dxn = o.narrow_proj_bwd(d, cat, mean, rstd, proj.ln.weight, proj.ln.bias, proj.conv.weight, g(proj.conv.weight),
+                                            g(proj.conv.bias), Mk, ccat, proj.cout)
+                else:
+                    o.gemm("tn", xn, d, g(proj.conv.weight), Mk, proj.cout, ccat, ccat, proj.cout, ccat, dtype=dt,
+                           colsum=g(proj.conv.bias))
+                    dxn = torch.empty((Mk, ccat), dtype=dt, device=dev)
+                    o.gemm("nt", d, proj.WT, dxn, Mk, ccat, proj.cout, proj.cout, proj.cout, ccat, dtype=dt)
                 dcat = o.ln_bwd(dxn, cat, mean, rstd, proj.ln.weight, None, g(proj.ln.weight), g(proj.ln.bias), Mk, ccat)
                 del dxn
                 d, dskips[2 - k] = o.pixel_shuffle_cat_bwd(dcat, B, sh // 2, sw_ // 2, c_up, sc)
@@ -1046,7 +1117,10 @@ class Engine:
             M0, C0, K0 = f.shape[0], f.shape[1], P.shape[1]
             df = o.ln_bwd(d, f, mean, rstd, ln1.weight, None, g(ln1.weight), g(ln1.bias), M0, C0)
             Dp = cfg["ratio"]
-            if sv.get("flat_stem"):
+            if sv.get("stem_narrow") is not None:  # patches recomputed from the stored stack (P is x here)
+                sc = m.stem2d if sv.get("flat_stem") else m.stem.conv
+                o.narrow_stem_wgrad(P, df, g(sc.weight), g(sc.bias), sv["stem_narrow"])
+            elif sv.get("flat_stem"):
                 Kw = m.stem2d.weight[0].numel()
                 o.gemm("tn", P, df, g(m.stem2d.weight), M0, C0, Kw, K0, C0, Kw, dtype=dt, colsum=g(m.stem2d.bias))
             elif Dp == 1:

@@ -774,3 +774,111 @@ def voxel_shuffle_bwd(dout: Tensor, B: int, h: int, w: int, Cout: int, D: int, s
     check(lib().vsx_voxel_shuffle_bwd(ptr(dout), ptr(dfeat), B, h, w, Cout, D, s, int(pool), dtype_code(dtype), stream()),
           "voxel_shuffle_bwd")
     return dfeat
+
+
+# ------------------------------------------------------------------ narrow-channel family (csrc/narrow.hip): the 2x2-stem FCMAE
+NARROW_STEM, NARROW_PROJ, NARROW_FWD1, NARROW_BWD_A, NARROW_BWD_B, NARROW_BWD_C = range(6)
+_NARROW_WS: dict = {}
+
+
+def _narrow_ws(dev, op: int, B: int, n: int, C: int, K: int = 0) -> Tensor:
+    """per-workgroup partials of a narrow launch (grown, never freed: a captured hipGraph keeps pointing at it)"""
+    floats = int(lib().vsx_narrow_ws_floats(op, B, n, C, K))
+    if floats <= 0:
+        raise ValueError(f"vsx_narrow_ws_floats({op}, {B}, {n}, {C}, {K}) = {floats}")
+    held = _NARROW_WS.setdefault(dev, [])
+    if not held or held[-1].numel() < floats:
+        held.append(torch.empty(max(floats, 1 << 16), dtype=torch.float32, device=dev))
+    return held[-1]
+
+
+def narrow_stem_fwd(x: Tensor, W: Tensor, b: Tensor, kernel: tuple[int, int, int], dtype: torch.dtype) -> Tensor:
+    """stem whose patch (K = Cin*kz*ky*kx) is not a whole number of 16-byte bf16 vectors: [B*h*w, C0] straight from the fp32 stack"""
+    if x.dtype != torch.float32:
+        raise TypeError("input stacks are float32")
+    B, Cin, Z, H, Wd = x.shape
+    kz, ky, kx = kernel
+    C0 = W.shape[0]
+    out = torch.empty((B * (H // ky) * (Wd // kx), C0), dtype=dtype, device=x.device)
+    check(lib().vsx_narrow_stem_fwd(ptr(x), ptr(W), ptr(b), ptr(out), B, Cin, Z, H, Wd, kz, ky, kx, C0, dtype_code(dtype), stream()),
+          "narrow_stem_fwd")
+    return out
+
+
+def narrow_stem_wgrad(x: Tensor, df: Tensor, dW: Tensor, db: Tensor, kernel: tuple[int, int, int]) -> None:
+    B, Cin, Z, H, Wd = x.shape
+    kz, ky, kx = kernel
+    C0, K = df.shape[1], Cin * kz * ky * kx
+    ws = _narrow_ws(x.device, NARROW_STEM, B, df.shape[0], C0, K)
+    check(lib().vsx_narrow_stem_wgrad(ptr(x), ptr(df), ptr(dW), ptr(db), ptr(ws), ws.numel(), B, Cin, Z, H, Wd, kz, ky, kx, C0,
+                                      dtype_code(df.dtype), stream()), "narrow_stem_wgrad")
+
+
+def narrow_proj_fwd(cat: Tensor, gamma: Tensor, beta: Tensor, W: Tensor, b: Tensor, M: int, Ccat: int, C: int, eps: float = 1e-6):
+    """LayerNorm2d(Ccat, affine) + 1x1 convolution into C in {4, 8} channels; returns (out [M, C], mean [M], rstd [M])"""
+    out = torch.empty((M, C), dtype=cat.dtype, device=cat.device)
+    mean = torch.empty(M, dtype=torch.float32, device=cat.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=cat.device)
+    check(lib().vsx_narrow_proj_fwd(ptr(cat), ptr(gamma), ptr(beta), ptr(W), ptr(b), ptr(out), ptr(mean), ptr(rstd), M, Ccat, C, eps,
+                                    dtype_code(cat.dtype), stream()), "narrow_proj_fwd")
+    return out, mean, rstd
+
+
+def narrow_proj_bwd(dout: Tensor, cat: Tensor, mean: Tensor, rstd: Tensor, gamma: Tensor, beta: Tensor, W: Tensor, dW: Tensor,
+                    db: Tensor, M: int, Ccat: int, C: int) -> Tensor:
+    """returns dxn [M, Ccat] (gradient of the LayerNorm's affine output); dW [C, Ccat] / db [C] accumulate"""
+    dxn = torch.empty((M, Ccat), dtype=cat.dtype, device=cat.device)
+    ws = _narrow_ws(cat.device, NARROW_PROJ, 1, M, C, Ccat)
+    check(lib().vsx_narrow_proj_bwd(ptr(dout), ptr(cat), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(W), ptr(dxn), ptr(dW), ptr(db),
+                                    ptr(ws), ws.numel(), M, Ccat, C, dtype_code(cat.dtype), stream()), "narrow_proj_bwd")
+    return dxn
+
+
+def narrow_block_fwd1(x: Tensor, dw_w: Tensor, dw_b: Tensor, W1f: Tensor, b1f: Tensor, colsq: Tensor, B: int, H: int, W: int,
+                      C: int) -> Tensor:
+    """ConvNeXt-V2 block at C in {4, 8}, pass 1: returns the depthwise output y; colsq [B, 4C] += per-sample sum gelu(h)^2"""
+    y = torch.empty_like(x)
+    ws = _narrow_ws(x.device, NARROW_FWD1, B, H * W, C)
+    check(lib().vsx_narrow_block_fwd1(ptr(x), ptr(dw_w), ptr(dw_b), ptr(W1f), ptr(b1f), ptr(y), ptr(colsq), ptr(ws), ws.numel(), B, H, W,
+                                      C, dtype_code(x.dtype), stream()), "narrow_block_fwd1")
+    return y
+
+
+def narrow_block_fwd2(y: Tensor, x: Tensor, W1f: Tensor, b1f: Tensor, s: Tensor, grn_b: Tensor, W2: Tensor, b2: Tensor, B: int, H: int,
+                      W: int, C: int) -> Tensor:
+    out = torch.empty_like(x)
+    check(lib().vsx_narrow_block_fwd2(ptr(y), ptr(x), ptr(W1f), ptr(b1f), ptr(s), ptr(grn_b), ptr(W2), ptr(b2), ptr(out), B, H, W, C,
+                                      dtype_code(x.dtype), stream()), "narrow_block_fwd2")
+    return out
+
+
+def narrow_block_bwd_a(dout: Tensor, y: Tensor, W1f: Tensor, b1f: Tensor, s: Tensor, grn_b: Tensor, W2: Tensor, dW2: Tensor, db2: Tensor,
+                       P: Tensor, S: Tensor, B: int, H: int, W: int, C: int) -> None:
+    ws = _narrow_ws(y.device, NARROW_BWD_A, B, H * W, C)
+    check(lib().vsx_narrow_block_bwd_a(ptr(dout), ptr(y), ptr(W1f), ptr(b1f), ptr(s), ptr(grn_b), ptr(W2), ptr(dW2), ptr(db2), ptr(P),
+                                       ptr(S), ptr(ws), ws.numel(), B, H, W, C, dtype_code(y.dtype), stream()), "narrow_block_bwd_a")
+
+
+def narrow_block_bwd_b(dout: Tensor, y: Tensor, W1f: Tensor, b1f: Tensor, s: Tensor, t: Tensor, W2: Tensor, dW1f: Tensor, db1f: Tensor,
+                       B: int, H: int, W: int, C: int) -> Tensor:
+    dy = torch.empty_like(y)
+    ws = _narrow_ws(y.device, NARROW_BWD_B, B, H * W, C)
+    check(lib().vsx_narrow_block_bwd_b(ptr(dout), ptr(y), ptr(W1f), ptr(b1f), ptr(s), ptr(t), ptr(W2), ptr(dy), ptr(dW1f), ptr(db1f),
+                                       ptr(ws), ws.numel(), B, H, W, C, dtype_code(y.dtype), stream()), "narrow_block_bwd_b")
+    return dy
+
+
+def narrow_block_bwd_c(dy: Tensor, x: Tensor, dout: Tensor, dw_w: Tensor, ddw: Tensor, ddb: Tensor, B: int, H: int, W: int,
+                       C: int) -> Tensor:
+    dx = torch.empty_like(x)
+    ws = _narrow_ws(x.device, NARROW_BWD_C, B, H * W, C)
+    check(lib().vsx_narrow_block_bwd_c(ptr(dy), ptr(x), ptr(dout), ptr(dw_w), ptr(dx), ptr(ddw), ptr(ddb), ptr(ws), ws.numel(), B, H, W,
+                                       C, dtype_code(x.dtype), stream()), "narrow_block_bwd_c")
+    return dx
+
+
+def narrow_voxel_shuffle_bwd(dout: Tensor, B: int, h: int, w: int, Cout: int, D: int, s: int, pool: bool, dtype: torch.dtype) -> Tensor:
+    dfeat = torch.empty((B * h * w, Cout * D * s * s), dtype=dtype, device=dout.device)
+    check(lib().vsx_narrow_voxel_shuffle_bwd(ptr(dout), ptr(dfeat), B, h, w, Cout, D, s, int(pool), dtype_code(dtype), stream()),
+          "narrow_voxel_shuffle_bwd")
+    return dfeat

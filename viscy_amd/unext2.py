@@ -211,13 +211,26 @@ class _Core(nn.Module):
                decoder_conv_blocks, head: str, head_channels_from: int, head_pool: bool, head_expansion_ratio: int,
                decoder_upsample_pre_conv: bool = False) -> None:
         stem_kernel_size = tuple(stem_kernel_size)
-        if stem_kernel_size[1] != 4 or stem_kernel_size[2] != 4:
-            raise NotImplementedError("stem_kernel_size must be (k, 4, 4)")
+        sxy = tuple(stem_kernel_size[1:])
+        if sxy != (4, 4) and not (sxy == (2, 2) and head == "shuffle"):
+            raise NotImplementedError(
+                f"stem_kernel_size {stem_kernel_size}: built are (k, 4, 4) for every model and (k, 2, 2) for FullyConvolutionalMAE "
+                "with the PixelToVoxelShuffleHead (head_conv=False, the VSCyto2D recipes)")
         ratio = in_stack_depth // stem_kernel_size[0]
         if dims[0] % ratio != 0:
             raise ValueError(
                 f"out_channels ({dims[0]}) must be divisible by in_stack_depth // kernel_size[0] ({ratio})"
             )
+        if sxy == (2, 2):  # what the narrow-channel kernels (csrc/narrow.hip) serve
+            c_last = out_channels * out_stack_depth * 4
+            if c_last < 16 and c_last not in (4, 8):
+                raise NotImplementedError(f"2x2 stem: the last decoder stage has out_channels * in_stack_depth * 4 = {c_last} "
+                                          "channels; built are 4, 8 and multiples of 8 from 16 on")
+            K = in_channels * stem_kernel_size[0] * 4
+            if K % 8 and (ratio != 1 or K > 40 or dims[0] > 96 or dims[0] % 8):
+                raise NotImplementedError(f"2x2 stem with a patch of {K} values: built for in_stack_depth == kz, K <= 40 and "
+                                          f"a stem width that is a multiple of 8 up to 96 (got in_stack_depth // kz = {ratio}, "
+                                          f"width {dims[0]})")
         self.cfg = dict(
             in_channels=in_channels, out_channels=out_channels, in_stack_depth=in_stack_depth,
             out_stack_depth=out_stack_depth, depths=tuple(depths), dims=tuple(dims), conv_mlp=conv_mlp,
@@ -284,7 +297,8 @@ class _Core(nn.Module):
         dec = self.cfg.get("decoder_channels")
         if dec:
             skips = list(reversed(dims))[1:]
-            widths += [dec[i] // 4 + skips[i] for i in range(len(skips))] + list(dec)
+            # a last decoder stage of 4 or 8 channels (2x2 stem) runs on the narrow family (csrc/narrow.hip), built for them
+            widths += [dec[i] // 4 + skips[i] for i in range(len(skips))] + [c for c in dec if c not in (4, 8)]
         return all(w % 8 == 0 for w in widths)
 
     def _resolve_dtype(self) -> torch.dtype:
