@@ -607,6 +607,42 @@ int32_t vsx_warp_affine3d_roi(const float* x, float* y, const float* Minv, int32
 int32_t vsx_conv1d_axis(const float* x, float* y, const float* taps, int32_t k, int32_t B, int64_t per_sample,
     int64_t stride, int32_t L, vsx_stream_t stream);
 
+/* Dense 3x3x3 convolution family (csrc/conv3d.hip): FNet3D.  Activations channels-last [B*D*H*W][C] with a row stride (ld*) and a
+ * channel offset (*coff); dtype VSX_BF16 (MFMA bf16) or VSX_F32 (exact fp32 MFMA).  Reductions: per-workgroup partials, fixed-order fold.
+ * prep_weight: out[n][t * Kc + c] = w[n * sn + c * sc + (flip ? 26 - t : t)]  (tap-major GEMM operand, dtype).
+ * fwd: c[o][ccoff + n] = bias[n] (+ c, accumulate) + sum over taps / channels of a * W (prepared [Cout][27 Cin]); zero padding 1,
+ * stride 1 or 2, or (transposed = 1) ConvTranspose3d k 3 / stride 2 / padding 1 / output_padding 1 over the 2x output grid.  B, Di, Hi,
+ * Wi: input grid.  out_f32: c is fp32 (bf16 operands).  stats (optional): [vsx_conv3d_stats_rows][2][Cout] column partials of z, z^2.
+ * wgrad: out[r][c][t] += sum over voxels m of the P grid (B, Dg, Hg, Wg) of P[m][r] * Q[m * stride + k(t) - 1][c], Q on the grid
+ * (Dg, Hg, Wg) * stride; ws: vsx_conv3d_wgrad_ws_floats floats.
+ * colsum: out[c] += sum over M rows of x[row][xcoff + c]; ws: vsx_conv3d_colsum_groups(M) * C floats.
+ * bn3d_finalize: ss = [scale | shift | mean | rstd] ([4][C]) from the stats partials (training; running stats and num_batches_tracked
+ * updated on the device) or the running statistics (eval).  bn3d_apply_relu: dst[r][dcoff + c] = max(z * scale + shift, 0).
+ * bn3d_bwd: g = dy * [z * scale + shift > 0]; dgamma += sum g xhat, dbeta += sum g, dz = gamma rstd (g - mean g - xhat mean(g xhat))
+ * (training) or gamma rstd g (eval); ws: vsx_bn3d_bwd_ws_floats floats.  to_cl / from_cl: NCDHW fp32 <-> channels-last. */
+int32_t vsx_conv3d_prep_weight(const float* w, void* out, int32_t N, int32_t Kc, int32_t sn, int32_t sc, int32_t flip, int32_t dtype,
+    vsx_stream_t stream);
+int64_t vsx_conv3d_stats_rows(int32_t B, int32_t Di, int32_t Hi, int32_t Wi, int32_t stride, int32_t transposed);
+int32_t vsx_conv3d_fwd(const void* a, int32_t lda, int32_t acoff, const void* wp, const float* bias, void* c, int32_t ldc,
+    int32_t ccoff, float* stats, int32_t B, int32_t Di, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride,
+    int32_t transposed, int32_t accumulate, int32_t dtype, int32_t out_f32, vsx_stream_t stream);
+int64_t vsx_conv3d_wgrad_ws_floats(int32_t B, int32_t Dg, int32_t Hg, int32_t Wg, int32_t R, int32_t C, int32_t dtype);
+int32_t vsx_conv3d_wgrad(const void* P, int32_t ldp, int32_t pcoff, const void* Q, int32_t ldq, int32_t qcoff, float* ws,
+    int64_t ws_floats, float* out, int32_t B, int32_t Dg, int32_t Hg, int32_t Wg, int32_t R, int32_t C, int32_t stride,
+    int32_t dtype, vsx_stream_t stream);
+int64_t vsx_conv3d_colsum_groups(int64_t M);
+int32_t vsx_conv3d_colsum(const void* x, int32_t ldx, int32_t xcoff, int64_t M, int32_t C, float* ws, float* out, int32_t dtype,
+    vsx_stream_t stream);
+int32_t vsx_bn3d_finalize(const float* ws, int64_t G, int64_t M, int32_t C, const float* gamma, const float* beta, float* rmean,
+    float* rvar, int64_t* nbt, float* ss, float eps, float momentum, int32_t training, vsx_stream_t stream);
+int32_t vsx_bn3d_apply_relu(const void* z, const float* ss, void* dst, int32_t ldd, int32_t dcoff, int64_t M, int32_t C,
+    int32_t dtype, vsx_stream_t stream);
+int64_t vsx_bn3d_bwd_ws_floats(int64_t M, int32_t C);
+int32_t vsx_bn3d_bwd(const void* dy, int32_t ldy, int32_t ycoff, const void* z, const float* ss, const float* gamma, float* ws,
+    float* dgamma, float* dbeta, void* dz, int64_t M, int32_t C, int32_t training, int32_t dtype, vsx_stream_t stream);
+int32_t vsx_conv3d_to_cl(const float* x, void* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream);
+int32_t vsx_conv3d_from_cl(const void* y, float* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,19 @@ _SIGS = {
     "vsx_warp_affine3d": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vsx_warp_affine3d_roi": (_I32, [_P, _P, _P] + [_I32] * 12 + [_P]),
     "vsx_conv1d_axis": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I64, _I32, _P]),
+    "vsx_conv3d_prep_weight": (_I32, [_P, _P] + [_I32] * 6 + [_P]),
+    "vsx_conv3d_stats_rows": (_I64, [_I32] * 6),
+    "vsx_conv3d_fwd": (_I32, [_P, _I32, _I32, _P, _P, _P, _I32, _I32, _P] + [_I32] * 11 + [_P]),
+    "vsx_conv3d_wgrad_ws_floats": (_I64, [_I32] * 7),
+    "vsx_conv3d_wgrad": (_I32, [_P, _I32, _I32, _P, _I32, _I32, _P, _I64, _P] + [_I32] * 8 + [_P]),
+    "vsx_conv3d_colsum_groups": (_I64, [_I64]),
+    "vsx_conv3d_colsum": (_I32, [_P, _I32, _I32, _I64, _I32, _P, _P, _I32, _P]),
+    "vsx_bn3d_finalize": (_I32, [_P, _I64, _I64, _I32] + [_P] * 6 + [_F32, _F32, _I32, _P]),
+    "vsx_bn3d_apply_relu": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P]),
+    "vsx_bn3d_bwd_ws_floats": (_I64, [_I64, _I32]),
+    "vsx_bn3d_bwd": (_I32, [_P, _I32, _I32] + [_P] * 7 + [_I64, _I32, _I32, _I32, _P]),
+    "vsx_conv3d_to_cl": (_I32, [_P, _P, _I32, _I32, _I64, _I32, _P]),
+    "vsx_conv3d_from_cl": (_I32, [_P, _P, _I32, _I32, _I64, _I32, _P]),
 }
 
 _lib = None

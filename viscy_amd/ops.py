@@ -882,3 +882,125 @@ def narrow_voxel_shuffle_bwd(dout: Tensor, B: int, h: int, w: int, Cout: int, D:
     check(lib().vsx_narrow_voxel_shuffle_bwd(ptr(dout), ptr(dfeat), B, h, w, Cout, D, s, int(pool), dtype_code(dtype), stream()),
           "narrow_voxel_shuffle_bwd")
     return dfeat
+
+
+# ------------------------------------------------------------------------------------------------
+# dense 3x3x3 convolution family (csrc/conv3d.hip): FNet3D.  Activations are channels-last [M, ld] matrices; an operand is the
+# column slice [coff, coff + C) of one.  ``grid`` = (B, D, H, W) of the convolution's INPUT.
+# roles of a prepared weight (the GEMM operand [N][27 K] read by vsx_conv3d_fwd):
+#   conv          Conv3d weight [Cout, Cin, 3, 3, 3]            -> forward (stride 1 / 2)
+#   conv_dgrad_s1 Conv3d weight, flipped + channel-transposed   -> data gradient of a stride-1 convolution
+#   conv_dgrad_s2 Conv3d weight, channel-transposed             -> data gradient of the stride-2 convolution (transposed kernel)
+#   convT         ConvTranspose3d weight [Cin, Cout, 3, 3, 3]   -> forward (8 parity classes)
+#   convT_dgrad   ConvTranspose3d weight                        -> its data gradient (stride-2 convolution)
+_C3_ROLES = {  # role -> (N, Kc, sn, sc, flip) from the weight's dims (d0, d1)
+    "conv": lambda d0, d1: (d0, d1, d1 * 27, 27, 0),
+    "conv_dgrad_s1": lambda d0, d1: (d1, d0, 27, d1 * 27, 1),
+    "conv_dgrad_s2": lambda d0, d1: (d1, d0, 27, d1 * 27, 0),
+    "convT": lambda d0, d1: (d1, d0, 27, d1 * 27, 0),
+    "convT_dgrad": lambda d0, d1: (d0, d1, d1 * 27, 27, 0),
+}
+
+
+def c3_prep(w: Tensor, role: str, dtype: torch.dtype) -> Tensor:
+    """prepared GEMM operand [N, 27 * K] of a 3x3x3 weight (fp32 master view) for ``role``"""
+    d0, d1 = w.shape[0], w.shape[1]
+    N, Kc, sn, sc, flip = _C3_ROLES[role](d0, d1)
+    out = torch.empty((N, 27 * Kc), dtype=dtype, device=w.device)
+    check(lib().vsx_conv3d_prep_weight(ptr(w), ptr(out), N, Kc, sn, sc, flip, dtype_code(dtype), stream()), "conv3d_prep_weight")
+    return out
+
+
+def c3_conv(a: Tensor, acoff: int, cin: int, wp: Tensor, bias: Tensor | None, out: Tensor, ccoff: int, cout: int,
+            grid: Sequence[int], stride: int = 1, transposed: bool = False, accumulate: bool = False,
+            want_stats: bool = False) -> Tensor | None:
+    """out[:, ccoff:ccoff+cout] (+)= conv(a[:, acoff:acoff+cin]) + bias; returns the BatchNorm statistics partials if asked"""
+    B, D, H, W = grid
+    if a.dtype != wp.dtype:
+        raise TypeError("conv3d: activation and prepared weight dtypes differ")
+    Mo = B * D * H * W * 8 if transposed else B * (D // stride) * (H // stride) * (W // stride)
+    if a.ndim != 2 or out.ndim != 2 or a.shape[0] != B * D * H * W or out.shape[0] != Mo or acoff + cin > a.shape[1] \
+            or ccoff + cout > out.shape[1] or tuple(wp.shape) != (cout, 27 * cin):
+        raise ValueError(f"conv3d: operand shapes {tuple(a.shape)} / {tuple(wp.shape)} / {tuple(out.shape)} do not fit grid {tuple(grid)}")
+    stats = None
+    if want_stats:
+        rows = lib().vsx_conv3d_stats_rows(B, D, H, W, stride, int(transposed))
+        stats = torch.empty((rows, 2, cout), dtype=torch.float32, device=a.device)
+    out_f32 = int(out.dtype == torch.float32 and a.dtype == torch.bfloat16)
+    if not out_f32 and out.dtype != a.dtype:
+        raise TypeError("conv3d: output dtype must be the operand dtype or float32")
+    check(lib().vsx_conv3d_fwd(ptr(a), a.shape[1], acoff, ptr(wp), ptr(bias), ptr(out), out.shape[1], ccoff, ptr(stats), B, D, H, W,
+                               cin, cout, stride, int(transposed), int(accumulate), dtype_code(a.dtype), out_f32, stream()),
+          "conv3d_fwd")
+    return stats
+
+
+def c3_wgrad(P: Tensor, pcoff: int, R: int, Q: Tensor, qcoff: int, Cq: int, dW: Tensor, gridP: Sequence[int], stride: int) -> None:
+    """dW[r, c, kz, ky, kx] += sum over the voxels m of P's grid of P[m, r] * Q[m * stride + k - 1, c]  (zero outside Q's grid)"""
+    B, D, H, W = gridP
+    if P.dtype != Q.dtype or P.shape[0] != B * D * H * W or Q.shape[0] != P.shape[0] * stride ** 3 or pcoff + R > P.shape[1] \
+            or qcoff + Cq > Q.shape[1] or dW.numel() != R * Cq * 27 or dW.dtype != torch.float32:
+        raise ValueError("conv3d_wgrad: operand shapes do not fit")
+    dt = dtype_code(P.dtype)
+    n = lib().vsx_conv3d_wgrad_ws_floats(B, D, H, W, R, Cq, dt)
+    ws = torch.empty(n, dtype=torch.float32, device=P.device)
+    check(lib().vsx_conv3d_wgrad(ptr(P), P.shape[1], pcoff, ptr(Q), Q.shape[1], qcoff, ptr(ws), n, ptr(dW), B, D, H, W, R, Cq, stride,
+                                 dt, stream()), "conv3d_wgrad")
+
+
+def c3_colsum(x: Tensor, xcoff: int, C: int, out: Tensor) -> None:
+    """out += column sums of x[:, xcoff:xcoff+C] (bias gradients)"""
+    M = x.shape[0]
+    ws = torch.empty(lib().vsx_conv3d_colsum_groups(M) * C, dtype=torch.float32, device=x.device)
+    check(lib().vsx_conv3d_colsum(ptr(x), x.shape[1], xcoff, M, C, ptr(ws), ptr(out), dtype_code(x.dtype), stream()), "conv3d_colsum")
+
+
+def bn3d_finalize(stats: Tensor | None, M: int, C: int, gamma: Tensor, beta: Tensor, rmean: Tensor, rvar: Tensor, nbt: Tensor | None,
+                  training: bool, eps: float = 1e-5, momentum: float = 0.1) -> Tensor:
+    """[4, C] = scale | shift | mean | rstd of the BatchNorm (batch statistics + running-stat update, or running statistics)"""
+    ss = torch.empty((4, C), dtype=torch.float32, device=gamma.device)
+    G = stats.shape[0] if stats is not None else 0
+    check(lib().vsx_bn3d_finalize(ptr(stats) if training else None, G, M, C, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
+                                  ptr(nbt) if training else None, ptr(ss), float(eps), float(momentum), int(training), stream()),
+          "bn3d_finalize")
+    return ss
+
+
+def bn3d_apply_relu(z: Tensor, ss: Tensor, dst: Tensor, dcoff: int) -> None:
+    M, C = z.shape
+    if dst.shape[0] != M or dcoff + C > dst.shape[1] or ss.numel() != 4 * C:
+        raise ValueError("bn3d_apply_relu: destination does not fit")
+    check(lib().vsx_bn3d_apply_relu(ptr(z), ptr(ss), ptr(dst), dst.shape[1], dcoff, M, C, dtype_code(z.dtype), stream()),
+          "bn3d_apply_relu")
+
+
+def bn3d_bwd(dy: Tensor, ycoff: int, z: Tensor, ss: Tensor, gamma: Tensor, dgamma: Tensor, dbeta: Tensor, training: bool) -> Tensor:
+    """dz of relu(batch_norm(z)) for the upstream gradient dy[:, ycoff:ycoff+C]; dgamma / dbeta accumulate"""
+    M, C = z.shape
+    if dy.shape[0] != M or ycoff + C > dy.shape[1] or ss.numel() != 4 * C:
+        raise ValueError("bn3d_bwd: gradient does not fit")
+    ws = torch.empty(lib().vsx_bn3d_bwd_ws_floats(M, C), dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z)
+    check(lib().vsx_bn3d_bwd(ptr(dy), dy.shape[1], ycoff, ptr(z), ptr(ss), ptr(gamma), ptr(ws), ptr(dgamma), ptr(dbeta), ptr(dz), M, C,
+                             int(training), dtype_code(z.dtype), stream()), "bn3d_bwd")
+    return dz
+
+
+def c3_to_cl(x: Tensor, dtype: torch.dtype) -> Tensor:
+    """NCDHW float32 -> channels-last [B*D*H*W, C] in ``dtype``"""
+    if x.dtype != torch.float32:
+        raise TypeError("conv3d_to_cl reads float32")
+    B, C = x.shape[:2]
+    S = x[0, 0].numel()
+    out = torch.empty((B * S, C), dtype=dtype, device=x.device)
+    check(lib().vsx_conv3d_to_cl(ptr(x), ptr(out), B, C, S, dtype_code(dtype), stream()), "conv3d_to_cl")
+    return out
+
+
+def c3_from_cl(y: Tensor, B: int, spatial: Sequence[int]) -> Tensor:
+    """channels-last [B*D*H*W, C] -> NCDHW float32"""
+    C = y.shape[1]
+    out = torch.empty((B, C, *spatial), dtype=torch.float32, device=y.device)
+    S = out[0, 0].numel()
+    check(lib().vsx_conv3d_from_cl(ptr(y), ptr(out), B, C, S, dtype_code(y.dtype), stream()), "conv3d_from_cl")
+    return out

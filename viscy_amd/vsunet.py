@@ -34,10 +34,11 @@ except Exception:  # noqa: BLE001
 
 from .fcmae import FullyConvolutionalMAE  # noqa: E402
 from .unet2d import Unet2d  # noqa: E402
+from .unet3d import Unet3d  # noqa: E402
 
-# cytoland.engine._UNET_ARCHITECTURE (engine.py:36-43): "UNeXt2" / "fcmae" are the accelerated path; "2D" is the reference's
-# CPU plumbing case (BASELINE configs[0]) as a plain-PyTorch module (viscy_amd.unet2d) with torch.optim.AdamW — no kernels
-_UNET_ARCHITECTURE = {"UNeXt2": UNeXt2, "fcmae": FullyConvolutionalMAE, "2D": Unet2d}
+# cytoland.engine._UNET_ARCHITECTURE (engine.py:36-43): "UNeXt2" / "fcmae" / "FNet3D" are the accelerated path; "2D" is the
+# reference's CPU plumbing case (BASELINE configs[0]) as a plain-PyTorch module (viscy_amd.unet2d) with torch.optim.AdamW — no kernels
+_UNET_ARCHITECTURE = {"UNeXt2": UNeXt2, "fcmae": FullyConvolutionalMAE, "2D": Unet2d, "FNet3D": Unet3d}
 
 
 class _TorchOptimizer:
@@ -68,6 +69,12 @@ def _divisible_pad_amounts(shape_yx: Sequence[int], k: int) -> list[tuple[int, i
         tot = (-s) % k
         out.append((tot // 2, tot - tot // 2))
     return out
+
+
+def _make_divisible_pad_amounts(shape: Sequence[int], k: int, pad_z: bool) -> list[tuple[int, int]]:
+    """the reference's _make_divisible_pad: Y and X always; Z as well for a model that downsamples it (FNet3D)"""
+    pads = _divisible_pad_amounts(shape[-3:] if pad_z else shape[-2:], k)
+    return pads if pad_z else [(0, 0)] + pads
 
 
 def _center_crop_to_shape(tensor: Tensor, spatial_shape: Sequence[int]) -> Tensor:
@@ -105,7 +112,7 @@ def blend_in(old_stack: Tensor, new_stack: Tensor, z_slice: slice) -> Tensor:
 class VSUNet(_Base):
     def __init__(
         self,
-        architecture: Literal["UNeXt2", "fcmae", "2D"] = "UNeXt2",
+        architecture: Literal["UNeXt2", "fcmae", "2D", "FNet3D"] = "UNeXt2",
         model_config: dict | None = None,
         loss_function: nn.Module | None = None,
         lr: float = 1e-3,
@@ -130,7 +137,7 @@ class VSUNet(_Base):
         net_class = _UNET_ARCHITECTURE.get(architecture)
         if not net_class:
             raise ValueError(f"Architecture {architecture} not in {_UNET_ARCHITECTURE.keys()} (this build accelerates the "
-                             "UNeXt2 path only)")
+                             "UNeXt2, fcmae and FNet3D paths only)")
         self.model = net_class(**model_config)
         self._native = hasattr(self.model, "engine")  # False: the plain-PyTorch "2D" plumbing model
         if freeze_encoder:  # engine.py:204-206; only the FCMAE network has `.encoder` (as in the reference)
@@ -250,9 +257,10 @@ class VSUNet(_Base):
         if self._predict_pad_k is None:
             self.on_predict_start()
         original_shape = source.shape[2:]
-        (py0, py1), (px0, px1) = _divisible_pad_amounts(source.shape[-2:], self._predict_pad_k)
-        if py0 or py1 or px0 or px1:
-            source = torch.nn.functional.pad(source, (px0, px1, py0, py1))
+        pad_z = bool(getattr(self.model, "downsamples_z", False))
+        (pz0, pz1), (py0, py1), (px0, px1) = _make_divisible_pad_amounts(source.shape, self._predict_pad_k, pad_z)
+        if pz0 or pz1 or py0 or py1 or px0 or px1:
+            source = torch.nn.functional.pad(source, (px0, px1, py0, py1) + ((pz0, pz1) if pad_z else ()))
         if self.predict_graph and source.is_cuda and not torch.is_grad_enabled():
             # tiled inference: every window has the same padded shape -> replay one captured forward per window
             from .step import InferStep
