@@ -23,7 +23,7 @@ def timeit(fn, n=10):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-caps = [int(a.split("=")[1]) for a in sys.argv[1:] if a.startswith("ln_ablk=")] or [512, 1024, 2048, 4096, 0]
+caps = [int(a.split("=")[1]) for a in sys.argv[1:] if a.startswith("ln_ablk=")] or [512, 1024, 2048, 4096]
 dt = torch.bfloat16
 for rows, C in ((512 * 64 * 64, 96), (512 * 32 * 32, 192), (512 * 16 * 16, 384), (512 * 8 * 8, 768)):
     x = torch.randn(rows, C, device="cuda").to(dt)

@@ -12,17 +12,16 @@ int g_vsx_nt_wide = 1;
 int g_vsx_nt_fast = 3;  // bit 0: the lean NT / TN instantiations; bit 1 (round 6): K tails and the 2 x 2 patch gather on the lean NT kernel
 int g_vsx_tn_wide = 1;
 int g_vsx_ggb_blocks = 2048;  // grn_gelu_bwd: target workgroup count (tuning knob, see norm.hip)
-int g_vsx_tn_rect = 11;  // rectangular TN tiles: bit 0 = when N or K is 224..256 wide, bit 1 = 256x128 when 256 divides N (no prologue), bit 2 = 128x256 when 256 divides K (slower: off), bit 3 (round 5) = where the block backward takes its GRN statistics by recomputation (C = 384), the fc2 weight gradient delivers them instead: per-sample products scaled / contracted in the accumulators (gemm_tn_fast_kernel PRO == 2; read by viscy_amd.ops.tn_grn_stats_ok); bits 4 / 5 / 6 (round 6, off): eight-wave workgroups on 256 x 256 tiles for the plain weight gradients with K in [192, 256] (isolated -8 .. -15 %, step +-0), 256 x 192 tiles for K = 384 / 768 (+7 %), 256 x 256 tiles for the per-sample products (+4 .. +10 %)
-int g_vsx_dw_mfma = 15;  // depthwise conv on the matrix cores (dwconv_mfma.hip): bit 0 forward / data gradient (banded Toeplitz tiles), bit 3 the same with its tiles fetched by LDS-DMA two tiles ahead (round 4; whole 32-channel slabs only), bit 1 weight gradient (row contraction, transpose reads), bit 2 16-column weight-gradient tiles at every width (the 32-column variant spills: 471 vs 285 us at 64x64x96, B = 512); 0: VALU stencils
+int g_vsx_tn_rect = 11;  // rectangular TN tiles: bit 0 = when N or K is 224..256 wide, bit 1 = 256x128 when 256 divides N (no prologue), bit 3 (round 5) = where the block backward takes its GRN statistics by recomputation (C = 384), the fc2 weight gradient delivers them instead: per-sample products scaled / contracted in the accumulators (gemm_tn_fast_kernel PRO == 2; read by viscy_amd.ops.tn_grn_stats_ok).  Removed in round 7 with the paths they selected: bit 2 (mirrored 128x256 tiles when 256 divides K, for the GRN-prologue operand: 1.7 .. 2 x slower), bits 4 / 5 / 6 and their split target tn_want3 (eight-wave workgroups on 256 x 256 tiles for the plain weight gradients with K in [192, 256]: isolated -8 .. -15 %, step +-0; 256 x 192 tiles for K = 384 / 768: +7 %; 256 x 256 tiles for the per-sample products: +4 .. +10 %, 1 210 -> 1 340 us at C = 224, 308 -> 320 at C = 192)
+int g_vsx_dw_mfma = 15;  // depthwise conv on the matrix cores (dwconv_mfma.hip): bit 0 forward / data gradient (banded Toeplitz tiles), bit 3 the same with its tiles fetched by LDS-DMA two tiles ahead (round 4; whole 32-channel slabs only), bit 1 weight gradient (row contraction, transpose reads), bit 2 16-column weight-gradient tiles at every width (the 32-column variant spills: 471 vs 285 us at 64x64x96, B = 512), bit 4 the LDS-DMA kernel wherever it can run (A/B knob); 0: VALU stencils.  Removed in round 7: bit 5 (two pixels per LDS access in the LDS-DMA kernel's transposition / gather phases, bit-identical outputs: +-0)
 int g_vsx_ln_fblk = 32768;  // LayerNorm forward: cap on workgroups per launch (each sweeps rows / cap windows).  Measured at B = 512 (64x64x96 / x224): 2048 -> 209 / 438 us, 8192 -> 172 / 351, 32768 -> 162 / 331 (a grid-stride sweep by few workgroups streams at 5.0 TB/s where one vector per thread reaches 6.8: tools/micro/write_rate.hip)
 int g_vsx_ln_bblk = 8192;   // LayerNorm backward WITHOUT affine gradients (the block LayerNorms): cap on workgroups (with dgamma: 512, same-address atomics).  512 -> 319 / 651 us, 2048 -> 254 / 586, 8192 -> 240 / 541 (16x16x384: 83 -> 61), 32768 -> 225 / 516 but 78 at 16x16x384
-int g_vsx_ln_ablk = 512;  // LayerNorm backward WITH affine gradients: workgroup count = same-address atomics per dgamma / dbeta element; 0 = sized from the bytes of the pass (norm.hip ln_launch: isolated launches 336 -> 262 us at C = 96, 171 -> 132 at C = 192; bench step +-0: 91.47 vs 91.38 ms, profiles/r06_ln_affine_cap.txt), so the fixed 512 of rounds 1 - 5 stays
+int g_vsx_ln_ablk = 512;  // LayerNorm backward WITH affine gradients: cap on workgroups = same-address atomics per dgamma / dbeta element.  Removed in round 7: 0 = sized from the bytes of the pass, bytes / (4.5 TB/s x 80 ns) in 256 .. 4 096 (isolated launches 336 -> 262 us at C = 96, 171 -> 132 at C = 192, 91 -> 81 at C = 384; bench step +-0: 91.47 vs 91.38 ms, profiles/r06_ln_affine_cap.txt), so the fixed 512 of rounds 1 - 5 stays
 int g_vsx_ln_pack = 1;  // LayerNorm backward: rows of 24 / 48 16-byte vectors (C = 192 / 384 in bf16) on 8- / 16-lane groups with three vectors per lane instead of 32 / 64 lanes a quarter idle (norm.hip ln_dispatch, round 6)
 int g_vsx_nt_stream = 3;  // (round 4: a non-temporal LDS-DMA of the A panel in the second-generation NT kernel measured 14.9 -> 17.1 ms for the class: not kept) lean NT kernel: bit 0 = non-temporal stores of the wide outputs (fc1 h / g, fc2 data gradient dz): +0.6..1.9 % on the step; bit 1 = non-temporal load of the stored activation in the dZ epilogue (its last reader): +0.7 % (same-box A/B).  ON since round 3: the streaming stores are compiler builtins now (round 1 used inline asm, see vsx_common.h stvec_stream), soak / determinism / poison tests run with them
 int g_vsx_grn_stream = 2;  // grn_gelu_bwd: bit 0 = non-temporal store of dz (no effect), bit 1 = non-temporal load of h, its last reader (-3 % on the kernel)
 int g_vsx_ggb_contig = 1;  // grn_gelu_bwd: contiguous row range per workgroup instead of grid-strided rows
 int g_vsx_tn_fill = 1;  // TN split counts chosen to fill their last round of workgroups (csrc/gemm.hip fill_splits)
-int g_vsx_tn_want3 = 256;  // TN split target of the eight-wave 256 x 256 / 256 x 384 tiles (tn_rect bit 4): workgroups per launch, one per CU
 int g_vsx_tn_want2 = 512;  // TN split target of the rectangular (256 x 128 / 128 x 256) tiles: workgroups per launch
 int g_vsx_tn_p2_rounds = 1;  // weight gradient with GRN statistics (gemm_tn_fast_kernel PRO == 2): rounds of 512 workgroups the split count aims at (0 = power-of-two splits, round-5 first version)
 int g_vsx_tn_want = 768;  // TN split target: workgroups per launch (tiles x splits)
@@ -56,68 +55,33 @@ extern "C" int32_t vsx_det_workspace(float* ws, int64_t floats) {
 extern "C" int32_t vsx_version(void) { return 1; }
 extern "C" const char* vsx_last_error(void) { return g_err; }
 extern "C" const char* vsx_last_kernel(void) { return g_vsx_last_kernel; }
+// every knob once: vsx_set_flag / vsx_get_flag walk this table (declarations for the kernels' files: vsx_common.h)
+static const struct { const char* name; int* value; int32_t min; } g_flags[] = {
+    {"tn_tr", &g_vsx_tn_tr, INT32_MIN},           {"nt_wide", &g_vsx_nt_wide, INT32_MIN},
+    {"nt_fast", &g_vsx_nt_fast, INT32_MIN},       {"tn_wide", &g_vsx_tn_wide, INT32_MIN},
+    {"nt2", &g_vsx_nt2, INT32_MIN},               {"nt_stream", &g_vsx_nt_stream, INT32_MIN},
+    {"grn_stream", &g_vsx_grn_stream, INT32_MIN}, {"ggb_contig", &g_vsx_ggb_contig, INT32_MIN},
+    {"tn_want", &g_vsx_tn_want, INT32_MIN},       {"tn_p2_rounds", &g_vsx_tn_p2_rounds, INT32_MIN},
+    {"tn_want2", &g_vsx_tn_want2, INT32_MIN},     {"tn_fill", &g_vsx_tn_fill, INT32_MIN},
+    {"tn_contig", &g_vsx_tn_contig, INT32_MIN},   {"tn_stream", &g_vsx_tn_stream, INT32_MIN},
+    {"ln_stream", &g_vsx_ln_stream, INT32_MIN},   {"ggb_blocks", &g_vsx_ggb_blocks, INT32_MIN},
+    {"tn_rect", &g_vsx_tn_rect, INT32_MIN},       {"dw_mfma", &g_vsx_dw_mfma, INT32_MIN},
+    {"ln_fblk", &g_vsx_ln_fblk, 1},               {"ln_bblk", &g_vsx_ln_bblk, 1},
+    {"ln_ablk", &g_vsx_ln_ablk, 1},               {"ln_pack", &g_vsx_ln_pack, INT32_MIN},
+    {"mlp_fused", &g_vsx_mlp_fused, INT32_MIN},   {"loss_fused", &g_vsx_loss_fused, INT32_MIN},
+    {"mlp_sf32", &g_vsx_mlp_sf32, INT32_MIN},     {"det_reduce", &g_vsx_det_reduce, INT32_MIN},
+    {"head_rows", &g_vsx_head_rows, INT32_MIN},   {"head_bps", &g_vsx_head_bps, 0},
+};
+
+// an unknown name and a value below the flag's minimum are refused alike
 extern "C" int32_t vsx_set_flag(const char* name, int32_t value) {
-  if (name && !strcmp(name, "tn_tr")) { g_vsx_tn_tr = value; return 0; }
-  if (name && !strcmp(name, "nt_wide")) { g_vsx_nt_wide = value; return 0; }
-  if (name && !strcmp(name, "nt_fast")) { g_vsx_nt_fast = value; return 0; }
-  if (name && !strcmp(name, "tn_wide")) { g_vsx_tn_wide = value; return 0; }
-  if (name && !strcmp(name, "nt2")) { g_vsx_nt2 = value; return 0; }
-  if (name && !strcmp(name, "nt_stream")) { g_vsx_nt_stream = value; return 0; }
-  if (name && !strcmp(name, "grn_stream")) { g_vsx_grn_stream = value; return 0; }
-  if (name && !strcmp(name, "ggb_contig")) { g_vsx_ggb_contig = value; return 0; }
-  if (name && !strcmp(name, "tn_want")) { g_vsx_tn_want = value; return 0; }
-  if (name && !strcmp(name, "tn_p2_rounds")) { g_vsx_tn_p2_rounds = value; return 0; }
-  if (name && !strcmp(name, "tn_want2")) { g_vsx_tn_want2 = value; return 0; }
-  if (name && !strcmp(name, "tn_want3")) { g_vsx_tn_want3 = value; return 0; }
-  if (name && !strcmp(name, "tn_fill")) { g_vsx_tn_fill = value; return 0; }
-  if (name && !strcmp(name, "tn_contig")) { g_vsx_tn_contig = value; return 0; }
-  if (name && !strcmp(name, "tn_stream")) { g_vsx_tn_stream = value; return 0; }
-  if (name && !strcmp(name, "ln_stream")) { g_vsx_ln_stream = value; return 0; }
-  if (name && !strcmp(name, "ggb_blocks")) { g_vsx_ggb_blocks = value; return 0; }
-  if (name && !strcmp(name, "tn_rect")) { g_vsx_tn_rect = value; return 0; }
-  if (name && !strcmp(name, "dw_mfma")) { g_vsx_dw_mfma = value; return 0; }
-  if (name && !strcmp(name, "ln_fblk") && value > 0) { g_vsx_ln_fblk = value; return 0; }
-  if (name && !strcmp(name, "ln_bblk") && value > 0) { g_vsx_ln_bblk = value; return 0; }
-  if (name && !strcmp(name, "ln_ablk") && value >= 0) { g_vsx_ln_ablk = value; return 0; }
-  if (name && !strcmp(name, "ln_pack")) { g_vsx_ln_pack = value; return 0; }
-  if (name && !strcmp(name, "mlp_fused")) { g_vsx_mlp_fused = value; return 0; }
-  if (name && !strcmp(name, "loss_fused")) { g_vsx_loss_fused = value; return 0; }
-  if (name && !strcmp(name, "mlp_sf32")) { g_vsx_mlp_sf32 = value; return 0; }
-  if (name && !strcmp(name, "det_reduce")) { g_vsx_det_reduce = value; return 0; }
-  if (name && !strcmp(name, "head_rows")) { g_vsx_head_rows = value; return 0; }
-  if (name && !strcmp(name, "head_bps") && value >= 0) { g_vsx_head_bps = value; return 0; }
+  for (const auto& f : g_flags)
+    if (name && !strcmp(name, f.name) && value >= f.min) { *f.value = value; return 0; }
   vsx_set_error("vsx_set_flag: unknown flag '%s'", name ? name : "(null)");
   return 1;
 }
 extern "C" int32_t vsx_get_flag(const char* name) {
-  if (name && !strcmp(name, "tn_tr")) return g_vsx_tn_tr;
-  if (name && !strcmp(name, "nt_wide")) return g_vsx_nt_wide;
-  if (name && !strcmp(name, "nt_fast")) return g_vsx_nt_fast;
-  if (name && !strcmp(name, "tn_wide")) return g_vsx_tn_wide;
-  if (name && !strcmp(name, "nt2")) return g_vsx_nt2;
-  if (name && !strcmp(name, "nt_stream")) return g_vsx_nt_stream;
-  if (name && !strcmp(name, "grn_stream")) return g_vsx_grn_stream;
-  if (name && !strcmp(name, "ggb_contig")) return g_vsx_ggb_contig;
-  if (name && !strcmp(name, "tn_want")) return g_vsx_tn_want;
-  if (name && !strcmp(name, "tn_p2_rounds")) return g_vsx_tn_p2_rounds;
-  if (name && !strcmp(name, "tn_want2")) return g_vsx_tn_want2;
-  if (name && !strcmp(name, "tn_want3")) return g_vsx_tn_want3;
-  if (name && !strcmp(name, "tn_fill")) return g_vsx_tn_fill;
-  if (name && !strcmp(name, "tn_contig")) return g_vsx_tn_contig;
-  if (name && !strcmp(name, "tn_stream")) return g_vsx_tn_stream;
-  if (name && !strcmp(name, "ln_stream")) return g_vsx_ln_stream;
-  if (name && !strcmp(name, "ggb_blocks")) return g_vsx_ggb_blocks;
-  if (name && !strcmp(name, "tn_rect")) return g_vsx_tn_rect;
-  if (name && !strcmp(name, "dw_mfma")) return g_vsx_dw_mfma;
-  if (name && !strcmp(name, "ln_fblk")) return g_vsx_ln_fblk;
-  if (name && !strcmp(name, "ln_bblk")) return g_vsx_ln_bblk;
-  if (name && !strcmp(name, "ln_ablk")) return g_vsx_ln_ablk;
-  if (name && !strcmp(name, "ln_pack")) return g_vsx_ln_pack;
-  if (name && !strcmp(name, "mlp_fused")) return g_vsx_mlp_fused;
-  if (name && !strcmp(name, "loss_fused")) return g_vsx_loss_fused;
-  if (name && !strcmp(name, "mlp_sf32")) return g_vsx_mlp_sf32;
-  if (name && !strcmp(name, "det_reduce")) return g_vsx_det_reduce;
-  if (name && !strcmp(name, "head_rows")) return g_vsx_head_rows;
-  if (name && !strcmp(name, "head_bps")) return g_vsx_head_bps;
+  for (const auto& f : g_flags)
+    if (name && !strcmp(name, f.name)) return *f.value;
   return -1;
 }

@@ -314,16 +314,9 @@ static __device__ __forceinline__ void dwd_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// PAIR (round 6): the LDS -> LDS transposition and the gather back out of the planes move TWO horizontally adjacent pixels per
-// access — 32-bit words [col, col + 1] of a channel plane instead of 2-byte elements: 8 ds_write_b32 per 2 x 16-byte piece where
-// the first version issued 16 ds_write_b16, 8 ds_read_b32 by half of the threads where all of them issued 8 ds_read_u16.  A tile
-// of this kernel is ~43 LDS instructions per wave against 14 MFMAs (profiles/r05_sq_counters.txt: 4.14e8 / 1.42e8), 24 of them these
-// 2-byte accesses.  Planes of PAIR builds are skewed by 32 elements per 8 channels (the four 8-channel vectors of 16 pixel pairs
-// land on 4 x 16 distinct banks).  Same arithmetic, bit-identical outputs.
-template <bool PAIR>
-static __device__ __forceinline__ int dwd_plane_base(int ch) { return ch * DWD_PLANE + (ch >> 3) * (PAIR ? 32 : 16); }
+static __device__ __forceinline__ int dwd_plane_base(int ch) { return ch * DWD_PLANE + (ch >> 3) * 16; }
 
-template <bool FLIP, int CB, bool PAIR = false>
+template <bool FLIP, int CB>
 __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
                                                                        const float* __restrict__ bias,
                                                                        const bf16_t* __restrict__ add, bf16_t* __restrict__ y,
@@ -392,7 +385,7 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
       int r = i / PADW;
       const int row = r % DWM_ROWS;
       const int ch = r / DWM_ROWS;
-      planes[dwd_plane_base<PAIR>(ch) + row * DWD_PITCH + col] = 0;
+      planes[dwd_plane_base(ch) + row * DWD_PITCH + col] = 0;
     }
   }
 
@@ -464,25 +457,6 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
     dwd_dma16(src, dst + wave * 1024);
   };
   auto transpose_in = [&](const char* rawb) {
-    if constexpr (PAIR) {
-      constexpr int XPAIRS = DWM_ROWS * (DWD_IW / 2) * PP;  // (pixel pair, 8-channel vector) items of a halo tile: 968 at CB = 32
-      static_assert(!PAIR || (XPAIRS <= THREADS && DWD_IW % 2 == 0), "one pixel pair per thread");
-      if (tid < XPAIRS) {
-        const int cv = tid % PP, pp = tid / PP;
-        const int colp = pp % (DWD_IW / 2), row = pp / (DWD_IW / 2);
-        const int ia = (row * DWD_IW + 2 * colp) * PP + cv;     // raw piece of the left pixel; the right one is PP pieces on
-        const uint4 va = *reinterpret_cast<const uint4*>(rawb + (size_t)ia * 16);
-        const uint4 vb = *reinterpret_cast<const uint4*>(rawb + (size_t)(ia + PP) * 16);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(&planes[dwd_plane_base<PAIR>(cv * 8) + row * DWD_PITCH + 2 * colp]);
-        const uint32_t da[4] = {va.x, va.y, va.z, va.w}, db[4] = {vb.x, vb.y, vb.z, vb.w};
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2) {
-          dst[(e2 * 2) * (DWD_PLANE / 2)] = __builtin_amdgcn_perm(db[e2], da[e2], 0x05040100u);      // {a.lo, b.lo}
-          dst[(e2 * 2 + 1) * (DWD_PLANE / 2)] = __builtin_amdgcn_perm(db[e2], da[e2], 0x07060302u);  // {a.hi, b.hi}
-        }
-      }
-      return;
-    }
 #pragma unroll
     for (int it = 0; it < G::XIT; ++it) {
       const int i = tid + it * THREADS;
@@ -490,7 +464,7 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
         const int cv = i % PP, p = i / PP;
         const int col = p % DWD_IW, row = p / DWD_IW;
         const uint4 v = *reinterpret_cast<const uint4*>(rawb + (size_t)i * 16);
-        unsigned short* dst = &planes[dwd_plane_base<PAIR>(cv * 8) + row * DWD_PITCH + col];
+        unsigned short* dst = &planes[dwd_plane_base(cv * 8) + row * DWD_PITCH + col];
         const uint32_t d[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int e2 = 0; e2 < 4; ++e2) {
@@ -520,7 +494,7 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
 #pragma unroll
     for (int cc = 0; cc < CPW; ++cc) {
       const int chl = wave * CPW + cc;
-      unsigned short* plane = &planes[dwd_plane_base<PAIR>(chl)];
+      unsigned short* plane = &planes[dwd_plane_base(chl)];
       dwm_f32x4 acc = dwm_f32x4{bias_v[cc], bias_v[cc], bias_v[cc], bias_v[cc]};
 #pragma unroll
       for (int ky = 0; ky < 7; ++ky) {
@@ -538,65 +512,24 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
     // x(t+1) and add(t) are older.  add(t+1) is needed by the NEXT gather only, so it may stay in flight as well.
     wait_older_than((add && more1 ? 1 : 0) + (more2 ? nx : 0));
     dwd_barrier();                                    // H: every plane holds its channel's outputs
-    if constexpr (PAIR) {
-      if (tid < 128 * PP) {  // (pixel pair, 8-channel vector) items of the 16 x 16 outputs
-        const int cv = tid % PP, pp = tid / PP;
-        const int colp = pp & 7, row = pp >> 3;
-        const int gy = at.y0 + row, gx = at.x0 + 2 * colp;
-        if (gy < H && gx < W) {
-          const uint32_t* src = reinterpret_cast<const uint32_t*>(&planes[dwd_plane_base<PAIR>(cv * 8) + row * DWD_PITCH + 2 * colp]);
-          uint32_t w[8];
+    const int cv = ocv, col = ocol, row = orow;
+    const int gy = at.y0 + row, gx = at.x0 + col;
+    if (gy < H && gx < W) {
+      const unsigned short* src = &planes[dwd_plane_base(cv * 8) + row * DWD_PITCH + col];
+      uint32_t d[4];
 #pragma unroll
-          for (int e = 0; e < 8; ++e) w[e] = src[e * (DWD_PLANE / 2)];
-          uint4 oa, ob;
-          oa.x = __builtin_amdgcn_perm(w[1], w[0], 0x05040100u); ob.x = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u);
-          oa.y = __builtin_amdgcn_perm(w[3], w[2], 0x05040100u); ob.y = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
-          oa.z = __builtin_amdgcn_perm(w[5], w[4], 0x05040100u); ob.z = __builtin_amdgcn_perm(w[5], w[4], 0x07060302u);
-          oa.w = __builtin_amdgcn_perm(w[7], w[6], 0x05040100u); ob.w = __builtin_amdgcn_perm(w[7], w[6], 0x07060302u);
-          const int ip = (row * 16 + 2 * colp) * PP + cv;  // shortcut piece of the left pixel in `addc`
-          const size_t off = (size_t)tile_origin(at) + (size_t)((row * W + 2 * colp) * C + cv * 8);
-          if (add) {
-            float a[8], f[8];
-            unpack<bf16_t>(*reinterpret_cast<const uint4*>(addc + (size_t)ip * 16), a);
-            unpack<bf16_t>(oa, f);
+      for (int e2 = 0; e2 < 4; ++e2)
+        d[e2] = (uint32_t)src[(e2 * 2) * DWD_PLANE] | ((uint32_t)src[(e2 * 2 + 1) * DWD_PLANE] << 16);
+      uint4 o = make_uint4(d[0], d[1], d[2], d[3]);
+      if (add) {
+        float a[8], f[8];
+        unpack<bf16_t>(*reinterpret_cast<const uint4*>(addc + (size_t)tid * 16), a);
+        unpack<bf16_t>(o, f);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] += a[j];
-            oa = pack<bf16_t>(f);
-          }
-          *reinterpret_cast<uint4*>(y + off) = oa;
-          if (gx + 1 < W) {
-            if (add) {
-              float a[8], f[8];
-              unpack<bf16_t>(*reinterpret_cast<const uint4*>(addc + (size_t)(ip + PP) * 16), a);
-              unpack<bf16_t>(ob, f);
-#pragma unroll
-              for (int j = 0; j < 8; ++j) f[j] += a[j];
-              ob = pack<bf16_t>(f);
-            }
-            *reinterpret_cast<uint4*>(y + off + C) = ob;
-          }
-        }
+        for (int j = 0; j < 8; ++j) f[j] += a[j];
+        o = pack<bf16_t>(f);
       }
-    } else {
-      const int cv = ocv, col = ocol, row = orow;
-      const int gy = at.y0 + row, gx = at.x0 + col;
-      if (gy < H && gx < W) {
-        const unsigned short* src = &planes[dwd_plane_base<PAIR>(cv * 8) + row * DWD_PITCH + col];
-        uint32_t d[4];
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2)
-          d[e2] = (uint32_t)src[(e2 * 2) * DWD_PLANE] | ((uint32_t)src[(e2 * 2 + 1) * DWD_PLANE] << 16);
-        uint4 o = make_uint4(d[0], d[1], d[2], d[3]);
-        if (add) {
-          float a[8], f[8];
-          unpack<bf16_t>(*reinterpret_cast<const uint4*>(addc + (size_t)tid * 16), a);
-          unpack<bf16_t>(o, f);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) f[j] += a[j];
-          o = pack<bf16_t>(f);
-        }
-        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(y + tile_origin(at)) + obyte) = o;
-      }
+      *reinterpret_cast<uint4*>(reinterpret_cast<char*>(y + tile_origin(at)) + obyte) = o;
     }
   };
 
@@ -777,8 +710,6 @@ __global__ __launch_bounds__(DWM_THREADS) void dwconv7_wgrad_mfma_kernel(const b
   }
 }
 
-extern int g_vsx_dw_mfma;
-
 // *taken = 1 when the launch went to the MFMA path, 0 when the caller should use the VALU stencil; returns 0 or an error code
 int vsx_dwconv7_mfma_try(const void* x, const float* w, const float* bias, const void* add, void* y, int B, int H, int W, int C,
                          bool flip, hipStream_t s, int* taken) {
@@ -816,13 +747,11 @@ int vsx_dwconv7_mfma_try(const void* x, const float* w, const float* bias, const
 #define DWM_LAUNCH(NXT, FLIP)                                                                                          \
   hipLaunchKernelGGL((dwconv7_mfma_kernel<NXT, FLIP>), dim3(grid), dim3(DWM_THREADS), 0, s, (const bf16_t*)x, w, bias,  \
                      (const bf16_t*)add, (bf16_t*)y, B, H, W, C, nslab, tiles, per)
-#define DWD_LAUNCH(FLIP, CBV, PAIRV)                                                                                            \
-  hipLaunchKernelGGL((dwconv7_mfma_dma_kernel<FLIP, CBV, PAIRV>), dim3(grid), dim3(CBV * 32), 0, s, (const bf16_t*)x, w, bias,   \
+#define DWD_LAUNCH(FLIP, CBV)                                                                                         \
+  hipLaunchKernelGGL((dwconv7_mfma_dma_kernel<FLIP, CBV>), dim3(grid), dim3(CBV * 32), 0, s, (const bf16_t*)x, w, bias,  \
                      (const bf16_t*)add, (bf16_t*)y, B, H, W, C, nslab, tiles, per)
-  if (dma && (g_vsx_dw_mfma & 32)) {  // bit 5 (round 6): two pixels per LDS access in the transposition / gather phases
-    if (flip) DWD_LAUNCH(true, 32, true); else DWD_LAUNCH(false, 32, true);
-  } else if (dma) {
-    if (flip) DWD_LAUNCH(true, 32, false); else DWD_LAUNCH(false, 32, false);
+  if (dma) {
+    if (flip) DWD_LAUNCH(true, 32); else DWD_LAUNCH(false, 32);
   } else if (nxt == 2) {
     if (flip) DWM_LAUNCH(2, true); else DWM_LAUNCH(2, false);
   } else {

@@ -17,19 +17,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-extern int g_vsx_tn_tr;
-extern int g_vsx_tn_rect;
-extern int g_vsx_nt_wide;
-extern int g_vsx_nt_fast;
-extern int g_vsx_tn_wide;
-extern int g_vsx_nt_stream;
-extern int g_vsx_tn_want;
-extern int g_vsx_tn_p2_rounds;
-extern int g_vsx_tn_want2;
-extern int g_vsx_tn_want3;
-extern int g_vsx_tn_fill;
-extern int g_vsx_tn_contig;
-extern int g_vsx_tn_stream;
 bool vsx_gemm_nt2_ok(const VsxGemm* p);           // gemm_nt2.hip
 bool vsx_gemm_nt2_lnbwd_ok(const VsxGemm* p);
 int vsx_gemm_nt2(const VsxGemm* p, hipStream_t s);
@@ -856,7 +843,7 @@ static int launch_nt_fast(const VsxGemm* pin, hipStream_t s) {
 static bool nt_fast_ok(const VsxGemm* p, int es) {
   // round 6 (nt_fast bit 1): K tails (K % 32 != 0: whole 16-byte chunks, zero-filled last slab) and the 2 x 2 patch gather
   const bool ext = (g_vsx_nt_fast & 2) != 0;
-  if (!g_vsx_nt_fast || p->N <= 64) return false;
+  if (!(g_vsx_nt_fast & 1) || p->N <= 64) return false;
   if (p->c_mode != VSX_A_ROWS && !(ext && p->c_mode == VSX_A_PATCH2 && p->a_mode == VSX_A_ROWS && p->pro != VSX_PRO_GRN && p->b_bstride == 0 &&
                                    (p->epi == VSX_EPI_NONE || p->epi == VSX_EPI_BIAS)))
     return false;
@@ -1208,22 +1195,16 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const VsxGemm p, int rows_
 // The beta term is the rank-1 product (column sums of X) x beta, added once at the end; the column sums come from one extra MFMA
 // per X fragment against a ones operand.  By itself the post-scaled form is as fast as the prologue form (the launch is bound by
 // its operand stream, not by the prologue: 320 us plain vs 343 us at C = 384, B = 512); what it buys is the MODE 3 launch.
-// WG = 512 (round 6): eight waves as a 4 (N) x 2 (K) grid on ONE workgroup per CU — 256 x 256 and 256 x 384 output tiles.  The
-// split-K launches are bound by their operand stream L2 -> LDS (~10 TB/s chip-wide, section 3 item 18): a 128 x 256 tile moves
-// (128 + 256) / (128 * 256) operand elements per MAC, a 256 x 384 tile 1.8 x fewer, and an operand whose whole width fits the tile
-// is read exactly once by the launch.
-template <typename T, int BT, bool TR, int PRO, int BMS = 32, int NBUF = 2, int BTK_ = 0, int WG = 256>
-__global__ __launch_bounds__(WG, WG == 512 ? 1 : ((BTK_ != 0 || PRO == 2) ? 2 : ((BMS == 64 && TR && sizeof(T) == 2) ? 3 : 1))) void gemm_tn_fast_kernel(const VsxGemm p) {
+template <typename T, int BT, bool TR, int PRO, int BMS = 32, int NBUF = 2, int BTK_ = 0>
+__global__ __launch_bounds__(256, (BTK_ != 0 || PRO == 2) ? 2 : ((BMS == 64 && TR && sizeof(T) == 2) ? 3 : 1)) void gemm_tn_fast_kernel(const VsxGemm p) {
   constexpr int ES = sizeof(T);
   constexpr int VN = VT<T>::N;
   constexpr int BTN = BT, BTK = BTK_ != 0 ? BTK_ : BT;
   constexpr int LDBX = (BTN + 16) * ES, LDBY = (BTK + 16) * ES;
   constexpr int CPRX = BTN / VN, CPRY = BTK / VN;
-  constexpr int NCHX = (BMS * CPRX + WG - 1) / WG, NCHY = (BMS * CPRY + WG - 1) / WG;
-  constexpr int WN = WG / 128;  // wave rows (N) x 2 wave columns (K)
-  static_assert(WG == 256 || (WG == 512 && PRO == 0), "the eight-wave geometry serves the plain weight gradients");
+  constexpr int NCHX = (BMS * CPRX + 255) / 256, NCHY = (BMS * CPRY + 255) / 256;
   constexpr int TILE_X = BMS * LDBX, TILE_Y = BMS * LDBY;
-  constexpr int FN_ = BTN / WN / 16, FK_ = BTK / 2 / 16;
+  constexpr int FN_ = BTN / 2 / 16, FK_ = BTK / 2 / 16;  // 2 wave rows (N) x 2 wave columns (K)
   constexpr int MK = Frag<T>::MK;
   typedef typename VT<T>::vec vec;
   typedef typename Frag<T>::type frag_t;
@@ -1261,7 +1242,7 @@ __global__ __launch_bounds__(WG, WG == 512 ? 1 : ((BTK_ != 0 || PRO == 2) ? 2 : 
   bool livex[NCHX], livey[NCHY];
 #pragma unroll
   for (int i = 0; i < NCHX; ++i) {
-    const int cid = tid + i * WG, crow = cid / CPRX, cch = cid % CPRX;
+    const int cid = tid + i * 256, crow = cid / CPRX, cch = cid % CPRX;
     livex[i] = cid < BMS * CPRX;
     int nn = n0 + cch * VN;
     nn = nn < p.N ? nn : p.N - VN;
@@ -1270,7 +1251,7 @@ __global__ __launch_bounds__(WG, WG == 512 ? 1 : ((BTK_ != 0 || PRO == 2) ? 2 : 
   }
 #pragma unroll
   for (int i = 0; i < NCHY; ++i) {
-    const int cid = tid + i * WG, crow = cid / CPRY, cch = cid % CPRY;
+    const int cid = tid + i * 256, crow = cid / CPRY, cch = cid % CPRY;
     livey[i] = cid < BMS * CPRY;
     int kk = k0 + cch * VN;
     kk = kk < p.K ? kk : p.K - VN;
@@ -1613,7 +1594,7 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
     // (plain stores: the caller need not zero the outputs).  Used by the block backward: the per-sample products dout_b^T g_b
     // give the fc2 weight gradient AND the GRN statistics P, S without ever forming dz (vsx_grn_q_reduce).
     if constexpr (sizeof(T) == 2 && BT == 128 && TR) {
-      VSX_CHECK(g_vsx_nt_fast && p->a_mode == VSX_A_ROWS && p->pro == VSX_PRO_NONE && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 &&
+      VSX_CHECK((g_vsx_nt_fast & 1) && p->a_mode == VSX_A_ROWS && p->pro == VSX_PRO_NONE && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 &&
                     nz == 1 && (unsigned long long)64 * (p->lda > p->ldb ? p->lda : p->ldb) * sizeof(T) < (1ull << 31),
                 "vsx_gemm_tn: per-sample outputs (b_bstride) need plain bf16 row operands, no prologue, hw %% 64 == 0");
       VsxGemm pq = *p;
@@ -1623,8 +1604,7 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
       // N = 192 too since round 4: a quarter of the 256-wide tile idles, but the 4C-wide operand is read once instead of twice and,
       // with its loads non-temporal (tn_stream), the launch is 4 % faster than on 128 x 128 tiles (328 -> 315 us at B = 512)
       const bool n_full = p->N >= 192 && p->N <= 256 && p->K >= 128;
-      const bool big = TR && (g_vsx_tn_rect & 64) && n_full && p->K >= 512;  // round 6, bit 6 (off: 1 210 -> 1 340 us at C = 224, 308 -> 320 at C = 192): eight-wave 256 x 256 tiles, one workgroup per CU
-      const int t2 = big ? vsx_cdiv(p->K, 256) : (n_full ? vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, 128) : tiles);
+      const int t2 = n_full ? vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, 128) : tiles;
       // few samples with large maps (the 2048^2 gate shape: 8 samples of 262 144 rows): ks splits per sample so that the launch
       // still fills the chip; their partial products meet in zero-filled outputs through atomics (<= ks adds per address)
       int ks = 1;
@@ -1633,7 +1613,7 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
       if (g_vsx_tn_fill && ks > 1) {
         // ... and of the power-of-two counts from there up to 4 x, the one that fills its last round of workgroups best (2 per CU for
         // the 256-wide tiles, 3 for the square ones): 8 samples x 36 tiles x 4 ran 1.5 rounds at the gate shape's C = 384 blocks
-        const int slots = 256 * (big ? 1 : (n_full ? 2 : 3));
+        const int slots = 256 * (n_full ? 2 : 3);
         int best = ks;
         double bf = -1.0;
         for (int k2 = ks; k2 <= 4 * ks && k2 <= 64 && spp % k2 == 0; k2 *= 2) {
@@ -1649,10 +1629,7 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
         hipLaunchKernelGGL(tn_zero_kernel, dim3(vsx_cdiv(nq, 1024L)), dim3(256), 0, s, reinterpret_cast<float*>(p->C) + p->c_coff[0], nq);
         if (nc) hipLaunchKernelGGL(tn_zero_kernel, dim3(vsx_cdiv(nc, 1024L)), dim3(256), 0, s, p->colsum, nc);
       }
-      if (big) {
-        dim3 g2(t2, nb * ks, 1);
-        hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, false, 32, 2, 256, 512>), g2, dim3(512), 0, s, pq);
-      } else if (n_full) {
+      if (n_full) {
         dim3 g2(t2, nb * ks, 1);
         hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, false, 64, 1, 128>), g2, dim3(256), 0, s, pq);
       } else {
@@ -1671,7 +1648,7 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
     // passing the bf16 fc2 weight as `aux` ([N, ldx]) and the statistics target as `red0` ([M / hw, K], zeroed); whole samples per
     // split, 64-row steps inside one sample.  (Without aux / red0 the prologue kernel below is as fast: nothing to gain.)
     if (p->pro == VSX_PRO_GRN && p->aux != nullptr && p->red0 != nullptr) {
-      VSX_CHECK(g_vsx_nt_fast && p->a_mode == VSX_A_ROWS && nz == 1 && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 && p->N >= 96 &&
+      VSX_CHECK((g_vsx_nt_fast & 1) && p->a_mode == VSX_A_ROWS && nz == 1 && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 && p->N >= 96 &&
                     p->K >= 128 && p->N % 8 == 0 && p->K % 8 == 0 && p->ldx >= p->K &&
                     (unsigned long long)64 * (p->lda > p->ldb ? p->lda : p->ldb) * sizeof(T) < (1ull << 31),
                 "vsx_gemm_tn: the weight gradient with GRN statistics (aux = W2, red0 = P) needs plain bf16 row operands, hw %% 64 == 0, N >= 96, K >= 128");
@@ -1700,7 +1677,7 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
   dim3 grid(tiles, splits, nz);
   const bool patch_ok = (g_vsx_nt_fast & 2) && p->a_mode == VSX_A_PATCH2 && p->pro == VSX_PRO_NONE && p->gw > 0 && (32 % p->gw == 0 || p->gw % 64 == 0) &&
                         p->cs % VT<T>::N == 0 && (unsigned long long)(512 + 4 * p->gw) * p->lda * sizeof(T) < (1ull << 31);
-  const bool fast = g_vsx_nt_fast && (p->a_mode == VSX_A_ROWS || patch_ok) && p->M % 32 == 0 && p->N >= VT<T>::N && p->K >= VT<T>::N &&
+  const bool fast = (g_vsx_nt_fast & 1) && (p->a_mode == VSX_A_ROWS || patch_ok) && p->M % 32 == 0 && p->N >= VT<T>::N && p->K >= VT<T>::N &&
                     (p->pro == VSX_PRO_NONE || (p->pro == VSX_PRO_GRN && p->hw > 0 && p->hw % 32 == 0)) &&
                     (unsigned long long)32 * (p->lda > p->ldb ? p->lda : p->ldb) * sizeof(T) < (1ull << 31);
   if (fast) {
@@ -1715,35 +1692,14 @@ static int launch_tn(const VsxGemm* p, hipStream_t s) {
           grid.y = splits = spf < 1 ? 1 : spf;
         }
         if constexpr (TR) {
-          // round 6, tn_rect bit 4: eight-wave workgroups on 256 x 256 / 256 x 384 tiles (one per CU) for the plain weight gradients
-          // whose K side fits (or divides into) such a tile: dW1 of the C = 192 / 224 (256 wide), C = 384 / 768 (384 wide) blocks
-          if ((g_vsx_tn_rect & 16) && p->pro == VSX_PRO_NONE && p->a_mode == VSX_A_ROWS && p->N >= 512 && p->M % 32 == 0) {
-            // (a 256 x 384 tile — the K side of the C = 384 / 768 gradients in one tile — needs 192 accumulator registers and spilled
-            // 60 - 105: 228 -> 410 us.  Those launches take 192-wide K tiles instead: tn_rect bit 5)
-            const int btk = (p->K >= 192 && p->K <= 256) ? 256 : (((g_vsx_tn_rect & 32) && p->K > 256 && p->K % 192 == 0) ? 192 : 0);
-            if (btk) {
-              const int t3 = vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, btk);
-              int sp3 = vsx_cdiv(g_vsx_tn_want3, t3 * nz);
-              if (sp3 > p->M / 64) sp3 = p->M / 64;
-              if (g_vsx_tn_fill) sp3 = fill_splits(t3 * nz, 1, sp3, p->M / 64);
-              if (sp3 < 1) sp3 = 1;
-              dim3 g3(t3, sp3, nz);
-              if (btk == 192) hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, false, 32, 2, 192, 512>), g3, dim3(512), 0, s, pq);
-              else hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, false, 32, 2, 256, 512>), g3, dim3(512), 0, s, pq);
-              VSX_LAUNCH_CHECK();
-              return 0;
-            }
-          }
           // rectangular tiles when one side of the weight gradient fits a single 256-wide tile (see the kernel's header)
           // measured (tools/perf_nt.py, B = 512): C = 224 -9 % (dW1) / -14 % (dW2); C = 192 +4..8 % (a quarter of the
           // 256-wide tile idles) -> only when the tile is >= 7/8 full
           // bit 1: 256x128 tiles also when 256 divides N exactly and there is no prologue (dW1 of the C = 192 / 384 / 768
-          // stages: -5..-11 % on those launches); bit 2 (off): the mirrored 128x256 tiles for the GRN-prologue operand —
-          // measured 1.7..2x SLOWER (twice the prologue work per workgroup at 2 workgroups per CU)
+          // stages: -5..-11 % on those launches)
           const bool n_div = (g_vsx_tn_rect & 2) && p->N % 256 == 0 && p->K >= 128 && p->pro == VSX_PRO_NONE;
-          const bool k_div = (g_vsx_tn_rect & 4) && !n_div && p->K % 256 == 0 && p->N >= 128;
           const bool n_full = ((g_vsx_tn_rect & 1) && p->N >= 224 && p->N <= 256 && p->K >= 256) || n_div;
-          const bool k_full = ((g_vsx_tn_rect & 1) && !n_full && p->K >= 224 && p->K <= 256 && p->N >= 256) || (k_div && !n_full);
+          const bool k_full = (g_vsx_tn_rect & 1) && !n_full && p->K >= 224 && p->K <= 256 && p->N >= 256;
           if (n_full || k_full) {
             const int t2 = n_full ? vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, 128) : vsx_cdiv(p->N, 128) * vsx_cdiv(p->K, 256);
             int want2 = vsx_cdiv(g_vsx_tn_want2, t2 * nz), sp2 = want2 < 1 ? 1 : (want2 > max_splits ? max_splits : want2);

@@ -36,8 +36,6 @@
 typedef __attribute__((ext_vector_type(4))) float nt2_f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 nt2_bf16x8;
 
-extern int g_vsx_nt2;
-
 namespace {
 
 constexpr int BM = 256, BK = 32, NST = 3;

@@ -961,9 +961,6 @@ struct MlpCfg { int C, MF, NW, modes; };  // modes: bit m set = this geometry se
 // 4, no fc2 accumulators) fit 8 waves at <= 256 registers and sit behind bit 2 of the mlp_fused flag (fc1 -12 %, backward -4 %,
 // -0.7 GB per block and step at B = 512).  The C = 384 inference pair (the output pass needs 192 accumulator registers: 4 waves x
 // 32 rows at one wave per SIMD, 875 us against 614 us for the unfused GEMMs at B = 512) was removed in round 4 (flag bit 4).
-extern int g_vsx_mlp_fused;
-extern int g_vsx_mlp_sf32;
-extern int g_vsx_nt_stream;
 static inline int mlp_nt() { return (g_vsx_nt_stream >> 2) & 15; }  // bits 2 / 3 of nt_stream: the fused passes' stores / last-reader loads; bits 4 / 5: static wave priority (A/B knob, see the kernel)
 static const MlpCfg kMlpCfgs[] = {{96, 2, 8, 255}, {192, 2, 8, 255}, {224, 2, 8, 255}, {384, 2, 8, 4 | 8 | 16}};
 

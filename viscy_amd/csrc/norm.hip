@@ -5,9 +5,6 @@
 #include "vsx_common.h"
 #include "wtasks.h"
 #include "../../include/vsx.h"
-extern int g_vsx_grn_stream;
-extern int g_vsx_ggb_contig;
-extern int g_vsx_ln_stream;
 
 // ------------------------------------------------------------------ LayerNorm forward
 template <typename T, int G, int CPL>
@@ -230,10 +227,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   }
 }
 
-extern int g_vsx_ln_fblk;
-extern int g_vsx_ln_bblk;
-extern int g_vsx_ln_ablk;
-extern int g_vsx_ln_pack;
 template <typename T, int G, int CPL>
 static int ln_launch(bool fwd, const void* a0, const void* a1, void* out, float* mean, float* rstd,
                      const float* gamma, const float* beta, const void* add, float* dgamma, float* dbeta, int rows,
@@ -250,18 +243,10 @@ static int ln_launch(bool fwd, const void* a0, const void* a1, void* out, float*
     hipLaunchKernelGGL((ln_fwd_kernel<T, G, CPL>), dim3(vsx_cdiv(rows, RPI * R * iters)), dim3(256), 0, s, (const T*)a0,
                        (T*)out, mean, rstd, gamma, beta, rows, C, eps, iters, g_vsx_ln_stream & 2);
   } else {
-    // with an affine LayerNorm: <= 512 blocks → <= 512 same-address atomics on dgamma / dbeta; the block LayerNorms have no
+    // with an affine LayerNorm: <= ln_ablk (512) workgroups → as many same-address atomics on dgamma / dbeta, which retire at
+    // ~40 ns each (tools/perf_ln.py: 8 192 workgroups at C = 768 take 339 us for a 33 us stream); the block LayerNorms have no
     // affine here (folded into fc1) and no such limit — their cap is the flag ln_bblk
-    // affine: every workgroup ends with one atomic per dgamma / dbeta element, and same-address atomics retire at ~40 ns each
-    // (tools/perf_ln.py: 8 192 workgroups at C = 768 take 339 us for a 33 us stream), so the workgroup count is what the pass
-    // can stream meanwhile: bytes / (4.5 TB/s x 80 ns), 256 .. 4 096 (C = 96 / 192 / 384 at B = 512: 336 -> 262, 171 -> 132,
-    // 91 -> 81 us against the fixed 512 of rounds 1 - 5); ln_ablk != 0 forces a count
-    int acap = g_vsx_ln_ablk;
-    if (dgamma && acap <= 0) {
-      const long cap = 3L * rows * C * (long)sizeof(T) / 360000L;
-      acap = (int)(cap < 256 ? 256 : (cap > 4096 ? 4096 : cap));
-    }
-    int iters = vsx_cdiv(rows, RPI * (dgamma ? acap : g_vsx_ln_bblk));
+    int iters = vsx_cdiv(rows, RPI * (dgamma ? g_vsx_ln_ablk : g_vsx_ln_bblk));
     if (iters < 1) iters = 1;
     int grid = vsx_cdiv(rows, RPI * iters);
     size_t sh = dgamma ? 2 * (size_t)C * sizeof(float) : 0;
@@ -433,7 +418,6 @@ extern "C" int32_t vsx_grn_bwd_stats(const float* colsq, const float* P, const f
   return 0;
 }
 
-extern int g_vsx_ggb_blocks;
 // ------------------------------------------------------------------ GRN + GELU backward (pass 2)
 // dh = (dz * s[b,n] + gelu(h) * t[b,n]) * gelu'(h), written over dz; colsum[n] += Σ_m dh
 // Block = [256/tpr row slots][tpr column chunks]; every thread streams its column chunk down the

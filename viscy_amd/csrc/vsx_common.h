@@ -12,9 +12,13 @@ typedef __bf16 bf16_t;
 
 // ------------------------------------------------------------------ error plumbing (host)
 void vsx_set_error(const char* fmt, ...);
-extern int g_vsx_head_bps;                   // api.hip: workgroups per sample of head backward pass 1 (0 = sized from the batch)
-extern int g_vsx_head_rows;                  // api.hip: row-tiled MFMA passes of the head tail (head.hip)
-extern int g_vsx_det_reduce;                 // api.hip: fixed-order forward sums (vsx_set_flag("det_reduce", 1))
+// the knobs of vsx_set_flag: defined, described and tabulated in api.hip
+extern int g_vsx_tn_tr, g_vsx_tn_wide, g_vsx_tn_rect, g_vsx_tn_want, g_vsx_tn_want2, g_vsx_tn_p2_rounds, g_vsx_tn_fill, g_vsx_tn_contig, g_vsx_tn_stream;
+extern int g_vsx_nt_wide, g_vsx_nt_fast, g_vsx_nt_stream, g_vsx_nt2;
+extern int g_vsx_ln_fblk, g_vsx_ln_bblk, g_vsx_ln_ablk, g_vsx_ln_pack, g_vsx_ln_stream;
+extern int g_vsx_grn_stream, g_vsx_ggb_contig, g_vsx_ggb_blocks;
+extern int g_vsx_dw_mfma, g_vsx_mlp_fused, g_vsx_mlp_sf32, g_vsx_loss_fused;
+extern int g_vsx_head_bps, g_vsx_head_rows, g_vsx_det_reduce;
 extern thread_local float* g_vsx_det_ws;     // api.hip: vsx_det_workspace
 extern thread_local long g_vsx_det_ws_floats;
 // out[g * N + n] += sum over r < rows_per_group, IN ORDER, of ws[(g * rows_per_group + r) * ld + col0 + n]   (norm.hip)
