@@ -354,3 +354,44 @@ def test_stochastic_depth_schedule_matches_reference_golden(which):
     with torch.no_grad():
         out_e, _ = eng.forward(x, torch.float32, need_bwd=False)
         torch.testing.assert_close(out_e, ref(x), rtol=2e-4, atol=1e-4 * gold["y"].abs().max().item())
+
+
+def _mlp_cfg_serves(flag, C, hw, M, mode):
+    """the shapes csrc/mlp.hip serves (kMlpCfgs / mlp_cfg): widths 96 / 192 / 224 in every mode, 384 in the training passes
+    (2, 3, 4) behind flag bit 2, modes 5 - 7 behind bit 6 and 7 behind bit 7, whole 256-row workgroups per sample; None = the
+    inference pair (modes 0 and 1)"""
+    if mode is None:
+        return _mlp_cfg_serves(flag, C, hw, M, 0) and _mlp_cfg_serves(flag, C, hw, M, 1)
+    modes = {96: 255, 192: 255, 224: 255, 384: (4 | 8 | 16) if flag & 4 else 0}.get(C, 0)
+    need = {5: 64, 6: 64, 7: 64 | 128}.get(mode, 0)
+    return bool(modes & (1 << mode)) and flag & need == need and hw % 256 == 0 and M % 256 == 0
+
+
+def test_mlp_plan_reproduces_the_recorded_decisions():
+    """tests/golden/mlp_plan_table.json: for every point of a grid over (dtype, training, `mlp_fused` value, C, hw, B, LayerNorm
+    epilogue available, TN-GEMM statistics available) the schedule the engine chose before the decisions moved into
+    ``_plan_mlp`` — which has to give the same answer, row for row"""
+    import itertools
+    import json
+    import os
+
+    from tests.conftest import GOLDEN
+    from viscy_amd.engine_unext2 import _MlpPlan, _plan_mlp
+
+    with open(os.path.join(GOLDEN, "mlp_plan_table.json")) as f:
+        tab = json.load(f)
+    assert tuple(tab["fields"]) == _MlpPlan._fields
+    dts = {"bf16": torch.bfloat16, "fp32": torch.float32}
+    outer = list(itertools.product(*(tab["axes"][k] for k in tab["outer"])))
+    inner = list(itertools.product(*(tab["axes"][k] for k in tab["inner"])))
+    assert len(tab["rows"]) == len(outer) and all(len(r) == len(inner) for r in tab["rows"])
+    n = 0
+    for o, row in zip(outer, tab["rows"]):
+        for i, letter in zip(inner, row):
+            a = dict(zip(tab["outer"] + tab["inner"], o + i))
+            M = a["B"] * a["hw"]
+            got = _plan_mlp(a["flag"], lambda mode: _mlp_cfg_serves(a["flag"], a["C"], a["hw"], M, mode), a["C"], a["hw"], M, a["B"],
+                            dts[a["dt"]], a["training"], a["ln_bwd_ok"], a["tn_stats_ok"])
+            assert got == _MlpPlan(*tab["codes"][letter]), (a, got, tab["codes"][letter])
+            n += 1
+    assert n == 8640 and len(set("".join(tab["rows"]))) == len(tab["codes"]) >= 12

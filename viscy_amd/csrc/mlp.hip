@@ -1055,36 +1055,54 @@ extern "C" int32_t vsx_mlp_gelu_table(float* tab, vsx_stream_t stream) {
   return 0;
 }
 
-// LayerNorm-in-prologue variants (vsx_mlp_fwd_ln / vsx_mlp_fc1_ln) reuse the argument marshalling of the plain entry points
-static thread_local float g_mlp_ln_eps = 0.f;
-static thread_local bf16_t* g_mlp_xh_out = nullptr;
-static thread_local float* g_mlp_rstd_out = nullptr;
-static thread_local float* g_mlp_mean_out = nullptr;
-
-extern "C" int32_t vsx_mlp_fwd(const void* xh, const void* wimg, const float* b1, const float* grn_s, const float* grn_b,
-                               const float* b2, const void* res, const float* rscale, void* out, float* colsq,
-                               const float* gtab, int64_t M, int32_t C, int32_t hw, int32_t mode, int32_t dtype,
-                               vsx_stream_t stream) {
+// vsx_mlp_fwd and vsx_mlp_fwd_ln (ln_eps > 0: `xh` holds the un-normalised rows)
+static int32_t mlp_fwd_impl(const void* xh, float ln_eps, const void* wimg, const float* b1, const float* grn_s, const float* grn_b,
+                            const float* b2, const void* res, const float* rscale, void* out, float* colsq, const float* gtab,
+                            int64_t M, int32_t C, int32_t hw, int32_t mode, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(dtype == VSX_BF16, "vsx_mlp_fwd: bf16 only (the fp32 parity mode runs the unfused schedule)");
   VSX_CHECK(xh && wimg && b1 && gtab && M > 0 && hw > 0, "vsx_mlp_fwd: bad arguments");
   const MlpCfg* c = mlp_cfg(C, hw, M, mode == 0 ? 0 : 1);
   VSX_CHECK(c != nullptr, "vsx_mlp_fwd: unsupported shape C=%d hw=%d M=%ld (query vsx_mlp_supported first)", C, hw, (long)M);
   VSX_CHECK(M < (1ll << 31), "vsx_mlp_fwd: M too large");
-  MlpArgs a;
-  a.xh = (const bf16_t*)xh; a.wimg = (const char*)wimg; a.b1 = b1; a.grn_s = grn_s; a.grn_b = grn_b; a.b2 = b2;
-  a.res = (const bf16_t*)res; a.rscale = rscale; a.out = (bf16_t*)out; a.colsq = colsq; a.gtab = gtab; a.M = (int)M; a.hw = hw;
-  a.hout = nullptr; a.gout = nullptr; a.tin = nullptr; a.red0 = nullptr; a.red1 = nullptr; a.ws = nullptr; a.nt = 0;
-  a.ln_eps = g_mlp_ln_eps; a.xh_out = nullptr; a.rstd_out = nullptr; a.xh2 = nullptr; a.wimg2 = nullptr;
-  a.mean_out = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr;
+  MlpArgs a = {};
+  a.xh = (const bf16_t*)xh; a.wimg = (const char*)wimg; a.b1 = b1; a.gtab = gtab; a.M = (int)M; a.hw = hw; a.ln_eps = ln_eps;
   hipStream_t s = (hipStream_t)stream;
   if (mode == 0) {
     VSX_CHECK(colsq != nullptr, "vsx_mlp_fwd: mode 0 needs colsq");
+    a.colsq = colsq;
     if (int e = mlp_det_begin(a, c, "vsx_mlp_fwd")) return e;
     if (int e = mlp_dispatch<0>(c, a, s)) return e;
     return mlp_det_end(a, c, s);
   }
   VSX_CHECK(mode == 1 && grn_s && grn_b && b2 && res && out, "vsx_mlp_fwd: mode 1 needs s, beta, b2, res, out");
+  a.grn_s = grn_s; a.grn_b = grn_b; a.b2 = b2; a.res = (const bf16_t*)res; a.rscale = rscale; a.out = (bf16_t*)out;
   return mlp_dispatch<1>(c, a, s);
+}
+
+extern "C" int32_t vsx_mlp_fwd(const void* xh, const void* wimg, const float* b1, const float* grn_s, const float* grn_b,
+                               const float* b2, const void* res, const float* rscale, void* out, float* colsq,
+                               const float* gtab, int64_t M, int32_t C, int32_t hw, int32_t mode, int32_t dtype,
+                               vsx_stream_t stream) {
+  return mlp_fwd_impl(xh, 0.f, wimg, b1, grn_s, grn_b, b2, res, rscale, out, colsq, gtab, M, C, hw, mode, dtype, stream);
+}
+
+// vsx_mlp_fc1 and vsx_mlp_fc1_ln (ln_eps > 0: `xh` holds the un-normalised rows; xh_out / rstd_out / mean_out receive the
+// normalised rows and the row statistics)
+static int32_t mlp_fc1_impl(const void* xh, float ln_eps, void* xh_out, float* rstd_out, float* mean_out, const void* wimg,
+                            const float* b1, float* colsq, const float* gtab, void* h, void* g, int64_t M, int32_t C, int32_t hw,
+                            int32_t dtype, vsx_stream_t stream) {
+  VSX_CHECK(dtype == VSX_BF16, "vsx_mlp_fc1: bf16 only");
+  VSX_CHECK(xh && wimg && b1 && colsq && gtab && g && M > 0 && hw > 0, "vsx_mlp_fc1: bad arguments");
+  const MlpCfg* c = mlp_cfg(C, hw, M, h ? 2 : 6);
+  VSX_CHECK(c != nullptr, "vsx_mlp_fc1: unsupported shape C=%d hw=%d M=%ld (query vsx_mlp_supported first)", C, hw, (long)M);
+  VSX_CHECK(M < (1ll << 31), "vsx_mlp_fc1: M too large");
+  MlpArgs a = {};
+  a.xh = (const bf16_t*)xh; a.wimg = (const char*)wimg; a.b1 = b1; a.colsq = colsq; a.gtab = gtab; a.hout = (bf16_t*)h;
+  a.gout = (bf16_t*)g; a.nt = mlp_nt(); a.M = (int)M; a.hw = hw;
+  a.ln_eps = ln_eps; a.xh_out = (bf16_t*)xh_out; a.rstd_out = rstd_out; a.mean_out = mean_out;
+  if (int e = mlp_det_begin(a, c, "vsx_mlp_fc1")) return e;
+  if (int e = h ? mlp_dispatch<2>(c, a, (hipStream_t)stream) : mlp_dispatch<6>(c, a, (hipStream_t)stream)) return e;
+  return mlp_det_end(a, c, (hipStream_t)stream);
 }
 
 /* training fc1 (MODE 2): h = bf16(xh . W1'^T + b1), g = bf16(gelu(h)) stored for the backward, colsq[b, 4C] += sum_hw g^2 —
@@ -1092,21 +1110,7 @@ extern "C" int32_t vsx_mlp_fwd(const void* xh, const void* wimg, const float* b1
  * h = NULL (MODE 6, where vsx_mlp_mode_supported(.., 6, ..)): only g is stored — the backward recomputes h (vsx_mlp_bwd_dh_re) */
 extern "C" int32_t vsx_mlp_fc1(const void* xh, const void* wimg, const float* b1, float* colsq, const float* gtab, void* h,
                                void* g, int64_t M, int32_t C, int32_t hw, int32_t dtype, vsx_stream_t stream) {
-  VSX_CHECK(dtype == VSX_BF16, "vsx_mlp_fc1: bf16 only");
-  VSX_CHECK(xh && wimg && b1 && colsq && gtab && g && M > 0 && hw > 0, "vsx_mlp_fc1: bad arguments");
-  const MlpCfg* c = mlp_cfg(C, hw, M, h ? 2 : 6);
-  VSX_CHECK(c != nullptr, "vsx_mlp_fc1: unsupported shape C=%d hw=%d M=%ld (query vsx_mlp_supported first)", C, hw, (long)M);
-  VSX_CHECK(M < (1ll << 31), "vsx_mlp_fc1: M too large");
-  MlpArgs a;
-  a.xh = (const bf16_t*)xh; a.wimg = (const char*)wimg; a.b1 = b1; a.grn_s = nullptr; a.grn_b = nullptr; a.b2 = nullptr;
-  a.res = nullptr; a.rscale = nullptr; a.out = nullptr; a.colsq = colsq; a.gtab = gtab; a.hout = (bf16_t*)h; a.gout = (bf16_t*)g;
-  a.tin = nullptr; a.red0 = nullptr; a.red1 = nullptr; a.ws = nullptr; a.nt = mlp_nt();
-  a.M = (int)M; a.hw = hw;
-  a.ln_eps = g_mlp_ln_eps; a.xh_out = g_mlp_xh_out; a.rstd_out = g_mlp_rstd_out; a.xh2 = nullptr; a.wimg2 = nullptr;
-  a.mean_out = g_mlp_mean_out; a.ln_mean = nullptr; a.ln_rstd = nullptr;
-  if (int e = mlp_det_begin(a, c, "vsx_mlp_fc1")) return e;
-  if (int e = h ? mlp_dispatch<2>(c, a, (hipStream_t)stream) : mlp_dispatch<6>(c, a, (hipStream_t)stream)) return e;
-  return mlp_det_end(a, c, (hipStream_t)stream);
+  return mlp_fc1_impl(xh, 0.f, nullptr, nullptr, nullptr, wimg, b1, colsq, gtab, h, g, M, C, hw, dtype, stream);
 }
 
 /* The same passes with the block LayerNorm (eps, no affine: folded into W1' / b1) applied in the kernel's prologue: `y` holds
@@ -1120,30 +1124,23 @@ extern "C" int32_t vsx_mlp_fwd_ln(const void* y, float eps, const void* wimg, co
                                   float* colsq, const float* gtab, int64_t M, int32_t C, int32_t hw, int32_t mode, int32_t dtype,
                                   vsx_stream_t stream) {
   VSX_CHECK(eps > 0.f, "vsx_mlp_fwd_ln: eps must be positive");
-  g_mlp_ln_eps = eps;
-  const int32_t rc = vsx_mlp_fwd(y, wimg, b1, grn_s, grn_b, b2, res, rscale, out, colsq, gtab, M, C, hw, mode, dtype, stream);
-  g_mlp_ln_eps = 0.f;
-  return rc;
+  return mlp_fwd_impl(y, eps, wimg, b1, grn_s, grn_b, b2, res, rscale, out, colsq, gtab, M, C, hw, mode, dtype, stream);
 }
 extern "C" int32_t vsx_mlp_fc1_ln(const void* y, float eps, void* xh_out, float* rstd_out, float* mean_out, const void* wimg,
                                   const float* b1, float* colsq, const float* gtab, void* h, void* g, int64_t M, int32_t C,
                                   int32_t hw, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(eps > 0.f && rstd_out && (xh_out || mean_out), "vsx_mlp_fc1_ln: eps must be positive, rstd_out and one of xh_out / mean_out non-null");
-  g_mlp_ln_eps = eps; g_mlp_xh_out = (bf16_t*)xh_out; g_mlp_rstd_out = rstd_out; g_mlp_mean_out = mean_out;
-  const int32_t rc = vsx_mlp_fc1(y, wimg, b1, colsq, gtab, h, g, M, C, hw, dtype, stream);
-  g_mlp_ln_eps = 0.f; g_mlp_xh_out = nullptr; g_mlp_rstd_out = nullptr; g_mlp_mean_out = nullptr;
-  return rc;
+  return mlp_fc1_impl(y, eps, xh_out, rstd_out, mean_out, wimg, b1, colsq, gtab, h, g, M, C, hw, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ backward passes
 __global__ void reduce_rows_kernel(const float* __restrict__ ws, float* __restrict__ out, int R, int N);  // norm.hip
 
-static void mlp_bwd_args(MlpArgs& a, const void* dout, const void* wimg, const void* tin, int64_t M, int32_t hw, const float* gtab = nullptr) {
-  a.xh = (const bf16_t*)dout; a.wimg = (const char*)wimg; a.b1 = nullptr; a.grn_s = nullptr; a.grn_b = nullptr; a.b2 = nullptr;
-  a.res = nullptr; a.rscale = nullptr; a.out = nullptr; a.colsq = nullptr; a.gtab = gtab; a.hout = nullptr; a.gout = nullptr;
-  a.tin = (const bf16_t*)tin; a.red0 = nullptr; a.red1 = nullptr; a.ws = nullptr; a.M = (int)M; a.hw = hw; a.nt = mlp_nt();
-  a.ln_eps = 0.f; a.xh_out = nullptr; a.rstd_out = nullptr; a.xh2 = nullptr; a.wimg2 = nullptr;
-  a.mean_out = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr;
+// what MODE 3 / 4 / 5 / 7 share: `xh` holds dout, `wimg` the backward image (W2^T, W2)
+static MlpArgs mlp_bwd_args(const void* dout, const void* wimg, int64_t M, int32_t hw) {
+  MlpArgs a = {};
+  a.xh = (const bf16_t*)dout; a.wimg = (const char*)wimg; a.M = (int)M; a.hw = hw; a.nt = mlp_nt();
+  return a;
 }
 
 /* MODE 3: the GRN statistics path of the block backward without a stored dz: dz = dout . W2 recomputed tile by tile
@@ -1155,10 +1152,26 @@ extern "C" int32_t vsx_mlp_bwd_stats(const void* dout, const void* wimg, const v
   VSX_CHECK(dout && wimg && g && P && S && M > 0 && hw > 0, "vsx_mlp_bwd_stats: bad arguments");
   const MlpCfg* c = mlp_cfg(C, hw, M, 3);
   VSX_CHECK(c != nullptr && M < (1ll << 31), "vsx_mlp_bwd_stats: unsupported shape C=%d hw=%d M=%ld", C, hw, (long)M);
-  MlpArgs a;
-  mlp_bwd_args(a, dout, wimg, g, M, hw);
-  a.red0 = P; a.red1 = S;
+  MlpArgs a = mlp_bwd_args(dout, wimg, M, hw);
+  a.tin = (const bf16_t*)g; a.red0 = P; a.red1 = S;
   return mlp_dispatch<3>(c, a, (hipStream_t)stream);
+}
+
+// The three dh passes (MODE 4 / 5 / 7) from here on: `a` carries the mode's own operands; s, t, dh, the gelu table and the
+// workspace go in, the pass runs, and the per-workgroup rows of `ws` (wsN floats each) are added into colsum[wsN]
+template <int MODE>
+static int32_t mlp_bwd_dh_run(const char* who, MlpArgs& a, const float* s, const float* t, void* dh, float* ws, int64_t ws_rows,
+                              float* colsum, int wsN, const float* gtab, int64_t M, int32_t C, int32_t hw, vsx_stream_t stream) {
+  const MlpCfg* c = mlp_cfg(C, hw, M, MODE);
+  VSX_CHECK(c != nullptr && M < (1ll << 31), "%s: unsupported shape C=%d hw=%d M=%ld", who, C, hw, (long)M);
+  const int R = (int)(M / (c->NW * 16 * c->MF));
+  VSX_CHECK(ws_rows >= R, "%s: workspace needs %d rows of %d floats", who, R, wsN);
+  a.grn_s = s; a.grn_b = t; a.hout = (bf16_t*)dh; a.ws = ws; a.gtab = gtab;
+  if (int e = mlp_dispatch<MODE>(c, a, (hipStream_t)stream)) return e;
+  hipLaunchKernelGGL(reduce_rows_kernel, dim3(vsx_cdiv(wsN, 64), vsx_cdiv(R, 64)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)ws, colsum, R, wsN);
+  VSX_LAUNCH_CHECK();
+  return 0;
 }
 
 /* MODE 4: dh = (dz * s[b] + gelu(h) * t[b]) * gelu'(h) with dz recomputed, stored [M, 4C]; colsum[4C] += sum over all pixels
@@ -1169,19 +1182,9 @@ extern "C" int32_t vsx_mlp_bwd_dh(const void* dout, const void* wimg, const void
                                   int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(dtype == VSX_BF16, "vsx_mlp_bwd_dh: bf16 only");
   VSX_CHECK(dout && wimg && h && s && t && dh && ws && colsum && gtab && M > 0 && hw > 0, "vsx_mlp_bwd_dh: bad arguments");
-  const MlpCfg* c = mlp_cfg(C, hw, M, 4);
-  VSX_CHECK(c != nullptr && M < (1ll << 31), "vsx_mlp_bwd_dh: unsupported shape C=%d hw=%d M=%ld", C, hw, (long)M);
-  const int bm = c->NW * 16 * c->MF;
-  VSX_CHECK(ws_rows >= M / bm, "vsx_mlp_bwd_dh: workspace needs %ld rows of %d floats", (long)(M / bm), 4 * C);
-  MlpArgs a;
-  mlp_bwd_args(a, dout, wimg, h, M, hw, gtab);
-  a.grn_s = s; a.grn_b = t; a.hout = (bf16_t*)dh; a.ws = ws;
-  if (int e = mlp_dispatch<4>(c, a, (hipStream_t)stream)) return e;
-  const int R = (int)(M / bm), N = 4 * C;
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(vsx_cdiv(N, 64), vsx_cdiv(R, 64)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)ws, colsum, R, N);
-  VSX_LAUNCH_CHECK();
-  return 0;
+  MlpArgs a = mlp_bwd_args(dout, wimg, M, hw);
+  a.tin = (const bf16_t*)h;
+  return mlp_bwd_dh_run<4>("vsx_mlp_bwd_dh", a, s, t, dh, ws, ws_rows, colsum, 4 * C, gtab, M, C, hw, stream);
 }
 
 /* MODE 5: vsx_mlp_bwd_dh WITHOUT a stored pre-activation: h = bf16(xh . W1'^T + b1) is recomputed on chip from the normalised
@@ -1193,19 +1196,9 @@ extern "C" int32_t vsx_mlp_bwd_dh_re(const void* dout, const void* xh, const voi
                                      const float* gtab, int64_t M, int32_t C, int32_t hw, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(dtype == VSX_BF16, "vsx_mlp_bwd_dh_re: bf16 only");
   VSX_CHECK(dout && xh && wimg_bwd && wimg_fwd && b1 && s && t && dh && ws && colsum && gtab && M > 0 && hw > 0, "vsx_mlp_bwd_dh_re: bad arguments");
-  const MlpCfg* c = mlp_cfg(C, hw, M, 5);
-  VSX_CHECK(c != nullptr && M < (1ll << 31), "vsx_mlp_bwd_dh_re: unsupported shape C=%d hw=%d M=%ld", C, hw, (long)M);
-  const int bm = c->NW * 16 * c->MF;
-  VSX_CHECK(ws_rows >= M / bm, "vsx_mlp_bwd_dh_re: workspace needs %ld rows of %d floats", (long)(M / bm), 4 * C);
-  MlpArgs a;
-  mlp_bwd_args(a, dout, wimg_bwd, nullptr, M, hw, gtab);
-  a.grn_s = s; a.grn_b = t; a.hout = (bf16_t*)dh; a.ws = ws; a.xh2 = (const bf16_t*)xh; a.wimg2 = (const char*)wimg_fwd; a.b1 = b1;
-  if (int e = mlp_dispatch<5>(c, a, (hipStream_t)stream)) return e;
-  const int R = (int)(M / bm), N = 4 * C;
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(vsx_cdiv(N, 64), vsx_cdiv(R, 64)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)ws, colsum, R, N);
-  VSX_LAUNCH_CHECK();
-  return 0;
+  MlpArgs a = mlp_bwd_args(dout, wimg_bwd, M, hw);
+  a.xh2 = (const bf16_t*)xh; a.wimg2 = (const char*)wimg_fwd; a.b1 = b1;
+  return mlp_bwd_dh_run<5>("vsx_mlp_bwd_dh_re", a, s, t, dh, ws, ws_rows, colsum, 4 * C, gtab, M, C, hw, stream);
 }
 
 /* MODE 7: vsx_mlp_bwd_dh_re for a block whose forward stored NO normalised rows (vsx_mlp_fc1_ln with xh_out = NULL): `y` [M, C]
@@ -1223,20 +1216,9 @@ extern "C" int32_t vsx_mlp_bwd_dh_ln(const void* dout, const void* y, const floa
   VSX_CHECK(dtype == VSX_BF16, "vsx_mlp_bwd_dh_ln: bf16 only");
   VSX_CHECK(dout && y && mean && rstd && wimg_bwd && wimg_fwd && b1 && s && t && dh && ws && colsum2 && gtab && M > 0 && hw > 0,
             "vsx_mlp_bwd_dh_ln: bad arguments");
-  const MlpCfg* c = mlp_cfg(C, hw, M, 7);
-  VSX_CHECK(c != nullptr && M < (1ll << 31), "vsx_mlp_bwd_dh_ln: unsupported shape C=%d hw=%d M=%ld", C, hw, (long)M);
-  const int bm = c->NW * 16 * c->MF;
-  VSX_CHECK(ws_rows >= M / bm, "vsx_mlp_bwd_dh_ln: workspace needs %ld rows of %d floats", (long)(M / bm), 8 * C);
-  MlpArgs a;
-  mlp_bwd_args(a, dout, wimg_bwd, nullptr, M, hw, gtab);
-  a.grn_s = s; a.grn_b = t; a.hout = (bf16_t*)dh; a.ws = ws; a.xh2 = (const bf16_t*)y; a.wimg2 = (const char*)wimg_fwd; a.b1 = b1;
-  a.ln_mean = mean; a.ln_rstd = rstd;
-  if (int e = mlp_dispatch<7>(c, a, (hipStream_t)stream)) return e;
-  const int R = (int)(M / bm), N = 8 * C;
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(vsx_cdiv(N, 64), vsx_cdiv(R, 64)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)ws, colsum2, R, N);
-  VSX_LAUNCH_CHECK();
-  return 0;
+  MlpArgs a = mlp_bwd_args(dout, wimg_bwd, M, hw);
+  a.xh2 = (const bf16_t*)y; a.wimg2 = (const char*)wimg_fwd; a.b1 = b1; a.ln_mean = mean; a.ln_rstd = rstd;
+  return mlp_bwd_dh_run<7>("vsx_mlp_bwd_dh_ln", a, s, t, dh, ws, ws_rows, colsum2, 8 * C, gtab, M, C, hw, stream);
 }
 
 #ifdef MLP_TS

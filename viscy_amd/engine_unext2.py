@@ -15,11 +15,14 @@ itself on CPU (tests/ref_ops.py); nothing in the package does.
 from __future__ import annotations
 
 import os
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
 
 from . import _lib as L
+from . import ops as hip_ops
 
 
 class _BlockW:
@@ -30,6 +33,55 @@ class _BlockW:
 
 class _ProjW:
     __slots__ = ("cin", "cout", "taps", "ln", "conv", "W", "WT")
+
+
+FWD_UNFUSED, FWD_PAIR, FWD_FC1 = 0, 1, 2
+
+
+class _MlpPlan(NamedTuple):
+    """how one ConvNeXt block runs its GRN-MLP: decided once per block and forward (``_plan_mlp``), saved with the block's
+    tensors and executed as saved by the backward"""
+
+    fwd: int        # FWD_UNFUSED (GEMMs) | FWD_PAIR (inference: statistics + output pass) | FWD_FC1 (training fc1, MODE 2 / 6)
+    ln_in: bool     # the block LayerNorm rides in the prologue of the fused passes (no LayerNorm pass over y)
+    keep_h: bool    # the forward stores the pre-activation h (False: the dh pass recomputes it, MODE 6 here / 5 or 7 there)
+    keep_xh: bool   # ... and the normalised rows x^ (False: it keeps y, mean, rstd and the backward re-normalises, MODE 7)
+    bwd: int        # 0 unfused | fused dh pass (MODE 4 / 5 / 7), GRN statistics from 1: the per-sample products dout_b^T g_b, 2:
+    tn_stats: bool  # the fc2 weight-gradient TN GEMM if tn_stats, else the MODE 3 pass
+
+
+def _plan_mlp(flag: int, supported, C: int, hw: int, M: int, B: int, dt: torch.dtype, training: bool, ln_bwd_ok: bool,
+              tn_stats_ok: bool) -> _MlpPlan:
+    """Pure: the plan from the value of ``mlp_fused``, ``supported(mode)`` (csrc/mlp.hip serves MODE ``mode`` — None: the
+    inference pair — at this shape) and whether the data-gradient GEMM's LayerNorm epilogue / the TN GEMM's GRN statistics
+    serve the shape.  Flag bits: 0 inference pair, 1 training fc1 (fc2 stays the unfused GEMM, which reads the stored g), 3 the
+    backward writes dh once (MODE 4) instead of dz and then dh, 5 LayerNorm in the prologue, 6 h recomputed instead of stored
+    (needs the fused backward), 7 (with 5 and 6) x^ not stored either (needs the LayerNorm epilogue, C <= 256: the stand-alone
+    LayerNorm backward reads a stored x^).  bf16 only."""
+    if dt != torch.bfloat16:
+        flag = 0
+    if not training:
+        pair = bool(flag & 1) and supported(None)
+        return _MlpPlan(FWD_PAIR if pair else FWD_UNFUSED, pair and bool(flag & 32), False, False, 0, False)
+    fc1 = bool(flag & 2) and supported(2)
+    bwd = 0
+    if flag & 8 and supported(4):
+        if B * C * 4 * C * 4 <= (512 << 20) and C >= 96 and hw % 64 == 0:  # the B products [C, 4C] (fp32) fit 512 MB
+            bwd = 1
+        elif supported(3):
+            bwd = 2
+    recompute_h = bool(flag & 64) and bwd != 0 and supported(5) and supported(6)
+    drop_xh = bool(flag & 128) and bool(flag & 32) and recompute_h and supported(7) and ln_bwd_ok
+    ln_in = fc1 and bool(flag & 32)
+    return _MlpPlan(FWD_FC1 if fc1 else FWD_UNFUSED, ln_in, not (fc1 and recompute_h), not (ln_in and drop_xh), bwd,
+                    bwd == 2 and bool(tn_stats_ok))
+
+
+# what a block's forward keeps for its backward: xh = the normalised rows [M, C] (plan.keep_xh), else y = the depthwise output
+# and mean = its row means; h = the pre-activation [M, 4C] (plan.keep_h), gact = gelu(h).  (The first nine fields are in the
+# order readers by position know: tests/test_gpu_model.py takes colsq as item 5.)
+_BlockSaved = namedtuple("_BlockSaved", "x xh rstd h gact colsq s rows dpm plan y mean")
+_NarrowSaved = namedtuple("_NarrowSaved", "x y colsq s")
 
 
 def _views(flat: Tensor, shapes):
@@ -49,16 +101,14 @@ class _ZeroArena:
     0.74 ms per step in the kernel trace).  Sized from the previous pass with the same key; a pass that needs more than
     was recorded falls back to individual allocations (and records the new size)."""
 
-    def __init__(self, dev, numel: int, ops=None):
+    def __init__(self, dev, numel: int, ops):
         self.dev, self.ops = dev, ops
         self.buf = self._zeros(numel) if numel > 0 else None
         self.off = 0
         self.used = 0
 
     def _zeros(self, *shape) -> Tensor:
-        if self.ops is not None and hasattr(self.ops, "zeros"):
-            return self.ops.zeros(*shape, device=self.dev)  # vsx_fill_f32: the captured step holds no ATen fill
-        return torch.zeros(shape, dtype=torch.float32, device=self.dev)
+        return self.ops.zeros(*shape, device=self.dev)  # vsx_fill_f32: the captured step holds no ATen fill
 
     def take(self, *shape) -> Tensor:
         n = 1
@@ -75,11 +125,9 @@ class _ZeroArena:
 
 class Engine:
     def __init__(self, model, ops=None):
-        if ops is None:
-            from . import ops as hip_ops
-
-            ops = hip_ops
-        self.ops = ops
+        self.ops = hip_ops if ops is None else ops
+        self._hip = self.ops is hip_ops  # the HIP backend: the only one that has the library's flags and fused GRN-MLP passes
+        self._mlp_flag = 0               # `mlp_fused` as read by the forward in flight (0 on any other backend)
         self.model = model
         self.cfg = model.cfg
         self._zeros4c = {}       # C -> zeros(4C): the identity GRN of ConvNeXt-V1 blocks
@@ -200,7 +248,7 @@ class Engine:
                                       gamma=blk.norm.weight)
         w.b1f = o.matvec(blk.mlp.fc1.weight, blk.norm.bias, blk.mlp.fc1.bias, 4 * C, C)
         w.dp = 0.0  # stochastic-depth rate of this block (set by prepare() from cfg["drop_path"])
-        w.img = None  # fragment-major LDS image of (W1f, W2) for the fused GRN-MLP kernel, packed on first use
+        w.img = None  # fragment-major LDS image of (W1f, W2) for the fused GRN-MLP kernel (prepare())
         w.v1 = hasattr(blk, "gamma")
         if w.v1:
             # ConvNeXt-V1: y = x + gamma * fc2(gelu(fc1(.))) — the layer scale is folded into fc2 (vsx_layer_scale_fold) and
@@ -231,15 +279,17 @@ class Engine:
             w.W, w.WT = o.prep_weight(conv.weight, cout, cin, taps, dt, want=True, want_t=need_bwd)
         return w
 
-    def prepare(self, dt: torch.dtype, need_bwd: bool):
+    def prepare(self, dt: torch.dtype, need_bwd: bool, mlp_flag: int = 0):
         key = (dt, need_bwd)
         m, cfg, o = self.model, self.cfg, self.ops
         with o.batch():  # ~150 weight-space jobs -> a handful of task-list launches (ops.batch)
             W = self._prepare_ops(dt, need_bwd)
-        if dt == torch.bfloat16 and self._mlp_flag() and hasattr(o, "mlp_pack"):
+        if dt == torch.bfloat16 and mlp_flag:
             # fragment-major weight images of the fused GRN-MLP kernels, every block's in one task list (their inputs are the
-            # outputs of the list above); a block whose shape the fused kernels do not serve simply never reads its image
-            bwd_img = need_bwd and bool(self._mlp_flag() & 8)
+            # outputs of the list above); a block whose shape the fused kernels do not serve simply never reads its image.
+            # `_plan_mlp` fuses a pass only where mode None / 2 / 4 is served (and the backward only with bit 3), from the same
+            # flag value: every image a plan of this forward reads is packed here
+            bwd_img = need_bwd and bool(mlp_flag & 8)
             with o.batch():
                 for _, blocks in list(W["enc"]) + list(W["dec"]):
                     for w in blocks:
@@ -344,43 +394,12 @@ class Engine:
         return dt
 
     # ------------------------------------------------------------------ block forward / backward
-    def _mlp_flag(self) -> int:
-        return L.lib().vsx_get_flag(b"mlp_fused") if self.ops.__name__.endswith("viscy_amd.ops") else 0
-
-    def _mlp_mode(self, C, hw, M, dt, training: bool) -> bool:
-        """fused GRN-MLP kernel available for this block shape (bf16, C a supported width, whole workgroup tiles per sample)
-        and enabled (``mlp_fused`` flag: bit 0 = inference forward (statistics + output passes), bit 1 = training fc1 (the
-        statistics pass that also stores h and g; fc2 stays the unfused GEMM, which reads the stored g))"""
-        if dt != torch.bfloat16:
-            return False
-        flag = self._mlp_flag()
-        if training:
-            return bool(flag & 2) and self.ops.mlp_supported(C, hw, M, dt, 2)
-        return bool(flag & 1) and self.ops.mlp_supported(C, hw, M, dt)
-
-    def _mlp_bwd_fused(self, C, hw, M, dt, B) -> int:
-        """``mlp_fused`` bit 3: the block backward writes dh once (csrc/mlp.hip MODE 4) instead of dz and then dh.  Returns
-        0 (unfused), 1 (GRN statistics and fc2 weight gradient from the per-sample products dout_b^T g_b) or 2 (statistics
-        from the MODE 3 pass: when the B per-sample [C, 4C] fp32 products would be larger than 512 MB)"""
-        if dt != torch.bfloat16 or not (self._mlp_flag() & 8) or not self.ops.mlp_supported(C, hw, M, dt, 4):
-            return 0
-        if B * C * 4 * C * 4 <= (512 << 20) and C >= 96 and hw % 64 == 0:
-            return 1
-        return 2 if self.ops.mlp_supported(C, hw, M, dt, 3) else 0
-
-    def _mlp_recompute_h(self, C, hw, M, dt, B) -> bool:
-        """``mlp_fused`` bit 6: the training fc1 stores g only and the dh pass recomputes h (needs the fused backward)"""
-        return bool(self._mlp_flag() & 64) and self._mlp_bwd_fused(C, hw, M, dt, B) != 0 and self.ops.mlp_supported(C, hw, M, dt, 5) \
-            and self.ops.mlp_supported(C, hw, M, dt, 6)
-
-    def _mlp_drop_xh(self, C, hw, M, dt, B) -> bool:
-        """``mlp_fused`` bit 7 (with 5 and 6): the normalised rows x^ are not stored either — the forward keeps the depthwise
-        output y and the row mean / rstd; the dh pass re-normalises y and hands on dh * rstd (csrc/mlp.hip MODE 7), the fc1
-        weight gradient is a plain TN GEMM on y with a rank-1 correction, the data-gradient GEMM's LayerNorm epilogue re-forms
-        x^ from y.  Needs that epilogue (C <= 256): the stand-alone LayerNorm backward reads a stored x^."""
-        flag = self._mlp_flag()
-        return bool(flag & 128) and bool(flag & 32) and self._mlp_recompute_h(C, hw, M, dt, B) and self.ops.mlp_supported(C, hw, M, dt, 7) \
-            and hasattr(self.ops, "dgrad_ln_bwd") and bool(L.lib().vsx_gemm_nt_ln_bwd_supported(M, C, 4 * C, L.dtype_code(dt)))
+    def _plan(self, C, hw, M, B, dt, training: bool) -> _MlpPlan:
+        o, flag = self.ops, self._mlp_flag
+        ask = training and dt == torch.bfloat16 and flag != 0  # the two shape queries only matter to a fused training block
+        return _plan_mlp(flag, lambda mode: o.mlp_supported(C, hw, M, dt, mode), C, hw, M, B, dt, training,
+                         ask and bool(L.lib().vsx_gemm_nt_ln_bwd_supported(M, C, 4 * C, L.dtype_code(dt))),
+                         ask and o.tn_grn_stats_ok(M, C, 4 * C, hw, dt))
 
     def _block_fwd(self, x, w, B, H, Wd, dt, save, rows=None):
         """One ConvNeXt-V2 block on a dense channels-last map [B*H*W, C].  ``rows = (idx, inv, keep, L)`` selects the FCMAE
@@ -400,15 +419,15 @@ class Engine:
             M, hw = B * Lr, Lr
             y = o.rows_select(y, idx, M, C)      # masked_patchify
             xres = o.rows_select(x, idx, M, C)   # the shortcut of the kept tokens
-        fused = self._mlp_mode(C, hw, M, dt, save is not None)
-        # mlp_fused bit 5: the block LayerNorm rides in the prologue of the fused GRN-MLP passes (csrc/mlp.hip) — no LayerNorm
-        # pass over y, and in inference no normalised rows in memory at all
-        ln_in = fused and bool(self._mlp_flag() & 32) and hasattr(o, "mlp_fc1_ln")
-        if ln_in:
-            xh, rstd = y, None
+        plan = self._plan(C, hw, M, B, dt, save is not None)
+        # plan.ln_in: the block LayerNorm rides in the prologue of the fused GRN-MLP passes (csrc/mlp.hip) — no LayerNorm pass
+        # over y, and in inference no normalised rows in memory at all
+        mean = rstd = None
+        if plan.ln_in:
+            xh = None
         else:
             xh, _, rstd = o.ln_fwd(y, None, None, M, C, 1e-6, need_mean=False)
-            del y
+            y = None
         colsq = self._za.take(B, 4 * C)
         # stochastic depth (timm DropPath, scale_by_keep): the whole branch of a sample is dropped with probability dp and
         # the survivors are scaled by 1 / (1 - dp); training mode only.  One device-side draw per block (graph-capturable).
@@ -416,41 +435,32 @@ class Engine:
         if w.dp > 0.0 and self.model.training:
             inj = self._dp_inject
             dpm = inj.pop(0) if inj else (torch.rand(B, device=x.device) < (1.0 - w.dp)).float() / (1.0 - w.dp)
-        lne = 1e-6 if ln_in else 0.0
-        if fused and save is None:
+        assert plan.fwd == FWD_UNFUSED or w.img is not None  # packed by prepare() from the flag value this plan was made from
+        if plan.fwd == FWD_PAIR:
             # inference: the 4C-wide hidden never leaves the CU (csrc/mlp.hip) — pass 1 = GRN statistics, pass 2 = fc1
             # recomputed, GELU, GRN, fc2, bias, shortcut
-            if w.img is None:
-                w.img = o.mlp_pack(w.W1f, w.W2, C)
-                o.flush()  # inside an open task-list batch the pack is only queued; its reader is the next launch
-            if ln_in:
-                o.mlp_stats(xh, w.img, w.b1f, colsq, M, C, hw, ln_eps=lne)
-                s = o.grn_scale(colsq, w.grn_w)
-                out = o.mlp_out(xh, w.img, w.b1f, s, w.grn_b, w.fc2_b, xres, dpm, M, C, hw, ln_eps=lne)
-            else:
-                o.mlp_stats(xh, w.img, w.b1f, colsq, M, C, hw)
-                s = o.grn_scale(colsq, w.grn_w)
-                out = o.mlp_out(xh, w.img, w.b1f, s, w.grn_b, w.fc2_b, xres, dpm, M, C, hw)
+            src, lne = (y, 1e-6) if plan.ln_in else (xh, 0.0)
+            o.mlp_stats(src, w.img, w.b1f, colsq, M, C, hw, ln_eps=lne)
+            s = o.grn_scale(colsq, w.grn_w)
+            out = o.mlp_out(src, w.img, w.b1f, s, w.grn_b, w.fc2_b, xres, dpm, M, C, hw, ln_eps=lne)
             if rows is not None:
                 out = o.rows_select(out, rows[1], B * H * Wd, C)
             return out
         # fc1 writes the pre-activation h (needed for gelu' in backward) AND the activation g = gelu(h):
         # fc2, the fc2 weight gradient and the GRN statistics path all consume g, so GELU is evaluated once
         # (inference keeps the activation only: C = NULL skips the pre-activation store, a third of the block's 4C-wide traffic)
-        if save is not None and self._mlp_mode(C, hw, M, dt, True):
-            # training fc1 on the fused kernel's statistics pass, which also stores h and g (csrc/mlp.hip MODE 2)
-            if w.img is None:
-                w.img = o.mlp_pack(w.W1f, w.W2, C)
-                o.flush()
-            # mlp_fused bit 6: the pre-activation h is NOT stored — the backward's dh pass recomputes it from the C-wide
+        if plan.fwd == FWD_FC1:
+            # training fc1 on the fused kernel's statistics pass, which also stores h and g (csrc/mlp.hip MODE 2).
+            # not plan.keep_h: the pre-activation h is NOT stored — the backward's dh pass recomputes it from the C-wide
             # normalised rows (csrc/mlp.hip MODE 6 here, MODE 5 there): one 4C-wide write and one 4C-wide read less per block
-            keep_h = not self._mlp_recompute_h(C, hw, M, dt, B)
-            if ln_in:
-                # bit 7: ... and neither is x^ — `xh` is then the pair (y, row means) the backward re-normalises from
-                xh, rstd, h, gact = o.mlp_fc1_ln(xh, w.img, w.b1f, colsq, M, C, hw, 1e-6, store_h=keep_h,
-                                                 store_xh=keep_h or not self._mlp_drop_xh(C, hw, M, dt, B))
+            if plan.ln_in:
+                # not plan.keep_xh: ... and neither is x^ — the backward re-normalises from y and the row means
+                first, rstd, h, gact = o.mlp_fc1_ln(y, w.img, w.b1f, colsq, M, C, hw, 1e-6, store_h=plan.keep_h,
+                                                    store_xh=plan.keep_xh)
+                xh, y, mean = (first, None, None) if plan.keep_xh else (None, *first)
+                del first
             else:
-                h, gact = o.mlp_fc1(xh, w.img, w.b1f, colsq, M, C, hw, store_h=keep_h)
+                h, gact = o.mlp_fc1(xh, w.img, w.b1f, colsq, M, C, hw, store_h=plan.keep_h)
         else:
             h = torch.empty((M, 4 * C), dtype=dt, device=x.device) if save is not None else None
             gact = torch.empty((M, 4 * C), dtype=dt, device=x.device)
@@ -476,7 +486,7 @@ class Engine:
         if rows is not None:
             out = o.rows_select(out, rows[1], B * H * Wd, C)  # masked_unpatchify: zero rows where masked (shortcut is 0 there)
         if save is not None:
-            save.append((x, xh, rstd, h, gact, colsq, s, rows, dpm))
+            save.append(_BlockSaved(x, xh, rstd, h, gact, colsq, s, rows, dpm, plan, y, mean))
         return out
 
     def _block_fwd_narrow(self, x, w, B, H, Wd, save, rows):
@@ -491,7 +501,7 @@ class Engine:
         s = o.grn_scale(colsq, w.grn_w)
         out = o.narrow_block_fwd2(y, x, w.W1f, w.b1f, s, w.grn_b, w.W2, w.fc2_b, B, H, Wd, C)
         if save is not None:
-            save.append((x, y, colsq, s))
+            save.append(_NarrowSaved(x, y, colsq, s))
         return out
 
     def _block_bwd_narrow(self, dout, w, saved, B, H, Wd):
@@ -522,7 +532,7 @@ class Engine:
         o, g = self.ops, self.g
         C, M = w.C, B * H * Wd
         blk = w.p
-        x, xh, rstd, h, gact, colsq, s, rows, dpm = saved
+        x, xh, rstd, h, gact, colsq, s, rows, dpm, plan, y, mean = saved
         dev = dout.device
         hw = H * Wd
         dfull = dout
@@ -538,10 +548,9 @@ class Engine:
         else:
             dW2, db2 = g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias)
             dgw, dgb = g(blk.mlp.grn.weight), g(blk.mlp.grn.bias)
-        fused_bwd = self._mlp_bwd_fused(C, hw, M, dt, B)
-        if h is None and not fused_bwd:
-            raise RuntimeError("this block's forward did not store the pre-activation h (mlp_fused bit 6) and the fused backward "
-                               "that recomputes it is switched off now: do not change `mlp_fused` between a forward and its backward")
+        # the schedule is the one the forward planned, whatever `mlp_fused` says by now (a pass whose flag bit was cleared in
+        # between is refused by the library)
+        fused_bwd, stats_in_tn = plan.bwd, plan.tn_stats
         PS = self._za.take(2, B, 4 * C)
         if fused_bwd == 1:
             # dz = dout·W2 is LINEAR in dout, so everything the backward needs from "Σ over the sample of dz·(something)" comes
@@ -554,10 +563,7 @@ class Engine:
             o.gemm("tn", gact, dout, Qb, M, C, 4 * C, 4 * C, C, 4 * C, dtype=dt, hw=hw, colsum=csb, b_bstride=C * 4 * C)
             o.grn_q_reduce(Qb, csb, w.W2, s, w.grn_b, PS[0], PS[1], dW2, db2)
             del Qb
-        stats_in_tn = False
-        if fused_bwd == 1:
-            pass
-        elif fused_bwd == 2 and hasattr(o, "tn_grn_stats_ok") and o.tn_grn_stats_ok(M, C, 4 * C, hw, dt):
+        elif stats_in_tn:
             # round 5: the products are too large to store (C = 384 at B = 512), but each per-sample TILE of Q_b passes through the
             # accumulators of the fc2 weight-gradient GEMM anyway — that launch scales it by s_b into dW2 and contracts it with its
             # W2 tile into P_b on the way (csrc/gemm.hip, gemm_tn_fast_kernel PRO == 2).  The statistics pass that recomputed dz for
@@ -572,7 +578,6 @@ class Engine:
             if not w.v1:
                 o.transpose_f32(cs, db2, C, 1, True)     # db2 += cs
             o.matvec_t_add(w.fc2_w, cs, dgb, C, 4 * C)   # dbeta += W2^T cs
-            stats_in_tn = True
         else:
             # fc2: weight gradient (Z recomputed in the operand prologue) + bias gradient
             o.gemm("tn", gact, dout, dW2, M, C, 4 * C, 4 * C, C, 4 * C, dtype=dt, pro=L.PRO_GRN, grn_s=s,
@@ -580,10 +585,7 @@ class Engine:
         if w.v1:
             o.layer_scale_unfold(dW2, db2, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma, g(blk.mlp.fc2.weight),
                                  g(blk.mlp.fc2.bias), g(blk.gamma))
-        ln_re = isinstance(xh, tuple)  # (y, mean): the forward stored no normalised rows (mlp_fused bit 7)
-        if ln_re and not (fused_bwd and h is None and self._mlp_drop_xh(C, hw, M, dt, B)):
-            raise RuntimeError("this block's forward stored no normalised rows (mlp_fused bit 7) and the passes that re-normalise "
-                               "are switched off now: do not change `mlp_fused` between a forward and its backward")
+        ln_re = not plan.keep_xh  # the forward stored no normalised rows: y and the row means instead (MODE 7)
         u1 = None
         if ln_re:
             cs2 = self._za.take(2, 4 * C)  # {column sums of dh, u = sum_r dh' * mean}
@@ -595,12 +597,7 @@ class Engine:
             # dz = dout·W2 tile by tile (K = C is short) and writes dh directly (csrc/mlp.hip MODE 4) — one 4C-wide write
             # where the unfused pair (dz GEMM, then GRN / GELU backward over it) has two
             img2 = w.img2
-            if img2 is None:
-                # not packed by prepare() (mlp_fused bit 3 switched on between a forward and its backward): _block_bwd runs
-                # inside the backward segment's open task-list batch, where the pack would only be QUEUED while the passes below
-                # read the image right away — launch the list before going on
-                img2 = w.img2 = o.mlp_pack(w.W2T, w.W2, C)
-                o.flush()
+            assert img2 is not None  # plan.bwd != 0 needs bit 3 and MODE 4 at the forward: prepare() packed it then
             if fused_bwd == 2 and not stats_in_tn:  # statistics by recomputing dz tile by tile (P = Σ dz·g, S = Σ dz), nothing stored
                 o.mlp_bwd_stats(dout, img2, gact, PS[0], PS[1], M, C, hw)
             if stats_in_tn:
@@ -608,8 +605,8 @@ class Engine:
             else:
                 t = o.grn_bwd_stats(colsq, PS[0], w.grn_w, dgw, Sb=PS[1], dbeta=dgb)
             if ln_re:  # h recomputed from y re-normalised on chip; dz holds dh * rstd (MODE 7)
-                dz = o.mlp_bwd_dh_ln(dout, xh[0], xh[1], rstd, img2, w.img, w.b1f, s, t, cs2, M, C, hw)
-            elif h is None:  # h recomputed on chip from the normalised rows (MODE 5)
+                dz = o.mlp_bwd_dh_ln(dout, y, mean, rstd, img2, w.img, w.b1f, s, t, cs2, M, C, hw)
+            elif not plan.keep_h:  # h recomputed on chip from the normalised rows (MODE 5)
                 dz = o.mlp_bwd_dh_re(dout, xh, img2, w.img, w.b1f, s, t, db1f, M, C, hw)
             else:
                 dz = o.mlp_bwd_dh(dout, img2, h, s, t, db1f, M, C, hw)  # (named dz below: it holds dH)
@@ -625,10 +622,10 @@ class Engine:
         if ln_re:
             # dz = dh * rstd: the accumulator is rstd * dx^ already, x^ is re-formed from y in the epilogue; the weight gradient
             # contracts dz with y itself, dh^T x^ = dz^T y - u (x) 1 — the rank-1 term goes in the unfold below
-            dy = o.dgrad_ln_bwd(dz, w.W1fT, xh[0], rstd, M, C, 4 * C, mean=xh[1])
-            xh = xh[0]
-        else:
-            dy = o.dgrad_ln_bwd(dz, w.W1fT, xh, rstd, M, C, 4 * C) if hasattr(o, "dgrad_ln_bwd") else None
+            xh = y
+        # (a HIP kernel only; None: the shape is not served)
+        dy = o.dgrad_ln_bwd(dz, w.W1fT, xh, rstd, M, C, 4 * C, mean=mean) if self._hip else None
+        assert dy is not None or not ln_re  # the plan drops x^ only where this epilogue serves the shape
         dxh = None
         if dy is None:
             dxh = torch.empty((M, C), dtype=dt, device=dev)
@@ -661,7 +658,7 @@ class Engine:
         bf16 forward at 2048^2 differs by 7e-3 of the output maximum from run to run, the fixed order costs 0.3 % of a pass
         (profiles/r05_det_reduce.txt; VERDICT r5).  Training forwards keep the atomics unless the flag is set by hand;
         ``VSX_DET_INFER=0`` in the environment switches the automatic setting off."""
-        auto = (not need_bwd) and self.ops.__name__.endswith("viscy_amd.ops") and os.environ.get("VSX_DET_INFER", "1") != "0" \
+        auto = (not need_bwd) and self._hip and os.environ.get("VSX_DET_INFER", "1") != "0" \
             and L.lib().vsx_get_flag(b"det_reduce") == 0
         if not auto:
             return self._forward(x, dt, need_bwd, masks, bn_groups)
@@ -675,10 +672,12 @@ class Engine:
         """``masks``: None (dense) or, per encoder stage, ``(idx, inv, keep, L)`` int32 row maps of the FCMAE mask at that
         stage's resolution (see ``viscy_amd.fcmae.stage_row_maps``)."""
         o, cfg, m = self.ops, self.cfg, self.model
-        W = self.prepare(dt, need_bwd)
+        # read once: prepare() packs the weight images and every block of this forward plans its schedule from this value
+        self._mlp_flag = L.lib().vsx_get_flag(b"mlp_fused") if self._hip else 0
+        W = self.prepare(dt, need_bwd, self._mlp_flag)
         B, Cin, Z, H, Wd = x.shape
         za_key = ("fwd", B, H, Wd, masks is not None)
-        self._za = za = _ZeroArena(x.device, self._za_need.get(za_key, 0), self.ops)
+        self._za = za = _ZeroArena(x.device, self._za_need.get(za_key, 0), o)
         # FCMAE 2-D branch (fcmae.py:369-370): the reference runs conv2d whenever x.shape[2] == 1, whatever in_stack_depth is —
         # a 2-D FCMAE (in_stack_depth = 1) trains and loads its conv2d weights, never the conv3d ones (ADVICE r2)
         flat_stem = Z == 1 and "stem2d_W" in W
@@ -1067,8 +1066,6 @@ class Engine:
                 g(m.stem.conv.bias).add_(dbe.view(co3, Dp).sum(1))
             self._za_need[za_key] = za.used
             yield from self._segment_end(2)
-
-
         finally:
             self.ops.batch_close()
 

@@ -505,16 +505,17 @@ def _gelu_table(dev) -> Tensor:
     return t
 
 
+def _mlp_fwd(who: str, mode: int, xh: Tensor, ln_eps: float, img: Tensor, b1: Tensor, *operands, M: int, C: int, hw: int) -> None:
+    """vsx_mlp_fwd, or vsx_mlp_fwd_ln where ``ln_eps`` > 0; ``operands`` = (s, beta, b2, res, rscale, out, colsq)"""
+    tail = (ptr(img), ptr(b1), *(ptr(t) for t in operands), ptr(_gelu_table(xh.device)), M, C, hw, mode, dtype_code(xh.dtype), stream())
+    check(lib().vsx_mlp_fwd_ln(ptr(xh), ln_eps, *tail) if ln_eps > 0.0 else lib().vsx_mlp_fwd(ptr(xh), *tail), who)
+
+
 def mlp_stats(xh: Tensor, img: Tensor, b1: Tensor, colsq: Tensor, M: int, C: int, hw: int, ln_eps: float = 0.0) -> None:
     """colsq[b, 4C] += per-sample column sums of gelu(fc1(xh))^2 — nothing 4C-wide is written.  ``ln_eps`` > 0: ``xh`` holds the
     UN-normalised rows and the kernel applies the block LayerNorm (no affine) in its prologue"""
     _det(xh.device, (M // 256) * 4 * C)
-    if ln_eps > 0.0:
-        check(lib().vsx_mlp_fwd_ln(ptr(xh), ln_eps, ptr(img), ptr(b1), None, None, None, None, None, None, ptr(colsq),
-                                   ptr(_gelu_table(xh.device)), M, C, hw, 0, dtype_code(xh.dtype), stream()), "mlp_stats")
-        return
-    check(lib().vsx_mlp_fwd(ptr(xh), ptr(img), ptr(b1), None, None, None, None, None, None, ptr(colsq), ptr(_gelu_table(xh.device)),
-                            M, C, hw, 0, dtype_code(xh.dtype), stream()), "mlp_stats")
+    _mlp_fwd("mlp_stats", 0, xh, ln_eps, img, b1, None, None, None, None, None, None, colsq, M=M, C=C, hw=hw)
 
 
 def mlp_fc1(xh: Tensor, img: Tensor, b1: Tensor, colsq: Tensor, M: int, C: int, hw: int, store_h: bool = True):
@@ -561,11 +562,16 @@ def mlp_bwd_stats(dout: Tensor, img2: Tensor, g: Tensor, P: Tensor, S: Tensor, M
           "mlp_bwd_stats")
 
 
-def mlp_bwd_dh(dout: Tensor, img2: Tensor, h: Tensor, s: Tensor, t: Tensor, colsum: Tensor, M: int, C: int, hw: int) -> Tensor:
-    """dh = (dz * s + gelu(h) * t) * gelu'(h), dz recomputed; colsum[4C] += column sums of dh"""
+def _mlp_dh_alloc(dout: Tensor, M: int, C: int, hw: int, ws_cols: int):
+    """what the three dh passes allocate: dh [M, 4C], and the workspace of one row of ``ws_cols`` column sums per workgroup"""
     dh = torch.empty((M, 4 * C), dtype=dout.dtype, device=dout.device)
     rows = M // int(lib().vsx_mlp_rows_per_workgroup(C, hw, M))
-    ws = _workspace(dout.device, rows * 4 * C)
+    return dh, _workspace(dout.device, rows * ws_cols), rows
+
+
+def mlp_bwd_dh(dout: Tensor, img2: Tensor, h: Tensor, s: Tensor, t: Tensor, colsum: Tensor, M: int, C: int, hw: int) -> Tensor:
+    """dh = (dz * s + gelu(h) * t) * gelu'(h), dz recomputed; colsum[4C] += column sums of dh"""
+    dh, ws, rows = _mlp_dh_alloc(dout, M, C, hw, 4 * C)
     check(lib().vsx_mlp_bwd_dh(ptr(dout), ptr(img2), ptr(h), ptr(s), ptr(t), ptr(dh), ptr(ws), rows, ptr(colsum),
                                ptr(_gelu_table(dout.device)), M, C, hw, dtype_code(dout.dtype), stream()), "mlp_bwd_dh")
     return dh
@@ -575,9 +581,7 @@ def mlp_bwd_dh_re(dout: Tensor, xh: Tensor, img2: Tensor, img: Tensor, b1: Tenso
                   hw: int) -> Tensor:
     """mlp_bwd_dh without a stored pre-activation: h = xh . W1'^T + b1 is recomputed on chip from the normalised rows (img = the
     forward image mlp_pack(W1f, W2), b1 = the folded fc1 bias: bit-identical to what mlp_fc1 would have stored)"""
-    dh = torch.empty((M, 4 * C), dtype=dout.dtype, device=dout.device)
-    rows = M // int(lib().vsx_mlp_rows_per_workgroup(C, hw, M))
-    ws = _workspace(dout.device, rows * 4 * C)
+    dh, ws, rows = _mlp_dh_alloc(dout, M, C, hw, 4 * C)
     check(lib().vsx_mlp_bwd_dh_re(ptr(dout), ptr(xh), ptr(img2), ptr(img), ptr(b1), ptr(s), ptr(t), ptr(dh), ptr(ws), rows, ptr(colsum),
                                   ptr(_gelu_table(dout.device)), M, C, hw, dtype_code(dout.dtype), stream()), "mlp_bwd_dh_re")
     return dh
@@ -588,9 +592,7 @@ def mlp_bwd_dh_ln(dout: Tensor, y: Tensor, mean: Tensor, rstd: Tensor, img2: Ten
     """mlp_bwd_dh_re for a block that stored no normalised rows: x^ is re-formed from the LayerNorm input ``y`` and its row
     statistics; returns dh' = dh * rstd (row-scaled); colsum2 [2, 4C] += {column sums of the UNSCALED dh, u = sum_r dh' * mean}
     (see vsx_mlp_bwd_dh_ln for what the consumers do with them)"""
-    dh = torch.empty((M, 4 * C), dtype=dout.dtype, device=dout.device)
-    rows = M // int(lib().vsx_mlp_rows_per_workgroup(C, hw, M))
-    ws = _workspace(dout.device, rows * 8 * C)
+    dh, ws, rows = _mlp_dh_alloc(dout, M, C, hw, 8 * C)
     check(lib().vsx_mlp_bwd_dh_ln(ptr(dout), ptr(y), ptr(mean), ptr(rstd), ptr(img2), ptr(img), ptr(b1), ptr(s), ptr(t), ptr(dh), ptr(ws),
                                   rows, ptr(colsum2), ptr(_gelu_table(dout.device)), M, C, hw, dtype_code(dout.dtype), stream()),
           "mlp_bwd_dh_ln")
@@ -601,12 +603,7 @@ def mlp_out(xh: Tensor, img: Tensor, b1: Tensor, s: Tensor, beta: Tensor, b2: Te
             M: int, C: int, hw: int, ln_eps: float = 0.0) -> Tensor:
     """out = res + rscale * (fc2(gelu(fc1(xh)) * s + beta) + b2), hidden activation kept on chip (``ln_eps``: see mlp_stats)"""
     out = torch.empty((M, C), dtype=xh.dtype, device=xh.device)
-    if ln_eps > 0.0:
-        check(lib().vsx_mlp_fwd_ln(ptr(xh), ln_eps, ptr(img), ptr(b1), ptr(s), ptr(beta), ptr(b2), ptr(res), ptr(rscale), ptr(out),
-                                   None, ptr(_gelu_table(xh.device)), M, C, hw, 1, dtype_code(xh.dtype), stream()), "mlp_out")
-        return out
-    check(lib().vsx_mlp_fwd(ptr(xh), ptr(img), ptr(b1), ptr(s), ptr(beta), ptr(b2), ptr(res), ptr(rscale), ptr(out), None,
-                            ptr(_gelu_table(xh.device)), M, C, hw, 1, dtype_code(xh.dtype), stream()), "mlp_out")
+    _mlp_fwd("mlp_out", 1, xh, ln_eps, img, b1, s, beta, b2, res, rscale, out, None, M=M, C=C, hw=hw)
     return out
 
 
