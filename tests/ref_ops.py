@@ -56,6 +56,21 @@ def gemm(kind, A, B, Cout, M, N, K, lda, ldb, ldc, *, dtype, a_mode=A_ROWS, gh=0
         a = rd(_gather(A, M, K, lda, a_mode, gh, gw, cs, a_coff[z], pro, grn_s, grn_b, hw))
         if kind == "tn":
             X = B.reshape(-1, ldb).float()[:M, b_off[z] : b_off[z] + N]
+            if b_bstride:  # one product and one column sum PER SAMPLE, stored (not accumulated)
+                for bb in range(M // hw):
+                    rows = slice(bb * hw, (bb + 1) * hw)
+                    Cout.reshape(-1)[c_coff[z] + bb * b_bstride :].as_strided((N, K), (ldc, 1)).copy_(X[rows].t() @ a[rows])
+                    if colsum is not None:
+                        colsum.view(-1, N)[bb] = X[rows].sum(0)
+                continue
+            if pro == PRO_GRN and aux is not None and red0 is not None:
+                # the weight gradient that also delivers the GRN statistics: P[b, k] += sum_n W2[n, k] Q_b[n, k] with
+                # Q_b = X_b^T g_b on the operand BEFORE the prologue (= sum_hw dz g, dz = X . W2)
+                graw = rd(_gather(A, M, K, lda, a_mode, gh, gw, cs, a_coff[z], PRO_NONE, None, None, hw))
+                W2 = aux.reshape(-1, ldx).float()[:N, :K]
+                for bb in range(M // hw):
+                    rows = slice(bb * hw, (bb + 1) * hw)
+                    red0[bb] += (W2 * (X[rows].t() @ graw[rows])).sum(0)
             Wv = Cout.reshape(-1)[c_coff[z] :].as_strided((N, K), (ldc, 1))
             Wv += X.t() @ a
             if colsum is not None:

@@ -74,11 +74,14 @@ GEMM_CASES = [
     (640, 224, 144, 320),
     (384, 32, 216, 384),
     (130, 8, 64, 130),
-    (512, 384, 256, 256),   # lean instantiation, 128-byte K slabs (BK = 64, single LDS buffer), 3 N tiles
-    (1024, 224, 512, 512),  # lean, BK = 64, ragged last N tile
-    (384, 192, 224, 128),   # lean, BK = 32 (K % 64 != 0)
-    (448, 384, 256, 64),    # lean with TWO samples per 128-row tile (8 x 8 feature maps), odd sample count, BK = 64
-    (512, 192, 96, 64),     # the same, BK = 32
+    # dispatch_nt sends a bf16 launch with N > 64, K >= 256 and fewer than 512 tiles to the generic kernel with BK = 128, so of the
+    # rows below only those with K < 256 reach the lean kernel in bf16 (BK = 32, one LDS buffer); its BK = 64 instantiations and
+    # every other leg are held per case, with the dispatched family checked, in tests/test_gpu_gemm_exact.py
+    (512, 384, 256, 256),   # 3 N tiles; fp32: lean kernel, bf16: generic, BK = 128 (12 tiles, K >= 256)
+    (1024, 224, 512, 512),  # ragged last N tile; fp32: lean, bf16: generic, BK = 128
+    (384, 192, 224, 128),   # lean in both dtypes (K < 256); bf16: BK = 32
+    (448, 384, 256, 64),    # TWO samples per 128-row tile (8 x 8 feature maps), odd sample count; fp32: lean, bf16: generic, BK = 128
+    (512, 192, 96, 64),     # the same on the lean kernel in both dtypes; bf16: BK = 32
 ]
 
 
@@ -135,7 +138,7 @@ NT2_CASES = [
     (1024, 384, 1536, 1024), # one 384-wide tile
     (512, 3072, 96, 64),     # eight 384-wide tiles, four samples per tile
     (512, 448, 64, 256),     # 384 + ragged 64: two 256-wide tiles
-    (256, 896, 224, 256),    # 256-wide tiles, ragged last (128 used)
+    (256, 896, 224, 256),    # three 384-wide tiles (pick_bn), ragged last (128 used)
 ]
 
 
