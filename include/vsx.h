@@ -127,6 +127,28 @@ int32_t vsx_gemm_nt_ln_bwd_supported(int64_t M, int32_t N, int32_t K, int32_t dt
 /* weight-gradient GEMM (contraction over pixels) for the same layers */
 int32_t vsx_gemm_tn(const VsxGemm* p, int32_t dtype, vsx_stream_t stream);
 
+/* What vsx_gemm_nt / vsx_gemm_tn would launch for these parameters under the current flags, decided from the flags and the
+ * fields of VsxGemm alone (pointer fields are only tested for NULL; no GPU is needed).  The numbers are the template arguments of
+ * the kernel that runs, 0 where it has no such parameter. */
+typedef struct VsxGemmPlan {
+  const char* family;   /* what vsx_last_kernel reports after the launch */
+  int32_t esize;        /* bytes per operand element: 2 (bf16) or 4 */
+  int32_t tile[2];      /* output tile.  NT: rows x columns of C (BM x BN);  TN: tile N x tile K of W */
+  int32_t step;         /* contraction depth per LDS stage.  NT: BK;  TN: pixel rows (0: the generic TN kernel) */
+  int32_t nbuf;         /* LDS buffers / stages */
+  int32_t pro_kind;     /* 0 none, 1 GRN prologue, 2 (TN) GRN prologue with the backward statistics */
+  int32_t tr;           /* TN: transposing LDS reads */
+  int32_t epi;          /* NT: VSX_EPI_* */
+  int32_t grid[3], block;
+  int32_t pro_bits;     /* kernel-side flag bits the launch ORs into VsxGemm.pro */
+  int64_t zero_c, zero_colsum; /* TN: floats of C / colsum zero-filled before the launch (per-sample outputs in several splits) */
+  int64_t det_floats;   /* NT: workspace floats of the fixed-order sums (det_reduce), 0 = none */
+} VsxGemmPlan;
+#define VSX_GEMM_NT 0
+#define VSX_GEMM_TN 1
+/* 0 and *out filled, or the return code and vsx_last_error of the launch that would be refused */
+int32_t vsx_gemm_plan(int32_t kind, const VsxGemm* p, int32_t dtype, VsxGemmPlan* out);
+
 
 /* =============================================================================================
  * Remaining entry points (one per fused kernel of the path).  `ws` arguments are caller-owned fp32

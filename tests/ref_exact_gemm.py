@@ -19,7 +19,8 @@ Every operand sits inside a wider buffer whose other columns hold ``SENT``; NT o
 Each GEMM case names the kernel family (``vsx_last_kernel``) that the shipped dispatch sends it to, for each dtype; the runner
 compares after every launch, so a case whose dispatch has moved fails instead of reporting a coverage it no longer gives.  The
 instantiation below the family is not observable through the ABI: the ``leg`` string of a case records it together with the
-dispatch condition that selects it (dispatch_nt / nt_fast_ok / launch_nt_fast / vsx_gemm_nt2_ok / pick_bn / launch_tn).
+dispatch condition that selects it (plan_nt / nt_fast_ok / vsx_gemm_nt2_ok / pick_bn / plan_tn of csrc/gemm.hip); the runner also asks
+vsx_gemm_plan for the same parameters and flags and compares its family with the listed one.
 
 A runner takes the op namespace as an argument, so the same tables run on ``viscy_amd.ops`` (GPU) and on the plain-PyTorch
 statements of tests/ref_ops.py (CPU).  No GPU is needed to import this module."""
@@ -81,10 +82,21 @@ class Flags:
         """the flag settings of a sweep; one empty setting where there are no flags to set"""
         return list(sweep) if self.lib is not None else [{}]
 
-    def check_family(self, want: str, what: str) -> None:
+    @staticmethod
+    def plan_of(ops, kind, *args, **kw):
+        """what ``ops.gemm`` with these arguments would launch (one host call, no launch)"""
+        from viscy_amd._lib import VsxGemmPlan
+
+        plan = VsxGemmPlan()
+        ops.gemm(kind, *args, plan=plan, **kw)
+        return plan
+
+    def check_family(self, want: str, what: str, plan=None) -> None:
+        """``plan``: what vsx_gemm_plan answers for the parameters and flags of the launch just made"""
         if self.lib is None:
             return
         got = self.lib.vsx_last_kernel().decode()
+        assert plan is None or plan.family.decode() == want, f"{what}: listed under {want}, planned as {plan.family.decode()}"
         assert got == want, (f"{what}: the case table lists this launch under {want}, the library dispatched it to {got}: the "
                              f"dispatch has moved and this case no longer covers the kernel it is listed for")
 
@@ -187,20 +199,20 @@ def nt(name, M, N, K, hw, epis, fam, leg, dts=BOTH, flags=({},), **kw):
 
 def nt_cases():
     c = []
-    # ---- generic tiles (N <= 64: launch_nt<128, 64 / 32 / 16>, BK = 32); ragged rows, tiles that span several samples
+    # ---- generic tiles (N <= 64: gemm_nt_kernel<T, 128, 64 / 32 / 16>, BK = 32); ragged rows, tiles that span several samples
     gen = [(130, 8, 72, 100), (8, 16, 8, 4), (200, 24, 40, 100), (130, 32, 8, 4), (200, 40, 72, 4), (8, 64, 40, 4)]
     for M, N, K, hw in gen:
         bn = 16 if N <= 16 else (32 if N <= 32 else 64)
-        c.append(nt(f"generic_{M}x{N}x{K}_hw{hw}", M, N, K, hw, ALL6, NT_GEN, f"N <= {bn}: launch_nt<128, {bn}, .., 32>"))
+        c.append(nt(f"generic_{M}x{N}x{K}_hw{hw}", M, N, K, hw, ALL6, NT_GEN, f"N <= {bn}: gemm_nt_kernel<T, 128, {bn}, .., 32>"))
     c.append(nt("generic_grn_200x40x72_hw100", 200, 40, 72, 100, ("none", "res"), NT_GEN, "N <= 64, GRN prologue in lstore", pro=R.PRO_GRN))
-    c.append(nt("generic_n72_lean_off", 200, 72, 40, 100, ALL6, NT_GEN, "N > 64 with nt_fast = 0: launch_nt<128, 128, 2, 2, 32>",
+    c.append(nt("generic_n72_lean_off", 200, 72, 40, 100, ALL6, NT_GEN, "N > 64 with nt_fast = 0: gemm_nt_kernel<T, 128, 128, 2, 2, 32>",
                 flags=({"nt_fast": 0},)))
     # ---- generic BK = 128 leg: bf16, N > 64, K >= 256, fewer than 512 tiles, not taken by gemm_nt2 (shipped nt2 = 17 wants
     #      >= 256 tiles and K >= 768; M % 256 != 0 here in any case)
-    c.append(nt("generic_bk128_200x96x264_hw100", 200, 96, 264, 100, ALL6, NT_GEN, "tiles < 512 && K >= 256: launch_nt<128, 128, 2, 2, 128>; K % 128 = 8",
+    c.append(nt("generic_bk128_200x96x264_hw100", 200, 96, 264, 100, ALL6, NT_GEN, "tiles < 512 && K >= 256: gemm_nt_kernel<T, 128, 128, 2, 2, 128>; K % 128 = 8",
                 dts=(BF16,)))
     c.append(nt("generic_bk128_384x224x512_hw128", 384, 224, 512, 128, ALL6, NT_GEN,
-                "launch_nt<128, 128, 2, 2, 128>, ragged last N tile (M % 256 != 0: gemm_nt2 cannot take it at any nt2)", dts=(BF16,)))
+                "gemm_nt_kernel<T, 128, 128, 2, 2, 128>, ragged last N tile (M % 256 != 0: gemm_nt2 cannot take it at any nt2)", dts=(BF16,)))
     # ---- gemm_nt_fast_kernel
     c.append(nt("lean_bk32_384x192x224_hw128", 384, 192, 224, 128, LEAN, NT_FAST,
                 "K < 256, N > 64, K % 32 == 0: bf16 <32, 1> (nt_wide != 0: BK = 32, one LDS buffer), fp32 the default instantiation"))
@@ -220,7 +232,7 @@ def nt_cases():
     c.append(nt("lean_two_samples_grn_448x192x224_hw64", 448, 192, 224, 64, ("none", "res"), NT_FAST, "hw = 64 with the GRN prologue (s row per tile row)",
                 pro=R.PRO_GRN))
     c.append(nt("lean_per_sample_weights_512x96x64_hw128", 512, 96, 64, 128, ("none", "res", "res_rscale"), NT_FAST,
-                "b_bstride != 0: dispatch_nt sends it to the lean kernel (hw % 128 == 0)", bstride=True))
+                "b_bstride != 0: plan_nt sends it to the lean kernel (hw % 128 == 0)", bstride=True))
     # BK = 64 instantiations: bf16, K % 64 == 0, K >= 256; 172 x 3 = 516 tiles, the fewest that pass the `tiles < 512` test of the
     # BK = 128 generic leg (gemm_nt2 as shipped does not take K < 768)
     c.append(nt("lean_bk64_22016x384x256_hw128", 172 * 128, 384, 256, 128, ("none", "res_rscale", "dz"), NT_FAST,
@@ -381,7 +393,8 @@ def run_nt_case(ops, case, dt, device, flags: Flags = Flags()) -> None:
                     ops.gemm_z("nt", *args, nz=nz, a_coff=a_coff, b_off=[0] * nz, c_coff=c_coff, **kw)
                 else:
                     ops.gemm("nt", *args, a_coff=a_coff, c_coff=c_coff, **kw)
-                flags.check_family(family_of(case, dt), what)
+                plan = None if flags.lib is None else flags.plan_of(ops, "nt", *args, nz=min(nz, 8), a_coff=a_coff[:8], c_coff=c_coff[:8], **kw)
+                flags.check_family(family_of(case, dt), what, plan)
                 ref = patch2_scatter_ref(c64, *case["grid"]) if scatter else c64
                 assert_bit_equal(C[:, PAD:PAD + cw], ref, what + " C")
                 assert_sentinel(C, PAD, cw, what + " C")
@@ -560,8 +573,10 @@ def run_tn_case(ops, case, dt, device, flags: Flags = Flags()) -> None:
                 assert flags.lib is None or ops.tn_grn_stats_ok(M, N, K, hw, dt), what + ": not served"
                 P = f32(fx["P_old"])
                 kw.update(aux=W2, ldx=ldx, red0=P)
-            ops.gemm("tn", Y, X, Wb, M, N, K, lda, ldb, ldc, a_coff=[PAD], b_off=[PAD], c_coff=[coff], **kw)
-            flags.check_family(family_of(case, dt), what)
+            args = (Y, X, Wb, M, N, K, lda, ldb, ldc)
+            ops.gemm("tn", *args, a_coff=[PAD], b_off=[PAD], c_coff=[coff], **kw)
+            plan = None if flags.lib is None else flags.plan_of(ops, "tn", *args, a_coff=[PAD], b_off=[PAD], c_coff=[coff], **kw)
+            flags.check_family(family_of(case, dt), what, plan)
             if case["per_sample"]:
                 assert_bit_equal(Wb, fx["W"].reshape(-1, K), what + " per-sample products (rows = sample * N + n)")
             else:

@@ -40,21 +40,23 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layout_matches_header():
-    """VsxGemm is passed by pointer: field count / order of the ctypes mirror must track the header."""
+    """VsxGemm and VsxGemmPlan are passed by pointer: field count / order of the ctypes mirrors must track the header."""
     from viscy_amd import _lib
 
     src = open(os.path.join(ROOT, "include", "vsx.h")).read()
-    body = src[src.index("typedef struct VsxGemm {") + len("typedef struct VsxGemm {") : src.index("} VsxGemm;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl or decl.startswith("typedef"):
-            continue
-        for part in decl.split(","):
-            m = re.search(r"(\w+)\s*(\[\d+\])?\s*$", part.strip())
-            names.append(m.group(1))
-    assert names == [f[0] for f in _lib.VsxGemm._fields_]
+    for struct in ("VsxGemm", "VsxGemmPlan"):
+        head = "typedef struct %s {" % struct
+        body = src[src.index(head) + len(head) : src.index("} %s;" % struct)]
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if not decl or decl.startswith("typedef"):
+                continue
+            for part in decl.split(","):
+                m = re.search(r"(\w+)\s*(\[\d+\])?\s*$", part.strip())
+                names.append(m.group(1))
+        assert names == [f[0] for f in getattr(_lib, struct)._fields_], struct
 
 
 def test_no_cpu_fallback():

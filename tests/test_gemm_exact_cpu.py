@@ -5,7 +5,7 @@
    conditions;
 2. the tables reach what they claim to reach: dtypes, flag settings, every generic tile width, the BK = 128 leg, the lean
    kernel's K tails / patch gather and scatter / two samples per tile / BK = 64 instantiations, the three gemm_nt2 tile widths,
-   the 64-, 128- and both rectangular TN tiles (from the conditions of launch_tn), split sweeps, statistics and per-sample forms;
+   the 64-, 128- and both rectangular TN tiles (asked of vsx_gemm_plan), split sweeps, statistics and per-sample forms;
 3. sensitivity: the reference namespace wrapped in mutants, each of which makes ONE subtle indexing error, fails the runner;
 4. the same mutants pass ``close()`` of tests/test_gpu_ops.py on that file's random operands: the gap these tests close."""
 
@@ -90,15 +90,16 @@ def test_case_tables_are_well_formed():
     assert {c["patch"][2] for c in tn if c["patch"]} >= {4, 8, 24, 32, 64, 128}
     assert all((c["M"] % 32 != 0 or bool(c["patch"] and c["patch"][2] == 24)) == (c["fam"] == X.TN_GEN) for c in tn)
     assert max(c["M"] * max(c["N"], c["K"]) for c in tn) == 65536 * 128
-    # which tile a bf16 launch with transposing reads gets (launch_tn as shipped: tn_rect = 11, 64-row steps need M % 64 == 0)
+    # which tile a bf16 launch with transposing reads gets, as shipped: asked of the library's own planner (vsx_gemm_plan)
+    import ctypes
+
+    from tests import gemm_plan_rows as G
+    from viscy_amd import _lib
+
     def tile(c):
-        cd = lambda a, b: -(-a // b)
-        if c["N"] < 96 or c["K"] < 96 or (cd(c["N"], 128) * cd(c["K"], 128) < 24 and c["M"] < 65536):
-            return "64"
-        n_div = c["N"] % 256 == 0 and c["K"] >= 128 and c["pro"] == R.PRO_NONE
-        n_full = (224 <= c["N"] <= 256 and c["K"] >= 256) or n_div
-        k_full = not n_full and 224 <= c["K"] <= 256 and c["N"] >= 256
-        return "256x128" if n_full else ("128x256" if k_full else "128")
+        arr, plan = G.struct_array([G.tn_case_row(c)]), _lib.VsxGemmPlan()
+        assert _lib.lib().vsx_gemm_plan(G.TN, arr, G.BF16, ctypes.byref(plan)) == 0, c["name"]
+        return str(plan.tile[0]) if plan.tile[0] == plan.tile[1] else f"{plan.tile[0]}x{plan.tile[1]}"
     plain = [c for c in tn if not (c["stats"] or c["per_sample"] or c["patch"])]
     for c in plain:
         want = {"t64": "64", "t128": "128", "rect_n": "256x128", "rect_k": "128x256"}
@@ -134,6 +135,68 @@ def test_operands_are_embedded_between_sentinels():
     W = seen["C"]
     assert seen["kind"] == "tn" and c0 > 0 and bool((W[:, :c0] == X.SENT).all()) and float(W[:, c0:c0 + 32].abs().max()) <= 8
     assert torch.equal(W[:, c0:c0 + 32], W[:, c0:c0 + 32].round()) and float(W[:, c0:c0 + 32].abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------------------------ 2b. the dispatch
+def _instantiations():
+    """every kernel instantiation the GEMM dispatch can launch, as (family, esize, tile0, tile1, step, nbuf, pro_kind, tr, epi)"""
+    s = set()
+    for es, trs in ((2, (1, 0)), (4, (0,))):
+        for tr in trs:
+            for bt in (64, 128):
+                s.add((X.TN_GEN, es, bt, bt, 0, 0, 0, tr, 0))
+                s.update((X.TN_FAST, es, bt, bt, 32, 2, pro, tr, 0) for pro in (0, 1))
+            if es == 2:
+                s.update((X.TN_FAST, 2, 128, 128, 64, 1, pro, tr, 0) for pro in (0, 1))
+    s.update((X.TN_FAST, 2, tn, tk, 64, 1, pro, 1, 0) for tn, tk in ((256, 128), (128, 256)) for pro in (0, 1))
+    s.add((X.TN_FAST, 2, 128, 128, 64, 1, 2, 1, 0))
+    for es in (2, 4):
+        s.update((X.NT_GEN, es, 128, bn, 32, 2, 0, 0, 0) for bn in (128, 64, 32, 16))
+        for bk, nbuf in (((64, 1), (64, 2), (32, 1), (32, 2)) if es == 2 else ((32, 2),)):
+            s.update((X.NT_FAST, es, 128, 128, bk, nbuf, pro, 0, epi) for pro in (0, 1) for epi in range(5))
+    s.add((X.NT_GEN, 2, 128, 128, 128, 2, 0, 0, 0))
+    for bn in (128, 256, 384):
+        s.update((X.NT2, 2, 256, bn, 32, 3, 0, 0, epi) for epi in range(5))
+        s.update((X.NT2, 2, 256, bn, 32, 3, 1, 0, epi) for epi in (R.EPI_NONE, R.EPI_BIAS_RES))
+    s.update((X.NT2, 2, 256, bn, 32, 3, 0, 0, 6) for bn in (128, 256))   # VSX_EPI_LN_BWD
+    return s
+
+
+def test_plans_equal_the_recorded_dispatch():
+    """vsx_gemm_plan on every row of tests/gemm_plan_rows.py against tests/golden/gemm_plan_table.json, which holds what the launch
+    sites of the commit before the plan / run split did for the same rows (family, template arguments, grid, the bits in ``pro``,
+    zero-fills, fixed-order sums; return code and error text of a refusal): no row differs, none is left out, and the table
+    reaches every one of that commit's instantiations (27 TN, 59 NT, 23 gemm_nt2)."""
+    import base64
+    import json
+    import lzma
+    import os
+
+    import numpy as np
+
+    from tests import gemm_plan_rows as G
+    from viscy_amd import _lib
+
+    table = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "gemm_plan_table.json")))
+    assert tuple(table["fields"]) == G.FIELDS
+    lib = _lib.lib()
+    if not os.environ.get("VSX_FLAGS"):
+        assert all(lib.vsx_get_flag(f.encode()) == v for f, v in G.SHIPPED.items())
+    got, strings = G.walk_plans(lib)
+    unpack = lambda pieces, dt: np.frombuffer(lzma.decompress(base64.b64decode("".join(pieces))), dtype=dt)
+    idx = unpack(table["rows"], "<u2")
+    codes = unpack(table["codes"], "<i8").reshape(len(G.FIELDS), table["n_codes"]).T
+    assert len(idx) == table["n_rows"] == len(got) > 1_000_000
+    want = codes[idx]
+    text = {s: i for i, s in enumerate(table["strings"])}
+    got[:, 1] = np.array([text.get(s, -1) for s in strings])[got[:, 1]]
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert len(bad) == 0, (len(bad), [(int(i), dict(zip(G.FIELDS, got[i].tolist())), dict(zip(G.FIELDS, want[i].tolist()))) for i in bad[:5]])
+    codes = codes.tolist()
+    launched = {(table["strings"][c[1]], *c[2:10]) for c in codes if c[0] == 0}
+    assert launched == _instantiations() and len(launched) == 27 + 59 + 23
+    refusals = {table["strings"][c[1]] for c in codes if c[0] != 0}
+    assert len(refusals) >= 25 and all(c[0] == 1 for c in codes if c[0] != 0)
 
 
 # ------------------------------------------------------------------------------------------------ 3. sensitivity

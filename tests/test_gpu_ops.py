@@ -74,7 +74,7 @@ GEMM_CASES = [
     (640, 224, 144, 320),
     (384, 32, 216, 384),
     (130, 8, 64, 130),
-    # dispatch_nt sends a bf16 launch with N > 64, K >= 256 and fewer than 512 tiles to the generic kernel with BK = 128, so of the
+    # plan_nt (csrc/gemm.hip) sends a bf16 launch with N > 64, K >= 256 and fewer than 512 tiles to the generic kernel with BK = 128, so of the
     # rows below only those with K < 256 reach the lean kernel in bf16 (BK = 32, one LDS buffer); its BK = 64 instantiations and
     # every other leg are held per case, with the dispatched family checked, in tests/test_gpu_gemm_exact.py
     (512, 384, 256, 256),   # 3 N tiles; fp32: lean kernel, bf16: generic, BK = 128 (12 tiles, K >= 256)

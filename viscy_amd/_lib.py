@@ -44,6 +44,15 @@ class VsxGemm(C.Structure):
     ]
 
 
+class VsxGemmPlan(C.Structure):
+    """what vsx_gemm_plan answers (include/vsx.h)"""
+    _fields_ = [
+        ("family", C.c_char_p), ("esize", _I32), ("tile", _I32 * 2), ("step", _I32), ("nbuf", _I32), ("pro_kind", _I32), ("tr", _I32),
+        ("epi", _I32), ("grid", _I32 * 3), ("block", _I32), ("pro_bits", _I32), ("zero_c", _I64), ("zero_colsum", _I64),
+        ("det_floats", _I64),
+    ]
+
+
 class VsxWTask(C.Structure):
     """one job of vsx_weight_tasks (include/vsx.h)"""
     _fields_ = [("kind", _I32), ("dtype", _I32), ("i0", _I32), ("i1", _I32), ("i2", _I32), ("i3", _I32),
@@ -62,6 +71,7 @@ _SIGS = {
     "vsx_det_workspace": (_I32, [_P, _I64]),
     "vsx_gemm_nt": (_I32, [C.POINTER(VsxGemm), _I32, _P]),
     "vsx_gemm_tn": (_I32, [C.POINTER(VsxGemm), _I32, _P]),
+    "vsx_gemm_plan": (_I32, [_I32, C.POINTER(VsxGemm), _I32, C.POINTER(VsxGemmPlan)]),
     "vsx_gemm_nt_ln_bwd_supported": (_I32, [_I64, _I32, _I32, _I32]),
     "vsx_ln_fwd": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _F32, _I32, _P]),
     "vsx_ln_bwd": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),

@@ -19,7 +19,8 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 bool vsx_gemm_nt2_ok(const VsxGemm* p);           // gemm_nt2.hip
 bool vsx_gemm_nt2_lnbwd_ok(const VsxGemm* p);
-int vsx_gemm_nt2(const VsxGemm* p, hipStream_t s);
+void vsx_gemm_nt2_plan(const VsxGemm* p, VsxGemmPlan& pl);  // (once vsx_gemm_nt2_ok has said yes)
+int vsx_gemm_nt2_run(const VsxGemmPlan& pl, const VsxGemm* p, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // operand gather: returns the 16-byte chunk holding A(m, k .. k+VN-1) after the prologue
@@ -672,7 +673,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 2 : ((BK == 64 && NBUF == 1) ? 3 :
 #pragma unroll
   for (int j = 0; j < VN; ++j) { r0[j] = 0.f; r1[j] = 0.f; }
   const size_t ccol = (size_t)p.c_coff[z] + n;
-  const bool ntst = (EPI == VSX_EPI_BIAS_GELU_SQ || EPI == VSX_EPI_DZ) && (p.pro & 256) != 0;  // set by launch_nt_fast
+  const bool ntst = (EPI == VSX_EPI_BIAS_GELU_SQ || EPI == VSX_EPI_DZ) && (p.pro & 256) != 0;  // set by the launcher (plan_nt)
   const bool ntld = EPI == VSX_EPI_DZ && (p.pro & 512) != 0;  // the dZ epilogue is the last reader of the stored activation
 #pragma unroll 1
   for (int half = 0; half < NPASS; ++half) {
@@ -804,40 +805,23 @@ __global__ __launch_bounds__(256, BM == 256 ? 2 : ((BK == 64 && NBUF == 1) ? 3 :
   }
 }
 
-template <typename T, int EPI, bool PRO>
-static int launch_nt_fast(const VsxGemm* pin, hipStream_t s) {
-  g_vsx_last_kernel = "gemm_nt_fast";
-  VsxGemm pq = *pin;
-  if (g_vsx_nt_stream & 1) pq.pro |= 256;
-  if (g_vsx_nt_stream & 2) pq.pro |= 512;  // kernel-side flag bit (the prologue kind itself is a template parameter there)
-  const VsxGemm* p = &pq;
-  int tiles = vsx_cdiv(p->M, 128) * vsx_cdiv(p->N, 128);
-  dim3 grid(tiles, 1, p->nz > 0 ? p->nz : 1);
-  if constexpr (sizeof(T) == 2) {
-    const bool k64 = p->K % 64 == 0 && p->K >= 256 && (p->a_mode == VSX_A_ROWS || p->cs % 64 == 0);
-    if (g_vsx_nt_wide == 1 && k64) {
-      hipLaunchKernelGGL((gemm_nt_fast_kernel<T, EPI, PRO, 64, 1>), grid, dim3(256), 0, s, *p);
-      VSX_LAUNCH_CHECK();
-      return 0;
-    }
-    if (g_vsx_nt_wide == 2 && k64) {
-      hipLaunchKernelGGL((gemm_nt_fast_kernel<T, EPI, PRO, 64, 2>), grid, dim3(256), 0, s, *p);
-      VSX_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (g_vsx_nt_wide) {
-      // short K (fc1, fc2 data gradient: epilogue-dominated): BK = 32 with ONE LDS buffer = 33.8 KB, 124 registers ->
-      // 4 workgroups per CU instead of 3 (measured -5..-10 % on these launches)
-      hipLaunchKernelGGL((gemm_nt_fast_kernel<T, EPI, PRO, 32, 1>), grid, dim3(256), 0, s, *p);
-      VSX_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  hipLaunchKernelGGL((gemm_nt_fast_kernel<T, EPI, PRO>), grid, dim3(256), 0, s, *p);
-  VSX_LAUNCH_CHECK();
-  return 0;
+// ------------------------------------------------------------------------------------------------
+// Dispatch.  plan_nt / plan_tn decide a launch from the flags and the fields of VsxGemm alone (no HIP call, no pointer
+// dereferenced) and write it down as a VsxGemmPlan (include/vsx.h; vsx_gemm_plan hands it out); run_nt / run_tn copy the
+// parameters once, OR the plan's bits into `pro`, zero-fill if asked and launch the instantiation the plan names.
+// ------------------------------------------------------------------------------------------------
+static const char* const FAM_NT_FAST = "gemm_nt_fast";
+static const char* const FAM_NT_GEN = "gemm_nt_generic";
+static const char* const FAM_TN_FAST = "gemm_tn_fast";
+static const char* const FAM_TN_GEN = "gemm_tn_generic";
+
+// one number per instantiation: the plan's template arguments (0 where a kernel has no such parameter).  Bits: 0 generic, 1 bf16,
+// 2 tr, 3-4 pro (0 .. 2), 5-6 nbuf (0 .. 3), 7-9 epi (0 .. 6), 10-12 step / 32 (0 .. 4), 13-17 and 18-22 tile / 16 (<= 24: 384 wide)
+constexpr unsigned inst_key(bool generic, int es, int t0, int t1, int step, int nbuf, int pro, bool tr, int epi) {
+  return (unsigned)generic | (es == 2) << 1 | tr << 2 | pro << 3 | nbuf << 5 | epi << 7 | (step / 32) << 10 | (t0 / 16) << 13 | (t1 / 16) << 18;
+}
+static unsigned inst_key(const VsxGemmPlan& pl) {
+  return inst_key(pl.family == FAM_NT_GEN || pl.family == FAM_TN_GEN, pl.esize, pl.tile[0], pl.tile[1], pl.step, pl.nbuf, pl.pro_kind, pl.tr != 0, pl.epi);
 }
 
 static bool nt_fast_ok(const VsxGemm* p, int es) {
@@ -862,52 +846,6 @@ static bool nt_fast_ok(const VsxGemm* p, int es) {
   return true;
 }
 
-template <typename T>
-static int dispatch_nt_fast(const VsxGemm* p, hipStream_t s) {
-  const bool pro = p->pro == VSX_PRO_GRN;
-  switch (p->epi) {
-    case VSX_EPI_NONE: return pro ? launch_nt_fast<T, VSX_EPI_NONE, true>(p, s) : launch_nt_fast<T, VSX_EPI_NONE, false>(p, s);
-    case VSX_EPI_BIAS: return pro ? launch_nt_fast<T, VSX_EPI_BIAS, true>(p, s) : launch_nt_fast<T, VSX_EPI_BIAS, false>(p, s);
-    case VSX_EPI_BIAS_GELU_SQ: return pro ? launch_nt_fast<T, VSX_EPI_BIAS_GELU_SQ, true>(p, s) : launch_nt_fast<T, VSX_EPI_BIAS_GELU_SQ, false>(p, s);
-    case VSX_EPI_BIAS_RES: return pro ? launch_nt_fast<T, VSX_EPI_BIAS_RES, true>(p, s) : launch_nt_fast<T, VSX_EPI_BIAS_RES, false>(p, s);
-    default: return pro ? launch_nt_fast<T, VSX_EPI_DZ, true>(p, s) : launch_nt_fast<T, VSX_EPI_DZ, false>(p, s);
-  }
-}
-
-template <typename T, int BM, int BN, int WM_, int WN_, int BK, int NBUF = 2>
-static int launch_nt(const VsxGemm* p, hipStream_t s) {
-  g_vsx_last_kernel = "gemm_nt_generic";
-  int tiles = vsx_cdiv(p->M, BM) * vsx_cdiv(p->N, BN);
-  dim3 grid(tiles, 1, p->nz > 0 ? p->nz : 1);
-  hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, WM_, WN_, BK, NBUF>), grid, dim3(256), 0, s, *p);
-  VSX_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename T>
-static int dispatch_nt(const VsxGemm* p, hipStream_t s) {
-  if (p->b_bstride != 0) {
-    if (!nt_fast_ok(p, (int)sizeof(T))) {
-      vsx_set_error("vsx_gemm_nt: per-sample weights (b_bstride) need plain row operands, N > 64, K %% 32 == 0, hw %% 128 == 0");
-      return 1;
-    }
-    return dispatch_nt_fast<T>(p, s);
-  }
-  if (p->N > 64) {
-    // few workgroups (< 2 per CU) and a long K loop: the loop is bound by global-load latency, not by MFMA
-    // or bandwidth — stage 4x more K per barrier so 4x more bytes are in flight per workgroup
-    long tiles = (long)vsx_cdiv(p->M, 128) * vsx_cdiv(p->N, 128) * (p->nz > 0 ? p->nz : 1);
-    if constexpr (sizeof(T) == 2) {
-      if (tiles < 512 && p->K >= 256) return launch_nt<T, 128, 128, 2, 2, 128>(p, s);
-    }
-    if (nt_fast_ok(p, (int)sizeof(T))) return dispatch_nt_fast<T>(p, s);
-    return launch_nt<T, 128, 128, 2, 2, 32>(p, s);
-  }
-  if (p->N > 32) return launch_nt<T, 128, 64, 2, 2, 32>(p, s);
-  if (p->N > 16) return launch_nt<T, 128, 32, 4, 1, 32>(p, s);
-  return launch_nt<T, 128, 16, 4, 1, 32>(p, s);
-}
-
 static int check_common(const VsxGemm* p, int dtype, const char* who) {
   int vn = dtype == VSX_BF16 ? 8 : 4;
   VSX_CHECK(p != nullptr, "%s: null params", who);
@@ -929,7 +867,7 @@ static int check_common(const VsxGemm* p, int dtype, const char* who) {
   return 0;
 }
 
-extern "C" int32_t vsx_gemm_nt(const VsxGemm* p, int32_t dtype, vsx_stream_t stream) {
+static int plan_nt(const VsxGemm* p, int dtype, VsxGemmPlan& pl) {
   if (int e = check_common(p, dtype, "vsx_gemm_nt")) return e;
   int vn = dtype == VSX_BF16 ? 8 : 4;
   VSX_CHECK(p->ldc % vn == 0, "vsx_gemm_nt: ldc=%d must be a multiple of %d", p->ldc, vn);
@@ -947,9 +885,84 @@ extern "C" int32_t vsx_gemm_nt(const VsxGemm* p, int32_t dtype, vsx_stream_t str
     VSX_CHECK(dtype == VSX_BF16 && p->aux && p->grn_s && p->C && vsx_gemm_nt2_lnbwd_ok(p),
               "vsx_gemm_nt: EPI_LN_BWD needs bf16 row operands, aux = xh, grn_s = rstd, N <= 256, M %% 256 == 0, K %% 32 == 0 "
               "(query vsx_gemm_nt_ln_bwd_supported)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VSX_BF16 && vsx_gemm_nt2_ok(p)) return vsx_gemm_nt2(p, s);  // second-generation kernel (gemm_nt2.hip)
-  return dtype == VSX_BF16 ? dispatch_nt<bf16_t>(p, s) : dispatch_nt<float>(p, s);
+  pl = VsxGemmPlan{};
+  pl.esize = dtype == VSX_BF16 ? 2 : 4;
+  if (dtype == VSX_BF16 && vsx_gemm_nt2_ok(p)) {  // second-generation kernel (gemm_nt2.hip)
+    vsx_gemm_nt2_plan(p, pl);
+    return 0;
+  }
+  const int nz = p->nz > 0 ? p->nz : 1;
+  int bn = 128, bk = 32, nbuf = 2;
+  bool fast = false;
+  if (p->b_bstride != 0) {
+    VSX_CHECK(nt_fast_ok(p, pl.esize), "vsx_gemm_nt: per-sample weights (b_bstride) need plain row operands, N > 64, K %% 32 == 0, hw %% 128 == 0");
+    fast = true;
+  } else if (p->N > 64) {
+    // few workgroups (< 2 per CU) and a long K loop: the loop is bound by global-load latency, not by MFMA
+    // or bandwidth — stage 4x more K per barrier so 4x more bytes are in flight per workgroup
+    const long tiles = (long)vsx_cdiv(p->M, 128) * vsx_cdiv(p->N, 128) * nz;
+    if (pl.esize == 2 && tiles < 512 && p->K >= 256) bk = 128;
+    else fast = nt_fast_ok(p, pl.esize);
+  } else {
+    bn = p->N > 32 ? 64 : (p->N > 16 ? 32 : 16);
+  }
+  if (fast) {
+    pl.epi = p->epi >= VSX_EPI_NONE && p->epi <= VSX_EPI_BIAS_RES ? p->epi : VSX_EPI_DZ;
+    pl.pro_kind = p->pro == VSX_PRO_GRN;
+    pl.pro_bits = (g_vsx_nt_stream & 3) << 8;  // kernel-side flag bits 8 / 9 (the prologue kind itself is a template parameter there)
+    if (pl.esize == 2 && g_vsx_nt_wide) {
+      // short K (fc1, fc2 data gradient: epilogue-dominated): BK = 32 with ONE LDS buffer = 33.8 KB, 124 registers ->
+      // 4 workgroups per CU instead of 3 (measured -5..-10 % on these launches); long K: BK = 64, one or two buffers
+      const bool k64 = p->K % 64 == 0 && p->K >= 256 && (p->a_mode == VSX_A_ROWS || p->cs % 64 == 0);
+      bk = k64 && (g_vsx_nt_wide == 1 || g_vsx_nt_wide == 2) ? 64 : 32;
+      nbuf = k64 && g_vsx_nt_wide == 2 ? 2 : 1;
+    }
+  }
+  pl.family = fast ? FAM_NT_FAST : FAM_NT_GEN;
+  pl.tile[0] = 128; pl.tile[1] = bn; pl.step = bk; pl.nbuf = nbuf;
+  pl.grid[0] = vsx_cdiv(p->M, 128) * vsx_cdiv(p->N, bn); pl.grid[1] = 1; pl.grid[2] = nz;
+  pl.block = 256;
+  return 0;
+}
+
+static int run_nt(const VsxGemmPlan& pl, const VsxGemm* p, hipStream_t s) {
+  if (pl.family != FAM_NT_FAST && pl.family != FAM_NT_GEN) return vsx_gemm_nt2_run(pl, p, s);
+  VsxGemm q = *p;
+  q.pro |= pl.pro_bits;
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
+#define NT_GEN(T, BN, WM, WN, BK) \
+  case inst_key(true, sizeof(T), 128, BN, BK, 2, 0, false, 0): hipLaunchKernelGGL((gemm_nt_kernel<T, 128, BN, WM, WN, BK>), grid, block, 0, s, q); break;
+#define NT_FAST1(T, EPI, PRO, BK, NBUF) \
+  case inst_key(false, sizeof(T), 128, 128, BK, NBUF, PRO, false, EPI): hipLaunchKernelGGL((gemm_nt_fast_kernel<T, EPI, PRO, BK, NBUF>), grid, block, 0, s, q); break;
+#define NT_FAST2(T, EPI, BK, NBUF) NT_FAST1(T, EPI, false, BK, NBUF) NT_FAST1(T, EPI, true, BK, NBUF)
+#define NT_FAST(T, BK, NBUF) /* every epilogue of the lean kernel, without and with the GRN prologue */ \
+  NT_FAST2(T, VSX_EPI_NONE, BK, NBUF) NT_FAST2(T, VSX_EPI_BIAS, BK, NBUF) NT_FAST2(T, VSX_EPI_BIAS_GELU_SQ, BK, NBUF) \
+  NT_FAST2(T, VSX_EPI_BIAS_RES, BK, NBUF) NT_FAST2(T, VSX_EPI_DZ, BK, NBUF)
+  switch (inst_key(pl)) {
+    NT_GEN(bf16_t, 128, 2, 2, 128)
+    NT_GEN(bf16_t, 128, 2, 2, 32) NT_GEN(float, 128, 2, 2, 32)
+    NT_GEN(bf16_t, 64, 2, 2, 32) NT_GEN(float, 64, 2, 2, 32)
+    NT_GEN(bf16_t, 32, 4, 1, 32) NT_GEN(float, 32, 4, 1, 32)
+    NT_GEN(bf16_t, 16, 4, 1, 32) NT_GEN(float, 16, 4, 1, 32)
+    NT_FAST(bf16_t, 64, 1)
+    NT_FAST(bf16_t, 64, 2)
+    NT_FAST(bf16_t, 32, 1)
+    NT_FAST(bf16_t, 32, 2) NT_FAST(float, 32, 2)
+    default: vsx_set_error("vsx_gemm_nt: the plan names no instantiation"); return 1;
+  }
+#undef NT_GEN
+#undef NT_FAST1
+#undef NT_FAST2
+#undef NT_FAST
+  VSX_LAUNCH_CHECK();
+  g_vsx_last_kernel = pl.family;
+  return 0;
+}
+
+extern "C" int32_t vsx_gemm_nt(const VsxGemm* p, int32_t dtype, vsx_stream_t stream) {
+  VsxGemmPlan pl;
+  if (int e = plan_nt(p, dtype, pl)) return e;
+  return run_nt(pl, p, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t vsx_gemm_nt_ln_bwd_supported(int64_t M, int32_t N, int32_t K, int32_t dtype) {
@@ -1518,7 +1531,7 @@ __global__ __launch_bounds__(256, (BTK_ != 0 || PRO == 2) ? 2 : ((BMS == 64 && T
     }
   }
 
-  // per-sample mode (b_bstride != 0, set up by launch_tn): split `by` IS sample `by` (one contiguous step range per sample, one
+  // per-sample mode (b_bstride != 0, set up by plan_tn): split `by` IS sample `by` (one contiguous step range per sample, one
   // workgroup per (sample, tile)), its product goes to its own output matrix with plain stores
   const bool per_sample = p.b_bstride != 0;
   const bool ps_atomic = (p.pro & 4096) != 0;  // several splits per sample (few samples, large maps): atomics into zeroed outputs
@@ -1550,216 +1563,209 @@ __global__ __launch_bounds__(256) void tn_zero_kernel(float* __restrict__ p, lon
   else for (; i < n; ++i) p[i] = 0.f;
 }
 
+// How full the last round of `wgs` workgroups is when `per_cu` of them fit a CU (256 CUs).
+static double last_round_fill(long wgs, int per_cu) {
+  const long slots = 256 * per_cu, rounds = (wgs + slots - 1) / slots;
+  return (double)wgs / (double)(rounds * slots);
+}
+
 // Split count for a split-K launch of `tiles` output tiles whose workgroups fit `per_cu` to a CU: the count in [want * 2 / 3,
 // want * 4 / 3] whose tiles x splits fill their last round of 256 x per_cu workgroups best (round 5, tools/rounds.py: the
 // stage-3 weight gradients ran 1.12 rounds — the last eighth of their workgroups alone on the chip — stage 2's dW1 0.84).  A tie
 // goes to the count nearest `want`.  tn_fill = 0 switches it off.
 static int fill_splits(int tiles, int per_cu, int want, int max_splits) {
   if (!g_vsx_tn_fill) return want;
-  const int slots = 256 * per_cu;
   int lo = want * 2 / 3, hi = want * 4 / 3;
   lo = lo < 1 ? 1 : lo;
   hi = hi > max_splits ? max_splits : hi;
   int best = want < lo ? lo : (want > hi ? hi : want);
   double best_fill = -1.0;
   for (int sp = lo; sp <= hi; ++sp) {
-    const long wgs = (long)tiles * sp;
-    const long rounds = (wgs + slots - 1) / slots;
-    const double fill = (double)wgs / (double)(rounds * slots);
+    const double fill = last_round_fill((long)tiles * sp, per_cu);
     const int d = sp > want ? sp - want : want - sp, bd = best > want ? best - want : want - best;
     if (fill > best_fill + 1e-9 || (fill > best_fill - 1e-9 && d < bd)) { best_fill = fill; best = sp; }
   }
   return best;
 }
 
-template <typename T, int BT, bool TR>
-static int launch_tn(const VsxGemm* p, hipStream_t s) {
-  g_vsx_last_kernel = "gemm_tn_fast";  // (the generic kernel overrides this at its launch below)
-  int tiles = vsx_cdiv(p->N, BT) * vsx_cdiv(p->K, BT);
-  int nz = p->nz > 0 ? p->nz : 1;
+// The same for the splits of one sample (per-sample outputs), which are powers of two that divide its `steps` 64-row steps: of
+// ks, 2 ks, 4 ks (at most 64) the count that fills the last round best; a tie stays with the smaller count.
+static int fill_sample_splits(int tiles, int per_cu, int ks, int steps) {
+  if (!g_vsx_tn_fill) return ks;
+  int best = ks;
+  double best_fill = -1.0;
+  for (int sp = ks; sp <= 4 * ks && sp <= 64 && steps % sp == 0; sp *= 2) {
+    const double fill = last_round_fill((long)tiles * sp, per_cu);
+    if (fill > best_fill + 1e-9) { best_fill = fill; best = sp; }
+  }
+  return best;
+}
+
+static int plan_tn(const VsxGemm* p, int dtype, VsxGemmPlan& pl) {
+  if (int e = check_common(p, dtype, "vsx_gemm_tn")) return e;
+  VSX_CHECK(p->epi == VSX_EPI_NONE && p->c_mode == VSX_A_ROWS, "vsx_gemm_tn: no epilogue / scatter modes");
+  // 128x128 tiles (4x the MFMA work per barrier of a 64x64 tile) whenever the output is at least one such tile
+  // and there are enough pixel rows to split; 64x64 only for genuinely small weight matrices
+  const long t128 = (long)vsx_cdiv(p->N, 128) * vsx_cdiv(p->K, 128);
+  bool small = (p->N < 96 || p->K < 96) || (t128 < 24 && p->M < 65536);
+  if (p->b_bstride != 0) small = false;  // per-sample outputs live on the 128-wide lean instantiations
+  // GRN-prologue weight gradient + GRN backward statistics in one launch (kernel header, PRO == 2): the caller asks for it by
+  // passing the bf16 fc2 weight as `aux` ([N, ldx]) and the statistics target as `red0` ([M / hw, K], zeroed); whole samples per
+  // split, 64-row steps inside one sample.  (Without aux / red0 the prologue kernel is as fast: nothing to gain.)
+  const bool stats = p->pro == VSX_PRO_GRN && p->aux != nullptr && p->red0 != nullptr;
+  if (stats) {  // ... and so does the weight gradient with GRN statistics
+    VSX_CHECK(dtype == VSX_BF16 && g_vsx_tn_tr, "vsx_gemm_tn: the weight gradient with GRN statistics (aux = W2, red0 = P) is a bf16 kernel");
+    small = false;
+  }
+  const int es = dtype == VSX_BF16 ? 2 : 4, vn = 16 / es, BT = small ? 64 : 128, nz = p->nz > 0 ? p->nz : 1;
+  const bool TR = es == 2 && g_vsx_tn_tr, lean128 = TR && BT == 128;
+  const unsigned long long ld_bytes = (unsigned long long)(p->lda > p->ldb ? p->lda : p->ldb) * es;
+  const int stream_bits = (g_vsx_tn_stream & 3) << 13;
+  pl = VsxGemmPlan{};
+  pl.family = FAM_TN_FAST;
+  pl.esize = es; pl.tr = TR; pl.tile[0] = pl.tile[1] = BT; pl.step = 32; pl.nbuf = 2; pl.block = 256;
+  const int tiles = vsx_cdiv(p->N, BT) * vsx_cdiv(p->K, BT);
   // split the pixel (contraction) axis so that the launch fills 256 CUs, but keep the number of
   // same-address atomics (= splits) small: they serialise at ~0.2 us each
-  int want = vsx_cdiv(g_vsx_tn_want, tiles * nz);
-  int max_splits = vsx_cdiv(p->M, 256);
+  const int want = vsx_cdiv(g_vsx_tn_want, tiles * nz), max_splits = vsx_cdiv(p->M, 256);
   int splits = want < 1 ? 1 : (want > max_splits ? max_splits : want);
   // few tiles (skinny weight matrices, e.g. the head's 8x32): the atomics spread over few addresses anyway,
   // parallelism matters more
-  int cap = tiles * nz <= 4 ? 384 : (tiles * nz <= 24 ? 96 : 48);
+  const int cap = tiles * nz <= 4 ? 384 : (tiles * nz <= 24 ? 96 : 48);
   if (splits > cap) splits = cap;
-  int rpb = 0;
   if (splits > vsx_cdiv(p->M, 32)) splits = vsx_cdiv(p->M, 32);
   if (splits >= 8) splits &= ~7;  // multiple of 8: the kernel maps whole splits onto XCDs
+  pl.grid[0] = tiles; pl.grid[1] = splits; pl.grid[2] = nz;
   if (p->b_bstride != 0) {
     // one product PER SAMPLE: C[b] (b_bstride elements apart) = X_b^T . Y_b over the hw rows of sample b, colsum[b][N] likewise
     // (plain stores: the caller need not zero the outputs).  Used by the block backward: the per-sample products dout_b^T g_b
     // give the fc2 weight gradient AND the GRN statistics P, S without ever forming dz (vsx_grn_q_reduce).
-    if constexpr (sizeof(T) == 2 && BT == 128 && TR) {
-      VSX_CHECK((g_vsx_nt_fast & 1) && p->a_mode == VSX_A_ROWS && p->pro == VSX_PRO_NONE && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 &&
-                    nz == 1 && (unsigned long long)64 * (p->lda > p->ldb ? p->lda : p->ldb) * sizeof(T) < (1ull << 31),
-                "vsx_gemm_tn: per-sample outputs (b_bstride) need plain bf16 row operands, no prologue, hw %% 64 == 0");
-      VsxGemm pq = *p;
-      pq.pro |= 1024;  // contiguous step range per split: a whole sample, or 1 / ks of one
-      pq.pro |= (g_vsx_tn_stream & 3) << 13;
-      const int nb = p->M / p->hw;
-      // N = 192 too since round 4: a quarter of the 256-wide tile idles, but the 4C-wide operand is read once instead of twice and,
-      // with its loads non-temporal (tn_stream), the launch is 4 % faster than on 128 x 128 tiles (328 -> 315 us at B = 512)
-      const bool n_full = p->N >= 192 && p->N <= 256 && p->K >= 128;
-      const int t2 = n_full ? vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, 128) : tiles;
-      // few samples with large maps (the 2048^2 gate shape: 8 samples of 262 144 rows): ks splits per sample so that the launch
-      // still fills the chip; their partial products meet in zero-filled outputs through atomics (<= ks adds per address)
-      int ks = 1;
-      const int spp = p->hw / 64;  // 64-row steps per sample
-      while ((long)nb * ks * t2 < 768 && ks < 64 && spp % (2 * ks) == 0) ks *= 2;
-      if (g_vsx_tn_fill && ks > 1) {
-        // ... and of the power-of-two counts from there up to 4 x, the one that fills its last round of workgroups best (2 per CU for
-        // the 256-wide tiles, 3 for the square ones): 8 samples x 36 tiles x 4 ran 1.5 rounds at the gate shape's C = 384 blocks
-        const int slots = 256 * (n_full ? 2 : 3);
-        int best = ks;
-        double bf = -1.0;
-        for (int k2 = ks; k2 <= 4 * ks && k2 <= 64 && spp % k2 == 0; k2 *= 2) {
-          const long wgs = (long)nb * k2 * t2, rounds = (wgs + slots - 1) / slots;
-          const double f = (double)wgs / (double)(rounds * slots);
-          if (f > bf + 1e-9) { bf = f; best = k2; }
-        }
-        ks = best;
-      }
-      if (ks > 1) {
-        pq.pro |= 4096;
-        const long nq = (long)nb * p->b_bstride, nc = p->colsum ? (long)nb * p->N : 0;
-        hipLaunchKernelGGL(tn_zero_kernel, dim3(vsx_cdiv(nq, 1024L)), dim3(256), 0, s, reinterpret_cast<float*>(p->C) + p->c_coff[0], nq);
-        if (nc) hipLaunchKernelGGL(tn_zero_kernel, dim3(vsx_cdiv(nc, 1024L)), dim3(256), 0, s, p->colsum, nc);
-      }
-      if (n_full) {
-        dim3 g2(t2, nb * ks, 1);
-        hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, false, 64, 1, 128>), g2, dim3(256), 0, s, pq);
-      } else {
-        dim3 g2(tiles, nb * ks, 1);
-        hipLaunchKernelGGL((gemm_tn_fast_kernel<T, BT, TR, false, 64, 1>), g2, dim3(256), 0, s, pq);
-      }
-      VSX_LAUNCH_CHECK();
-      return 0;
-    } else {
-      vsx_set_error("vsx_gemm_tn: per-sample outputs (b_bstride) exist for bf16 operands with outputs of at least 96 x 96 only");
-      return 1;
+    VSX_CHECK(lean128, "vsx_gemm_tn: per-sample outputs (b_bstride) exist for bf16 operands with outputs of at least 96 x 96 only");
+    VSX_CHECK((g_vsx_nt_fast & 1) && p->a_mode == VSX_A_ROWS && p->pro == VSX_PRO_NONE && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 &&
+                  nz == 1 && 64 * ld_bytes < (1ull << 31),
+              "vsx_gemm_tn: per-sample outputs (b_bstride) need plain bf16 row operands, no prologue, hw %% 64 == 0");
+    const int nb = p->M / p->hw;
+    // N = 192 too since round 4: a quarter of the 256-wide tile idles, but the 4C-wide operand is read once instead of twice and,
+    // with its loads non-temporal (tn_stream), the launch is 4 % faster than on 128 x 128 tiles (328 -> 315 us at B = 512)
+    const bool n_full = p->N >= 192 && p->N <= 256 && p->K >= 128;
+    const int t2 = n_full ? vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, 128) : tiles;
+    // few samples with large maps (the 2048^2 gate shape: 8 samples of 262 144 rows): ks splits per sample so that the launch
+    // still fills the chip; their partial products meet in zero-filled outputs through atomics (<= ks adds per address) ...
+    int ks = 1;
+    const int spp = p->hw / 64;  // 64-row steps per sample
+    while ((long)nb * ks * t2 < 768 && ks < 64 && spp % (2 * ks) == 0) ks *= 2;
+    // ... and of the power-of-two counts from there up to 4 x, the one that fills its last round of workgroups best (2 per CU for
+    // the 256-wide tiles, 3 for the square ones): 8 samples x 36 tiles x 4 ran 1.5 rounds at the gate shape's C = 384 blocks
+    if (ks > 1) ks = fill_sample_splits(nb * t2, n_full ? 2 : 3, ks, spp);
+    pl.pro_bits = 1024 | stream_bits;  // contiguous step range per split: a whole sample, or 1 / ks of one
+    if (ks > 1) {
+      pl.pro_bits |= 4096;
+      pl.zero_c = (long)nb * p->b_bstride;
+      pl.zero_colsum = p->colsum ? (long)nb * p->N : 0;
     }
-  }
-  if constexpr (sizeof(T) == 2 && BT == 128 && TR) {
-    // GRN-prologue weight gradient + GRN backward statistics in one launch (kernel header, PRO == 2): the caller asks for it by
-    // passing the bf16 fc2 weight as `aux` ([N, ldx]) and the statistics target as `red0` ([M / hw, K], zeroed); whole samples per
-    // split, 64-row steps inside one sample.  (Without aux / red0 the prologue kernel below is as fast: nothing to gain.)
-    if (p->pro == VSX_PRO_GRN && p->aux != nullptr && p->red0 != nullptr) {
-      VSX_CHECK((g_vsx_nt_fast & 1) && p->a_mode == VSX_A_ROWS && nz == 1 && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 && p->N >= 96 &&
-                    p->K >= 128 && p->N % 8 == 0 && p->K % 8 == 0 && p->ldx >= p->K &&
-                    (unsigned long long)64 * (p->lda > p->ldb ? p->lda : p->ldb) * sizeof(T) < (1ull << 31),
-                "vsx_gemm_tn: the weight gradient with GRN statistics (aux = W2, red0 = P) needs plain bf16 row operands, hw %% 64 == 0, N >= 96, K >= 128");
-      const int nb = p->M / p->hw;
-      // two workgroups per CU (68 KB of LDS each): the split count that fills `tn_p2_rounds` rounds of 512 workgroups as evenly as
-      // whole tiles allow (36 tiles at C = 384: 28 splits = 1008 workgroups; the power-of-two split of the first version ran 2.25
-      // rounds).  tn_p2_rounds = 0: that first version (the largest divisor of the batch below 2 * tn_want / tiles).
-      int sp = 1;
-      if (g_vsx_tn_p2_rounds > 0) {
-        sp = (g_vsx_tn_p2_rounds * 512) / tiles;
-      } else {
-        const int wantp = vsx_cdiv(g_vsx_tn_want * 2, tiles);
-        for (int d = wantp < nb ? wantp : nb; d >= 1; --d)
-          if (nb % d == 0) { sp = d; break; }
-      }
-      sp = sp < 1 ? 1 : (sp > nb ? nb : sp);
-      VsxGemm pq = *p;
-      pq.pro = 1024 | ((g_vsx_tn_stream & 3) << 13);
-      dim3 g2(tiles, sp, 1);
-      g_vsx_last_kernel = "gemm_tn_fast";
-      hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 128, TR, 2, 64, 1>), g2, dim3(256), 0, s, pq);
-      VSX_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  dim3 grid(tiles, splits, nz);
-  const bool patch_ok = (g_vsx_nt_fast & 2) && p->a_mode == VSX_A_PATCH2 && p->pro == VSX_PRO_NONE && p->gw > 0 && (32 % p->gw == 0 || p->gw % 64 == 0) &&
-                        p->cs % VT<T>::N == 0 && (unsigned long long)(512 + 4 * p->gw) * p->lda * sizeof(T) < (1ull << 31);
-  const bool fast = (g_vsx_nt_fast & 1) && (p->a_mode == VSX_A_ROWS || patch_ok) && p->M % 32 == 0 && p->N >= VT<T>::N && p->K >= VT<T>::N &&
-                    (p->pro == VSX_PRO_NONE || (p->pro == VSX_PRO_GRN && p->hw > 0 && p->hw % 32 == 0)) &&
-                    (unsigned long long)32 * (p->lda > p->ldb ? p->lda : p->ldb) * sizeof(T) < (1ull << 31);
-  if (fast) {
-    VsxGemm pq = *p;
-    if (g_vsx_tn_contig) pq.pro |= 1024;  // kernel-side flag bit (the prologue kind is a template parameter there)
-    pq.pro |= (g_vsx_tn_stream & 3) << 13;
-    if constexpr (sizeof(T) == 2 && BT == 128) {
-      if (g_vsx_tn_wide && p->M % 64 == 0 && (p->pro == VSX_PRO_NONE || p->hw % 64 == 0) && p->M / 64 >= 2 * splits) {
-        if (g_vsx_tn_fill && TR) {  // 128 x 128 tiles, 64-row steps, one LDS buffer: 160 - 168 registers, three workgroups per CU
-          int spf = fill_splits(tiles * nz, 3, splits, p->M / 128);
-          if (spf > cap) spf = cap;
-          grid.y = splits = spf < 1 ? 1 : spf;
-        }
-        if constexpr (TR) {
-          // rectangular tiles when one side of the weight gradient fits a single 256-wide tile (see the kernel's header)
-          // measured (tools/perf_nt.py, B = 512): C = 224 -9 % (dW1) / -14 % (dW2); C = 192 +4..8 % (a quarter of the
-          // 256-wide tile idles) -> only when the tile is >= 7/8 full
-          // bit 1: 256x128 tiles also when 256 divides N exactly and there is no prologue (dW1 of the C = 192 / 384 / 768
-          // stages: -5..-11 % on those launches)
-          const bool n_div = (g_vsx_tn_rect & 2) && p->N % 256 == 0 && p->K >= 128 && p->pro == VSX_PRO_NONE;
-          const bool n_full = ((g_vsx_tn_rect & 1) && p->N >= 224 && p->N <= 256 && p->K >= 256) || n_div;
-          const bool k_full = (g_vsx_tn_rect & 1) && !n_full && p->K >= 224 && p->K <= 256 && p->N >= 256;
-          if (n_full || k_full) {
-            const int t2 = n_full ? vsx_cdiv(p->N, 256) * vsx_cdiv(p->K, 128) : vsx_cdiv(p->N, 128) * vsx_cdiv(p->K, 256);
-            int want2 = vsx_cdiv(g_vsx_tn_want2, t2 * nz), sp2 = want2 < 1 ? 1 : (want2 > max_splits ? max_splits : want2);
-            if (sp2 > p->M / 128) sp2 = p->M / 128;
-            if (g_vsx_tn_fill) sp2 = fill_splits(t2 * nz, 2, sp2, p->M / 128);  // 256 registers: two workgroups per CU
-            else if (sp2 >= 8) sp2 &= ~7;
-            if (sp2 < 1) sp2 = 1;
-            dim3 g2(t2, sp2, nz);
-            if (n_full) {
-              if (p->pro == VSX_PRO_GRN)
-                hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, true, 64, 1, 128>), g2, dim3(256), 0, s, pq);
-              else
-                hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 256, TR, false, 64, 1, 128>), g2, dim3(256), 0, s, pq);
-            } else {
-              if (p->pro == VSX_PRO_GRN)
-                hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 128, TR, true, 64, 1, 256>), g2, dim3(256), 0, s, pq);
-              else
-                hipLaunchKernelGGL((gemm_tn_fast_kernel<T, 128, TR, false, 64, 1, 256>), g2, dim3(256), 0, s, pq);
-            }
-            VSX_LAUNCH_CHECK();
-            return 0;
-          }
-        }
-        if (p->pro == VSX_PRO_GRN)
-          hipLaunchKernelGGL((gemm_tn_fast_kernel<T, BT, TR, true, 64, 1>), grid, dim3(256), 0, s, pq);
-        else
-          hipLaunchKernelGGL((gemm_tn_fast_kernel<T, BT, TR, false, 64, 1>), grid, dim3(256), 0, s, pq);
-        VSX_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    if (p->pro == VSX_PRO_GRN)
-      hipLaunchKernelGGL((gemm_tn_fast_kernel<T, BT, TR, true>), grid, dim3(256), 0, s, pq);
-    else
-      hipLaunchKernelGGL((gemm_tn_fast_kernel<T, BT, TR, false>), grid, dim3(256), 0, s, pq);
-    VSX_LAUNCH_CHECK();
+    if (n_full) { pl.tile[0] = 256; pl.tile[1] = 128; }
+    pl.step = 64; pl.nbuf = 1;
+    pl.grid[0] = t2; pl.grid[1] = nb * ks;
     return 0;
   }
-  g_vsx_last_kernel = "gemm_tn_generic";
-  hipLaunchKernelGGL((gemm_tn_kernel<T, BT, TR>), grid, dim3(256), 0, s, *p, rpb);
+  if (stats) {
+    VSX_CHECK((g_vsx_nt_fast & 1) && p->a_mode == VSX_A_ROWS && nz == 1 && p->hw > 0 && p->hw % 64 == 0 && p->M % p->hw == 0 && p->N >= 96 &&
+                  p->K >= 128 && p->N % 8 == 0 && p->K % 8 == 0 && p->ldx >= p->K && 64 * ld_bytes < (1ull << 31),
+              "vsx_gemm_tn: the weight gradient with GRN statistics (aux = W2, red0 = P) needs plain bf16 row operands, hw %% 64 == 0, N >= 96, K >= 128");
+    const int nb = p->M / p->hw;
+    // two workgroups per CU (68 KB of LDS each): the split count that fills `tn_p2_rounds` rounds of 512 workgroups as evenly as
+    // whole tiles allow (36 tiles at C = 384: 28 splits = 1008 workgroups; the power-of-two split of the first version ran 2.25
+    // rounds).  tn_p2_rounds = 0: that first version (the largest divisor of the batch below 2 * tn_want / tiles).
+    int sp = 1;
+    if (g_vsx_tn_p2_rounds > 0) {
+      sp = (g_vsx_tn_p2_rounds * 512) / tiles;
+    } else {
+      const int wantp = vsx_cdiv(g_vsx_tn_want * 2, tiles);
+      for (int d = wantp < nb ? wantp : nb; d >= 1; --d)
+        if (nb % d == 0) { sp = d; break; }
+    }
+    pl.pro_kind = 2; pl.step = 64; pl.nbuf = 1;
+    pl.pro_bits = 1024 | stream_bits;
+    pl.grid[1] = sp < 1 ? 1 : (sp > nb ? nb : sp);
+    return 0;
+  }
+  const bool patch_ok = (g_vsx_nt_fast & 2) && p->a_mode == VSX_A_PATCH2 && p->pro == VSX_PRO_NONE && p->gw > 0 && (32 % p->gw == 0 || p->gw % 64 == 0) &&
+                        p->cs % vn == 0 && (unsigned long long)(512 + 4 * p->gw) * p->lda * es < (1ull << 31);
+  const bool fast = (g_vsx_nt_fast & 1) && (p->a_mode == VSX_A_ROWS || patch_ok) && p->M % 32 == 0 && p->N >= vn && p->K >= vn &&
+                    (p->pro == VSX_PRO_NONE || (p->pro == VSX_PRO_GRN && p->hw > 0 && p->hw % 32 == 0)) && 32 * ld_bytes < (1ull << 31);
+  if (!fast) {
+    pl.family = FAM_TN_GEN;
+    pl.step = pl.nbuf = 0;
+    return 0;
+  }
+  pl.pro_kind = p->pro == VSX_PRO_GRN;
+  pl.pro_bits = (g_vsx_tn_contig ? 1024 : 0) | stream_bits;  // kernel-side flag bits (the prologue kind is a template parameter there)
+  if (!(es == 2 && BT == 128 && g_vsx_tn_wide && p->M % 64 == 0 && (p->pro == VSX_PRO_NONE || p->hw % 64 == 0) && p->M / 64 >= 2 * splits))
+    return 0;
+  pl.step = 64; pl.nbuf = 1;
+  if (!TR) return 0;
+  if (g_vsx_tn_fill) {  // 128 x 128 tiles, 64-row steps, one LDS buffer: 160 - 168 registers, three workgroups per CU
+    int spf = fill_splits(tiles * nz, 3, splits, p->M / 128);
+    if (spf > cap) spf = cap;
+    pl.grid[1] = spf < 1 ? 1 : spf;
+  }
+  // rectangular tiles when one side of the weight gradient fits a single 256-wide tile (see the kernel's header)
+  // measured (tools/perf_nt.py, B = 512): C = 224 -9 % (dW1) / -14 % (dW2); C = 192 +4..8 % (a quarter of the
+  // 256-wide tile idles) -> only when the tile is >= 7/8 full
+  // bit 1: 256x128 tiles also when 256 divides N exactly and there is no prologue (dW1 of the C = 192 / 384 / 768
+  // stages: -5..-11 % on those launches)
+  const bool n_div = (g_vsx_tn_rect & 2) && p->N % 256 == 0 && p->K >= 128 && p->pro == VSX_PRO_NONE;
+  const bool n_full = ((g_vsx_tn_rect & 1) && p->N >= 224 && p->N <= 256 && p->K >= 256) || n_div;
+  const bool k_full = (g_vsx_tn_rect & 1) && !n_full && p->K >= 224 && p->K <= 256 && p->N >= 256;
+  if (!n_full && !k_full) return 0;
+  pl.tile[0] = n_full ? 256 : 128; pl.tile[1] = n_full ? 128 : 256;
+  const int t2 = vsx_cdiv(p->N, pl.tile[0]) * vsx_cdiv(p->K, pl.tile[1]);
+  const int want2 = vsx_cdiv(g_vsx_tn_want2, t2 * nz);
+  int sp2 = want2 < 1 ? 1 : (want2 > max_splits ? max_splits : want2);
+  if (sp2 > p->M / 128) sp2 = p->M / 128;
+  if (g_vsx_tn_fill) sp2 = fill_splits(t2 * nz, 2, sp2, p->M / 128);  // 256 registers: two workgroups per CU
+  else if (sp2 >= 8) sp2 &= ~7;
+  pl.grid[0] = t2; pl.grid[1] = sp2 < 1 ? 1 : sp2;
+  return 0;
+}
+
+static int run_tn(const VsxGemmPlan& pl, const VsxGemm* p, hipStream_t s) {
+  VsxGemm q = *p;
+  q.pro = (pl.pro_kind == 2 ? 0 : q.pro) | pl.pro_bits;  // (the statistics kernel has always been handed the bits alone)
+  if (pl.zero_c) hipLaunchKernelGGL(tn_zero_kernel, dim3(vsx_cdiv(pl.zero_c, 1024L)), dim3(256), 0, s, reinterpret_cast<float*>(p->C) + p->c_coff[0], (long)pl.zero_c);
+  if (pl.zero_colsum) hipLaunchKernelGGL(tn_zero_kernel, dim3(vsx_cdiv(pl.zero_colsum, 1024L)), dim3(256), 0, s, p->colsum, (long)pl.zero_colsum);
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
+#define TN_GEN(T, BT, TR) \
+  case inst_key(true, sizeof(T), BT, BT, 0, 0, 0, TR, 0): hipLaunchKernelGGL((gemm_tn_kernel<T, BT, TR>), grid, block, 0, s, q, 0); break;
+#define TN_FAST1(T, BT, TR, PRO, BMS, NBUF, BTK) \
+  case inst_key(false, sizeof(T), BT, BTK ? BTK : BT, BMS, NBUF, PRO, TR, 0): hipLaunchKernelGGL((gemm_tn_fast_kernel<T, BT, TR, PRO, BMS, NBUF, BTK>), grid, block, 0, s, q); break;
+#define TN_FAST(T, BT, TR, BMS, NBUF, BTK) /* without and with the GRN prologue */ TN_FAST1(T, BT, TR, 0, BMS, NBUF, BTK) TN_FAST1(T, BT, TR, 1, BMS, NBUF, BTK)
+  switch (inst_key(pl)) {
+    TN_GEN(bf16_t, 64, true) TN_GEN(bf16_t, 128, true) TN_GEN(bf16_t, 64, false) TN_GEN(bf16_t, 128, false) TN_GEN(float, 64, false) TN_GEN(float, 128, false)
+    TN_FAST(bf16_t, 64, true, 32, 2, 0) TN_FAST(bf16_t, 128, true, 32, 2, 0)      // 32-row steps, two LDS buffers
+    TN_FAST(bf16_t, 64, false, 32, 2, 0) TN_FAST(bf16_t, 128, false, 32, 2, 0)
+    TN_FAST(float, 64, false, 32, 2, 0) TN_FAST(float, 128, false, 32, 2, 0)
+    TN_FAST(bf16_t, 128, true, 64, 1, 0) TN_FAST(bf16_t, 128, false, 64, 1, 0)    // tn_wide: 64-row steps, one buffer
+    TN_FAST(bf16_t, 256, true, 64, 1, 128)                                         // tn_rect: 256 x 128 ...
+    TN_FAST(bf16_t, 128, true, 64, 1, 256)                                         // ... and 128 x 256 tiles
+    TN_FAST1(bf16_t, 128, true, 2, 64, 1, 0)                                       // with the GRN statistics
+    default: vsx_set_error("vsx_gemm_tn: the plan names no instantiation"); return 1;
+  }
+#undef TN_GEN
+#undef TN_FAST1
+#undef TN_FAST
   VSX_LAUNCH_CHECK();
+  g_vsx_last_kernel = pl.family;
   return 0;
 }
 
 extern "C" int32_t vsx_gemm_tn(const VsxGemm* p, int32_t dtype, vsx_stream_t stream) {
-  if (int e = check_common(p, dtype, "vsx_gemm_tn")) return e;
-  VSX_CHECK(p->epi == VSX_EPI_NONE && p->c_mode == VSX_A_ROWS, "vsx_gemm_tn: no epilogue / scatter modes");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // 128x128 tiles (4x the MFMA work per barrier of a 64x64 tile) whenever the output is at least one such tile
-  // and there are enough pixel rows to split; 64x64 only for genuinely small weight matrices
-  long t128 = (long)vsx_cdiv(p->N, 128) * vsx_cdiv(p->K, 128);
-  bool small = (p->N < 96 || p->K < 96) || (t128 < 24 && p->M < 65536);
-  if (p->b_bstride != 0) small = false;  // per-sample outputs live on the 128-wide lean instantiations
-  if (p->pro == VSX_PRO_GRN && p->aux != nullptr && p->red0 != nullptr) {  // ... and so does the weight gradient with GRN statistics
-    VSX_CHECK(dtype == VSX_BF16 && g_vsx_tn_tr, "vsx_gemm_tn: the weight gradient with GRN statistics (aux = W2, red0 = P) is a bf16 kernel");
-    small = false;
-  }
-  if (dtype == VSX_BF16) {
-    if (g_vsx_tn_tr) return small ? launch_tn<bf16_t, 64, true>(p, s) : launch_tn<bf16_t, 128, true>(p, s);
-    return small ? launch_tn<bf16_t, 64, false>(p, s) : launch_tn<bf16_t, 128, false>(p, s);
-  }
-  return small ? launch_tn<float, 64, false>(p, s) : launch_tn<float, 128, false>(p, s);
+  VsxGemmPlan pl;
+  if (int e = plan_tn(p, dtype, pl)) return e;
+  return run_tn(pl, p, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t vsx_gemm_plan(int32_t kind, const VsxGemm* p, int32_t dtype, VsxGemmPlan* out) {
+  VSX_CHECK(out != nullptr && (kind == VSX_GEMM_NT || kind == VSX_GEMM_TN), "vsx_gemm_plan: kind %d, out %p", kind, (void*)out);
+  return kind == VSX_GEMM_NT ? plan_nt(p, dtype, *out) : plan_tn(p, dtype, *out);
 }

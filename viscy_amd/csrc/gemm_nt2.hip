@@ -590,21 +590,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt2_lnbwd_kernel(const VsxGemm p)
   NT2_STAMP(5);
 }
 
-template <int EPI, int BN>
-int launch_bn(const VsxGemm* p, hipStream_t s) {
-  const int tiles = (p->M / BM) * vsx_cdiv(p->N, BN);
-  if constexpr (EPI == VSX_EPI_BIAS_RES || EPI == VSX_EPI_NONE) {
-    if (p->pro == VSX_PRO_GRN) {
-      hipLaunchKernelGGL((gemm_nt2_kernel<EPI, BN, true>), dim3(tiles), dim3(512), 0, s, *p);
-      VSX_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  hipLaunchKernelGGL((gemm_nt2_kernel<EPI, BN>), dim3(tiles), dim3(512), 0, s, *p);
-  VSX_LAUNCH_CHECK();
-  return 0;
-}
-
 // column-tile width: the one that moves the fewest operand bytes per 256 rows and K step — tiles x (256 + BN) — among
 // those that idle at most a third of their MFMA work on columns past N
 int pick_bn(int N) {
@@ -617,15 +602,6 @@ int pick_bn(int N) {
     if (cost < best_cost) { best_cost = cost; best = bn; }
   }
   return best;
-}
-
-template <int EPI>
-int launch(const VsxGemm* p, hipStream_t s) {
-  switch (pick_bn(p->N)) {
-    case 384: return launch_bn<EPI, 384>(p, s);
-    case 256: return launch_bn<EPI, 256>(p, s);
-    default: return launch_bn<EPI, 128>(p, s);
-  }
 }
 
 }  // namespace
@@ -669,36 +645,48 @@ bool vsx_gemm_nt2_ok(const VsxGemm* p) {
   return p->K >= 768 && (p->N > 192 || ((g_vsx_nt2 & 16) && p->N == 192));  // bit 4 (round 6, A/B): the C = 192 fc2 forward too
 }
 
-int vsx_gemm_nt2(const VsxGemm* p0, hipStream_t s) {
-  g_vsx_last_kernel = "gemm_nt2";
-  VsxGemm det = *p0;
-  const VsxGemm* p = p0;
-  const bool det_sums = g_vsx_det_reduce && p0->epi == VSX_EPI_BIAS_GELU_SQ && p0->hw > 0 && p0->hw % BM == 0 && p0->hw > BM;
-  if (det_sums) {  // (hw <= 256: at most two adds per address — already independent of their order)
-    const long need = (long)(p0->M / BM) * p0->N;
-    VSX_CHECK(g_vsx_det_ws != nullptr && g_vsx_det_ws_floats >= need, "vsx_gemm_nt: det_reduce needs vsx_det_workspace(>= %ld floats)", need);
-    det.aux = g_vsx_det_ws;
-    p = &det;
+// The plan of a launch that vsx_gemm_nt2_ok has accepted (gemm.hip: plan_nt).
+void vsx_gemm_nt2_plan(const VsxGemm* p, VsxGemmPlan& pl) {
+  const bool lnbwd = p->epi == VSX_EPI_LN_BWD;
+  const int bn = lnbwd ? (p->N <= 128 ? 128 : 256) : pick_bn(p->N);
+  pl.family = "gemm_nt2";
+  pl.tile[0] = BM; pl.tile[1] = bn; pl.step = BK; pl.nbuf = NST;
+  pl.epi = p->epi;
+  pl.pro_kind = p->pro == VSX_PRO_GRN;
+  pl.grid[0] = (p->M / BM) * (lnbwd ? 1 : vsx_cdiv(p->N, bn)); pl.grid[1] = pl.grid[2] = 1;
+  pl.block = 512;
+  // det_reduce: per-tile column sums to a workspace, added in a fixed order afterwards (hw <= 256: at most two adds per
+  // address — already independent of their order)
+  if (g_vsx_det_reduce && p->epi == VSX_EPI_BIAS_GELU_SQ && p->hw > 0 && p->hw % BM == 0 && p->hw > BM) pl.det_floats = (long)(p->M / BM) * p->N;
+}
+
+int vsx_gemm_nt2_run(const VsxGemmPlan& pl, const VsxGemm* p, hipStream_t s) {
+  VsxGemm q = *p;
+  if (pl.det_floats) {  // checked here, not in the plan: the workspace belongs to the calling thread
+    VSX_CHECK(g_vsx_det_ws != nullptr && g_vsx_det_ws_floats >= pl.det_floats, "vsx_gemm_nt: det_reduce needs vsx_det_workspace(>= %ld floats)", (long)pl.det_floats);
+    q.aux = g_vsx_det_ws;
   }
-  if (det_sums) {
-    int e = launch<VSX_EPI_BIAS_GELU_SQ>(p, s);
-    if (e) return e;
-    return vsx_det_group_sum(g_vsx_det_ws, p->N, 0, p->red0, p->M / p->hw, p->hw / BM, p->N, s);
+  const dim3 grid(pl.grid[0]), block(pl.block);
+#define NT2(EPI, BN, PRO) case (EPI) << 12 | (BN) << 1 | (PRO): hipLaunchKernelGGL((gemm_nt2_kernel<EPI, BN, PRO>), grid, block, 0, s, q); break;
+#define NT2_BN(BN) /* the five epilogues; the GRN prologue exists for the two of the fc2 forward */ \
+  NT2(VSX_EPI_NONE, BN, false) NT2(VSX_EPI_BIAS, BN, false) NT2(VSX_EPI_BIAS_GELU_SQ, BN, false) NT2(VSX_EPI_BIAS_RES, BN, false) \
+  NT2(VSX_EPI_DZ, BN, false) NT2(VSX_EPI_NONE, BN, true) NT2(VSX_EPI_BIAS_RES, BN, true)
+#define NT2_LNBWD(BN) case VSX_EPI_LN_BWD << 12 | (BN) << 1: hipLaunchKernelGGL((gemm_nt2_lnbwd_kernel<BN>), grid, block, 0, s, q); break;
+  switch (pl.epi << 12 | pl.tile[1] << 1 | pl.pro_kind) {
+    NT2_BN(128)
+    NT2_BN(256)
+    NT2_BN(384)
+    NT2_LNBWD(128)
+    NT2_LNBWD(256)
+    default: vsx_set_error("vsx_gemm_nt: the plan names no gemm_nt2 instantiation"); return 1;
   }
-  if (p->epi == VSX_EPI_LN_BWD) {
-    const int tiles = p->M / BM;
-    if (p->N <= 128) hipLaunchKernelGGL((gemm_nt2_lnbwd_kernel<128>), dim3(tiles), dim3(512), 0, s, *p);
-    else hipLaunchKernelGGL((gemm_nt2_lnbwd_kernel<256>), dim3(tiles), dim3(512), 0, s, *p);
-    VSX_LAUNCH_CHECK();
-    return 0;
-  }
-  switch (p->epi) {
-    case VSX_EPI_NONE: return launch<VSX_EPI_NONE>(p, s);
-    case VSX_EPI_BIAS: return launch<VSX_EPI_BIAS>(p, s);
-    case VSX_EPI_BIAS_GELU_SQ: return launch<VSX_EPI_BIAS_GELU_SQ>(p, s);
-    case VSX_EPI_BIAS_RES: return launch<VSX_EPI_BIAS_RES>(p, s);
-    default: return launch<VSX_EPI_DZ>(p, s);
-  }
+#undef NT2
+#undef NT2_BN
+#undef NT2_LNBWD
+  VSX_LAUNCH_CHECK();
+  g_vsx_last_kernel = pl.family;
+  if (pl.det_floats) return vsx_det_group_sum(g_vsx_det_ws, p->N, 0, p->red0, p->M / p->hw, p->hw / BM, p->N, s);
+  return 0;
 }
 
 #ifdef NT2_TS

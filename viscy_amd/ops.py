@@ -15,7 +15,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from ._lib import VsxGemm, check, dtype_code, lib, ptr, stream
+from ._lib import VsxGemm, VsxGemmPlan, check, dtype_code, lib, ptr, stream
 
 
 _WS: dict = {}
@@ -89,8 +89,10 @@ def gemm(
     C2: Tensor | None = None,
     b_bstride: int = 0,
     rscale: Tensor | None = None,
+    plan: VsxGemmPlan | None = None,
 ) -> None:
-    """kind='nt': C[M,N] = pro(A)[M,K]·B[N,K]^T (+epilogue);  kind='tn': C[N,K](fp32) += B[M,N]^T·pro(A)[M,K]."""
+    """kind='nt': C[M,N] = pro(A)[M,K]·B[N,K]^T (+epilogue);  kind='tn': C[N,K](fp32) += B[M,N]^T·pro(A)[M,K].
+    With ``plan``: nothing is launched; ``plan`` receives what the call would launch under the current flags (vsx_gemm_plan)."""
     for t in (bias, grn_s, grn_b, red0, red1, colsum):
         if t is not None and t.dtype != torch.float32:
             raise TypeError("bias / GRN / reduction buffers must be float32")
@@ -114,6 +116,8 @@ def gemm(
     p.C2 = ptr(C2)
     p.b_bstride = b_bstride
     p.rscale = ptr(rscale)
+    if plan is not None:
+        return check(lib().vsx_gemm_plan(0 if kind == "nt" else 1, C.byref(p), dtype_code(dtype), C.byref(plan)), f"gemm_plan_{kind}")
     if kind == "nt" and epi == L.EPI_BIAS_GELU_SQ:
         _det(A.device, (M // 256 + 1) * N)
     fn = lib().vsx_gemm_nt if kind == "nt" else lib().vsx_gemm_tn
@@ -124,8 +128,12 @@ def tn_grn_stats_ok(M: int, N: int, K: int, hw: int, dtype: torch.dtype) -> bool
     """``gemm("tn", g, dout, dW2, ..., pro=PRO_GRN, aux=W2 (bf16 [N, K]), ldx=K, red0=P)`` — the fc2 weight gradient that also
     delivers the GRN backward statistics P[b, k] = sum_hw dz * g from the per-sample tiles in its accumulators (csrc/gemm.hip,
     gemm_tn_fast_kernel PRO == 2) — serves this shape"""
-    return dtype == torch.bfloat16 and hw > 0 and hw % 64 == 0 and M % hw == 0 and N >= 96 and K >= 128 and N % 8 == 0 and K % 8 == 0 \
-        and bool(lib().vsx_get_flag(b"tn_rect") & 8)
+    if dtype != torch.bfloat16 or not lib().vsx_get_flag(b"tn_rect") & 8:
+        return False
+    p = VsxGemm()   # the statistics launch as the block issues it: pointer fields only say which operands are there
+    p.A = p.B = p.C = p.grn_s = p.grn_b = p.aux = p.red0 = 1
+    p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldx, p.nz, p.pro, p.hw = M, N, K, K, N, K, K, 1, L.PRO_GRN, hw
+    return lib().vsx_gemm_plan(1, C.byref(p), L.VSX_BF16, C.byref(VsxGemmPlan())) == 0
 
 
 def dgrad_ln_bwd(dh: Tensor, WT: Tensor, xh: Tensor, rstd: Tensor, M: int, C: int, K: int,
