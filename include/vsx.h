@@ -46,8 +46,17 @@ int32_t vsx_get_flag(const char* name);
  * — per-workgroup partials in this caller-owned scratch (`floats` fp32 values, thread-local, used by the NEXT launches of this
  * thread; every launch checks the size and names what it needs), then one ordered pass — instead of by fp32 atomics, whose order
  * differs from run to run (timm GlobalResponseNorm / nn.InstanceNorm3d reduce deterministically on the CPU: reference behaviour
- * restated at viscy_models/unet/fcmae.py:174-221, components/heads.py:617-627).  NULL / 0 releases the scratch. */
+ * restated at viscy_models/unet/fcmae.py:174-221, components/heads.py:617-627).  NULL / 0 releases the scratch.
+ * Lifetime: a launch writes through this pointer, and a launch captured into a hipGraph keeps the pointer it was recorded with —
+ * the memory must stay allocated for as long as any graph captured under it may be replayed (viscy_amd.ops never frees it).
+ * How much a launch wants: VsxGemmPlan.det_floats of vsx_gemm_plan, vsx_mlp_det_floats, vsx_head_conv_det_floats — each the
+ * expression the launch itself checks against. */
 int32_t vsx_det_workspace(float* ws, int64_t floats);
+/* The same fixed-order sums for the launches of the CALLING THREAD only, whatever the process-wide flag says: vsx_det_scope(1)
+ * opens the scope, and the call returns the previous value, so that vsx_det_scope(previous) closes it and scopes nest.
+ * vsx_det_active: 1 where the det_reduce flag is set or the calling thread's scope is open — what every launch and the planner ask. */
+int32_t vsx_det_scope(int32_t on);
+int32_t vsx_det_active(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Operand "gather" description shared by the two GEMM kernels.  Row m of the logical
@@ -176,6 +185,8 @@ int32_t vsx_dwconv7_bwd_weight(const void* dy, const void* x, float* dw, float* 
  * ssum / ssq [B,32] += InstanceNorm statistics of the stored U, dW fp32 [32][216] += , db fp32 [32] += (may be NULL),
  * Wp: 45*2*64*8 bf16 packed by vsx_head_conv_dgrad_prep from Wc. */
 int32_t vsx_head_conv_supported(int32_t H2, int32_t W2, int32_t c3, int32_t cmid, int32_t zo, int32_t dtype);
+/* vsx_det_workspace floats that vsx_head_conv_fwd wants while vsx_det_active(): 64 partials per workgroup (0: shape not served) */
+int64_t vsx_head_conv_det_floats(int32_t B, int32_t H2, int32_t W2);
 int32_t vsx_head_conv_fwd(const void* hin, const void* Wc, const float* bias, void* U, float* ssum, float* ssq,
     int32_t B, int32_t H2, int32_t W2, int32_t c3, int32_t cmid, int32_t zo, int32_t dtype, vsx_stream_t stream);
 int32_t vsx_head_conv_wgrad(const void* hin, const void* dU, float* dW, float* db, int32_t B, int32_t H2, int32_t W2,
@@ -397,6 +408,9 @@ int32_t vsx_adamw(float* p, const float* g, float* m, float* v, const float* hyp
  *   vsx_mlp_fwd mode 0: colsq[b, 4C] += sum_hw gelu(fc1(xh))^2   (GRN statistics; nothing else is stored)
  *               mode 1: out = res + rscale[b] * (fc2(gelu(fc1(xh)) * s[b] + beta) + b2) */
 int32_t vsx_mlp_supported(int32_t C, int32_t hw, int64_t M, int32_t dtype);   /* the inference pair (modes 0 and 1) */
+/* vsx_det_workspace floats that a statistics pass (mode 0: vsx_mlp_fwd, 2 / 6: vsx_mlp_fc1 with / without h) wants while
+ * vsx_det_active(): one row of 4C column sums per workgroup (0: not a statistics mode, or the shape is not served) */
+int64_t vsx_mlp_det_floats(int32_t C, int32_t hw, int64_t M, int32_t mode);
 int32_t vsx_mlp_mode_supported(int32_t C, int32_t hw, int64_t M, int32_t mode, int32_t dtype);  /* one pass (mode 0..7) */
 int64_t vsx_mlp_image_bytes(int32_t C);
 int32_t vsx_mlp_pack(const void* W1, const void* W2, void* img, int32_t C, vsx_stream_t stream);

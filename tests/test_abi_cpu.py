@@ -143,3 +143,169 @@ def test_flag_globals_are_declared_in_one_header():
     for g in defined:
         assert re.search(r"^extern int [^;]*\b%s\b[^;]*;" % g, common, flags=re.M), g
         assert '&%s,' % g in api, g
+
+
+# ------------------------------------------------------------------------------------------------ fixed-order sums: scope, sizes, scratch
+def _gelu_sq_row(M, N, K, hw):
+    """the fc1 launch with the GELU / sum-of-squares epilogue, as tests/gemm_plan_rows.py writes a VsxGemm (pointers only say
+    which operands are there: nothing below reaches a kernel)"""
+    from tests import gemm_plan_rows as G
+    from tests import ref_ops as R
+
+    return G.struct_array([dict(G.row(M, N, K, K, K, N, hw=hw), **G._epi_fields(R.EPI_BIAS_GELU_SQ, N))])[0]
+
+
+def _det_plan(p):
+    from viscy_amd import _lib
+
+    plan = _lib.VsxGemmPlan()
+    assert _lib.lib().vsx_gemm_plan(0, ctypes.byref(p), _lib.VSX_BF16, ctypes.byref(plan)) == 0
+    return plan
+
+
+def _in_thread(fn):
+    import threading
+
+    out = []
+    t = threading.Thread(target=lambda: out.append(fn()))
+    t.start()
+    t.join()
+    return out[0]
+
+
+def test_det_scope_is_per_thread_and_nests():
+    from viscy_amd import _lib, ops
+
+    l = _lib.lib()
+    flag0 = l.vsx_get_flag(b"det_reduce")
+    l.vsx_set_flag(b"det_reduce", 0)
+    p = _gelu_sq_row(1024, 384, 96, 512)
+
+    def refused():
+        """this thread's launch under det, while this thread has handed over no workspace: refused before anything is launched"""
+        rc = l.vsx_gemm_nt(ctypes.byref(p), _lib.VSX_BF16, None)
+        return rc, l.vsx_last_error()
+
+    try:
+        assert l.vsx_det_active() == 0
+        assert l.vsx_det_scope(1) == 0
+        assert l.vsx_det_active() == 1 and l.vsx_get_flag(b"det_reduce") == 0
+        assert l.vsx_det_scope(1) == 1          # nested: the previous value comes back ...
+        assert l.vsx_det_scope(1) == 1 and l.vsx_det_active() == 1
+        assert l.vsx_det_scope(0) == 1 and l.vsx_det_active() == 0
+        assert l.vsx_det_scope(1) == 0          # ... and closing hands it back
+        # a thread started while this one's scope is open is outside it
+        assert _in_thread(l.vsx_det_active) == 0
+        assert _det_plan(p).det_floats == 1536 and _in_thread(lambda: _det_plan(p).det_floats) == 0
+        # ... and its workspace is its own: handing one over there leaves this thread without
+        assert l.vsx_det_workspace(None, 0) == 0
+        keep = (ctypes.c_float * 1536)()
+        assert _in_thread(lambda: l.vsx_det_workspace(keep, 1536)) == 0
+        assert refused() == (1, b"vsx_gemm_nt: det_reduce needs vsx_det_workspace(>= 1536 floats)")
+        # and one handed over here is not the other thread's, which is under its own scope there
+        assert l.vsx_det_workspace(keep, 1535) == 0
+        assert refused() == (1, b"vsx_gemm_nt: det_reduce needs vsx_det_workspace(>= 1536 floats)")   # one float short
+
+        def other():
+            with ops.det_scope():
+                return l.vsx_det_active(), refused()
+
+        assert _in_thread(other) == (1, (1, b"vsx_gemm_nt: det_reduce needs vsx_det_workspace(>= 1536 floats)"))
+        assert l.vsx_det_scope(0) == 1 and l.vsx_det_active() == 0
+        l.vsx_set_flag(b"det_reduce", 1)
+        assert l.vsx_det_active() == 1 and _in_thread(l.vsx_det_active) == 1   # the flag is the process's
+        with ops.det_scope():
+            with ops.det_scope(False):
+                assert l.vsx_det_active() == 1
+        l.vsx_set_flag(b"det_reduce", 0)
+        with ops.det_scope():
+            assert l.vsx_det_active() == 1
+            with ops.det_scope():
+                pass
+            assert l.vsx_det_active() == 1
+        assert l.vsx_det_active() == 0
+    finally:
+        l.vsx_det_scope(0)
+        l.vsx_det_workspace(None, 0)
+        l.vsx_set_flag(b"det_reduce", flag0)
+
+
+def test_det_size_queries_against_the_formulas_they_replace():
+    """what viscy_amd.ops computed by hand before the library was asked: the query is never larger, and equal wherever the
+    launch exists — except the GEMM, where the old formula carried a spare row: (M // 256 + 1) * N against (M / BM) * N"""
+    from viscy_amd import _lib
+
+    l = _lib.lib()
+    served = 0
+    for C in (64, 96, 192, 224, 384):
+        for hw in (64, 100, 256, 512, 1024, 4096):
+            for B in (1, 2, 3, 8):
+                M = B * hw
+                for mode in range(8):
+                    q, old = l.vsx_mlp_det_floats(C, hw, M, mode), (M // 256) * 4 * C
+                    if mode in (0, 2, 6) and l.vsx_mlp_mode_supported(C, hw, M, mode, _lib.VSX_BF16):
+                        served += 1
+                        assert q == old > 0, (C, hw, B, mode, q, old)
+                        rows = l.vsx_mlp_rows_per_workgroup(C, hw, M)   # the geometry, as the dh passes' workspace asks for it
+                        assert rows == 0 or q == M // rows * 4 * C
+                    else:
+                        assert q == 0, (C, hw, B, mode, q)
+    assert served >= 100
+    for B in (1, 2, 3):
+        for H2 in (8, 16, 24, 32, 48, 2048):
+            for W2 in (16, 24, 32, 64, 2048):
+                q, old = l.vsx_head_conv_det_floats(B, H2, W2), B * (H2 // 8) * (W2 // 16) * 64
+                if l.vsx_head_conv_supported(H2, W2, 8, 32, 5, _lib.VSX_BF16):
+                    assert q == old > 0, (B, H2, W2, q, old)
+                else:
+                    assert q == 0, (B, H2, W2, q)
+    assert l.vsx_head_conv_det_floats(0, 16, 16) == 0
+    nonzero = 0
+    assert l.vsx_det_scope(1) == 0
+    try:
+        for hw in (64, 128, 256, 512, 1024, 4096):
+            for B in (1, 2, 8):
+                for N, K in ((384, 96), (768, 192), (896, 224), (1536, 384), (100, 96)):
+                    M = B * hw
+                    p, plan = _gelu_sq_row(M, N, K, hw), _lib.VsxGemmPlan()
+                    if l.vsx_gemm_plan(0, ctypes.byref(p), _lib.VSX_BF16, ctypes.byref(plan)) != 0:
+                        continue
+                    old = (M // 256 + 1) * N
+                    assert plan.det_floats <= old
+                    if plan.family == b"gemm_nt2" and hw % 256 == 0 and hw > 256:   # two or more 256-row tiles per sample
+                        nonzero += 1
+                        assert plan.det_floats == (M // 256) * N == old - N
+                    else:
+                        assert plan.det_floats == 0
+    finally:
+        l.vsx_det_scope(0)
+    assert nonzero >= 30
+
+
+def test_scratch_never_releases_and_stays_within_twice_its_largest_buffer():
+    from viscy_amd import ops
+
+    allocated = []
+
+    def alloc(floats, dev):
+        allocated.append(floats)
+        return torch.empty(floats, dtype=torch.float32)
+
+    sc = ops.Scratch(alloc)
+    handed = []   # (address, floats) of every request
+    for n in (10, 5, 11, 100, 100, 101, 3, 1000, 999, 2001, 1):
+        t = sc.take("dev0", n)
+        assert t.numel() >= n
+        handed.append((t.data_ptr(), n))
+    assert allocated == [10, 20, 100, 200, 1000, 2001]   # grows by appending max(request, twice the last)
+    spans = [(b.data_ptr(), b.data_ptr() + 4 * b.numel()) for b in sc.held]
+    assert len(sc.held) == len(allocated)
+    for addr, n in handed:   # every address a launch may still hold lies in a buffer that is alive
+        assert any(lo <= addr and addr + 4 * n <= hi for lo, hi in spans), (addr, n)
+    assert sum(b.numel() for b in sc.held) <= 2 * max(b.numel() for b in sc.held)
+    assert sc.take("dev1", 4).data_ptr() != sc.take("dev0", 4).data_ptr()   # one arena per device
+    mine = sc.take("dev0", 7)
+    theirs = _in_thread(lambda: sc.take("dev0", 7))   # ... and per thread
+    assert theirs.data_ptr() != mine.data_ptr() and theirs.numel() == 7
+    assert any(b is theirs for b in sc.held)   # kept after its thread has ended
+    assert sc.take("dev0", 7) is mine

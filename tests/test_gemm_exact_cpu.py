@@ -199,6 +199,39 @@ def test_plans_equal_the_recorded_dispatch():
     assert len(refusals) >= 25 and all(c[0] == 1 for c in codes if c[0] != 0)
 
 
+def test_plans_under_a_det_scope_equal_the_plans_under_the_flag():
+    """the `det_reduce` rows of the table: with the flag at 0 and the calling thread's vsx_det_scope open, every plan is the one
+    the flag gives (family, tiles, grid, fixed-order floats; return code of a refusal)"""
+    import ctypes as C
+
+    from tests import gemm_plan_rows as G
+    from viscy_amd import _lib
+
+    lib = _lib.lib()
+    flag0 = lib.vsx_get_flag(b"det_reduce")
+    n_det = 0
+    try:
+        for kind, setting, dt, rows in G._grid_groups():
+            if setting != {"det_reduce": 1}:
+                continue
+            arr = G.struct_array(rows)
+            got = []
+            for flag, scope in ((1, 0), (0, 1)):
+                lib.vsx_set_flag(b"det_reduce", flag)
+                assert lib.vsx_det_scope(scope) == 0
+                plans, rcs = (_lib.VsxGemmPlan * len(rows))(), []
+                for p, pl in zip(arr, plans):
+                    rcs.append(lib.vsx_gemm_plan(kind, C.byref(p), dt, C.byref(pl)))
+                lib.vsx_det_scope(0)
+                got.append((rcs, bytes(plans)))
+                n_det += sum(pl.det_floats > 0 for pl in plans)
+            assert got[0] == got[1], (kind, dt)
+    finally:
+        lib.vsx_det_scope(0)
+        lib.vsx_set_flag(b"det_reduce", flag0)
+    assert n_det > 100
+
+
 # ------------------------------------------------------------------------------------------------ 3. sensitivity
 def _mutant(**over):
     ns = types.SimpleNamespace(**{k: getattr(R, k) for k in dir(R) if not k.startswith("__")})

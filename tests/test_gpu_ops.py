@@ -1925,3 +1925,175 @@ def test_weight_task_list_equals_single_launches():
             assert (ta is None) == (tb is None)
             if ta is not None:  # dgamma / matvec_t accumulate through atomics: order-dependent round-off
                 assert torch.equal(ta, tb) or torch.allclose(ta, tb, rtol=1e-5, atol=1e-5)
+
+
+# ------------------------------------------------------------------ fixed-order sums: scope route, workspace sizes, scratch lifetime
+class _ExactScratch:
+    """a fresh viscy_amd.ops.Scratch whose buffers have exactly the requested size and lie in front of a row of NaNs: a launch
+    that wants more than its size query said is refused, one that writes past it is seen"""
+
+    def __init__(self, ops):
+        self.guarded, self.sizes = [], []
+        self.scratch = ops.Scratch(self._alloc)
+
+    def _alloc(self, floats, dev):
+        buf = torch.full((floats + 256,), float("nan"), dtype=torch.float32, device=dev)
+        self.guarded.append(buf)
+        self.sizes.append(floats)
+        return buf[:floats]
+
+    def check(self):
+        torch.cuda.synchronize()
+        for buf, n in zip(self.guarded, self.sizes):
+            assert bool(torch.isnan(buf[n:]).all()), "a launch wrote past the workspace it asked for"
+
+
+def _both_det_routes(monkeypatch, run, floats):
+    """``run()`` under the det_reduce flag and under a det_scope with the flag at 0, each on a workspace of exactly ``floats``
+    values (what the library's size query answered): the same bits"""
+    from viscy_amd import _lib as L
+    from viscy_amd import ops
+
+    lib = L.lib()
+    flag0 = lib.vsx_get_flag(b"det_reduce")
+    outs = []
+    try:
+        for flag, scope in ((1, False), (0, True)):
+            ex = _ExactScratch(ops)
+            monkeypatch.setattr(ops, "_SCRATCH", ex.scratch)
+            lib.vsx_set_flag(b"det_reduce", flag)
+            with ops.det_scope(scope):
+                assert lib.vsx_det_active() == 1
+                outs.append(run())
+            ex.check()
+            assert ex.sizes == [floats], (ex.sizes, floats)
+    finally:
+        lib.vsx_set_flag(b"det_reduce", flag0)
+        lib.vsx_det_workspace(None, 0)
+    assert lib.vsx_det_active() == flag0
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+    return outs[0]
+
+
+def test_det_scope_equals_det_flag_on_the_fused_statistics_passes(monkeypatch):
+    """C = 96, hw = 512, B = 2: M = 1024 is four 256-row workgroups, two per sample — 4 x 4C floats of workspace"""
+    if SELF_CHECK:
+        pytest.skip("HIP-only kernel")
+    from viscy_amd import _lib as L
+    from viscy_amd import ops
+
+    dt, C, hw, B = torch.bfloat16, 96, 512, 2
+    M, H4 = B * hw, 4 * C
+    xh = rnd(M, C, dt=dt, seed=1).cuda()
+    W1, W2 = rnd(H4, C, dt=dt, seed=3, scale=C ** -0.5).cuda(), rnd(C, H4, dt=dt, seed=4, scale=H4 ** -0.5).cuda()
+    b1 = rnd(H4, seed=5, scale=0.1).cuda()
+    img = ops.mlp_pack(W1, W2, C)
+
+    def stats():
+        colsq = torch.zeros((B, H4), dtype=torch.float32, device="cuda")
+        ops.mlp_stats(xh, img, b1, colsq, M, C, hw)
+        return (colsq,)
+
+    def fc1(store_h):
+        colsq = torch.zeros((B, H4), dtype=torch.float32, device="cuda")
+        h, g = ops.mlp_fc1(xh, img, b1, colsq, M, C, hw, store_h=store_h)
+        return (colsq, g) + ((h,) if store_h else ())
+
+    for mode in (0, 2, 6):
+        assert L.lib().vsx_mlp_det_floats(C, hw, M, mode) == 4 * H4
+    (colsq,) = _both_det_routes(monkeypatch, stats, 4 * H4)
+    colsq2, g, h = _both_det_routes(monkeypatch, lambda: fc1(True), 4 * H4)
+    colsq6, g6 = _both_det_routes(monkeypatch, lambda: fc1(False), 4 * H4)
+    assert torch.equal(colsq2, colsq) and torch.equal(colsq6, colsq) and torch.equal(g6, g)
+    ref = torch.nn.functional.gelu((xh.float() @ W1.float().T + b1).to(dt).float()).to(dt).float()
+    close(colsq, (ref * ref).view(B, hw, H4).sum(1), torch.float32, "colsq", scale=float((ref * ref).view(B, hw, H4).sum(1).max()) * 5)
+
+
+def test_det_scope_equals_det_flag_on_the_gemm_gelu_epilogue(monkeypatch):
+    """M = 1024, N = 384, K = 96, hw = 512: vsx_gemm_plan answers det_floats = (M / 256) * N = 1536 for this row (checked without a
+    GPU in tests/test_abi_cpu.py), one workspace row per 256-row tile"""
+    if SELF_CHECK:
+        pytest.skip("HIP-only kernel")
+    from viscy_amd import _lib as L
+    from viscy_amd import ops
+
+    dt, M, N, K, hw = torch.bfloat16, 1024, 384, 96, 512
+    A, W = rnd(M, K, dt=dt, seed=1).cuda(), rnd(N, K, dt=dt, seed=2, scale=K ** -0.5).cuda()
+    b = rnd(N, seed=3, scale=0.1).cuda()
+
+    def run():
+        h, g = torch.empty((M, N), dtype=dt, device="cuda"), torch.empty((M, N), dtype=dt, device="cuda")
+        colsq = torch.zeros((M // hw, N), dtype=torch.float32, device="cuda")
+        ops.gemm("nt", A, W, h, M, N, K, K, K, N, dtype=dt, epi=L.EPI_BIAS_GELU_SQ, bias=b, red0=colsq, hw=hw, C2=g)
+        assert L.lib().vsx_last_kernel() == b"gemm_nt2"
+        return colsq, h, g
+
+    colsq, h, g = _both_det_routes(monkeypatch, run, (M // 256) * N)
+    close(colsq, (g.float() * g.float()).view(M // hw, hw, N).sum(1), torch.float32, "colsq")
+
+
+def test_det_scope_equals_det_flag_on_the_direct_head_convolution(monkeypatch):
+    """B = 2, H2 = 32, W2 = 16, 8 -> 32 channels, 5 planes: eight 16 x 8-pixel workgroups of 64 partials"""
+    if SELF_CHECK:
+        pytest.skip("HIP-only kernel")
+    from viscy_amd import _lib as L
+    from viscy_amd import ops
+
+    dt, B, H2, W2, c3, cmid, Zo = torch.bfloat16, 2, 32, 16, 8, 32, 5
+    Mh = B * H2 * W2
+    hin = rnd(Mh, (Zo + 2) * c3, dt=dt, seed=1).cuda()
+    Wg, _ = ops.prep_weight(rnd(cmid, c3, 3, 3, 3, seed=2, scale=0.1).cuda(), cmid, c3, 27, dt, tapmode=1)
+    bias = rnd(cmid, seed=3).cuda()
+
+    def run():
+        st = torch.zeros(2, B, cmid, device="cuda")
+        return st, ops.head_conv_fwd(hin, Wg, bias, st[0], st[1], B, H2, W2, c3, cmid, Zo)
+
+    assert L.lib().vsx_head_conv_det_floats(B, H2, W2) == 512
+    st, U = _both_det_routes(monkeypatch, run, 512)
+    u = U.float().view(B, H2 * W2 * Zo, cmid)
+    close(st[0], u.sum(1), dt, "sum")
+    close(st[1], (u * u).sum(1), dt, "sumsq")
+
+
+def test_captured_reduction_survives_the_growth_of_the_scratch(monkeypatch):
+    """a graph captured at a small shape keeps the workspace pointer it was recorded with; a later, larger request must not
+    release that memory (the single grow-and-replace workspace before viscy_amd.ops.Scratch did)"""
+    if SELF_CHECK:
+        pytest.skip("HIP-only kernel")
+    from viscy_amd import ops
+
+    dt = torch.bfloat16
+    sc = ops.Scratch()
+    monkeypatch.setattr(ops, "_SCRATCH", sc)
+
+    def operands(B, H, W, C):
+        M = B * H * W
+        return (rnd(M, C, dt=dt, seed=2).cuda(), rnd(M, C, dt=dt, seed=1).cuda(), torch.zeros(49, C, device="cuda"),
+                torch.zeros(C, device="cuda"), B, H, W, C)
+
+    def run(a):
+        a[2].zero_()
+        a[3].zero_()
+        ops.dwconv7_bwd_weight(*a)
+
+    small, large = operands(1, 16, 16, 32), operands(4, 32, 32, 64)
+    run(small)   # eager: sizes the scratch outside the graph's pool, and is the result to compare with
+    want = small[2].clone(), small[3].clone()
+    assert len(sc.held) == 1
+    used = sc.held[0].data_ptr()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        run(small)
+    assert len(sc.held) == 1
+    run(large)   # grows: a second buffer, the first one stays
+    torch.cuda.synchronize()
+    assert len(sc.held) == 2 and sc.held[0].data_ptr() == used and sc.held[1].numel() >= 2 * sc.held[0].numel()
+    junk = [torch.full_like(sc.held[0], float("nan")) for _ in range(4)]   # what would take the place of a released buffer
+    small[2].fill_(7.0)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(small[2], want[0]) and torch.equal(small[3], want[1])
+    assert all(bool(torch.isnan(j).all()) for j in junk)

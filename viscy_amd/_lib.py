@@ -69,6 +69,8 @@ _SIGS = {
     "vsx_set_flag": (_I32, [C.c_char_p, _I32]),
     "vsx_get_flag": (_I32, [C.c_char_p]),
     "vsx_det_workspace": (_I32, [_P, _I64]),
+    "vsx_det_scope": (_I32, [_I32]),
+    "vsx_det_active": (_I32, []),
     "vsx_gemm_nt": (_I32, [C.POINTER(VsxGemm), _I32, _P]),
     "vsx_gemm_tn": (_I32, [C.POINTER(VsxGemm), _I32, _P]),
     "vsx_gemm_plan": (_I32, [_I32, C.POINTER(VsxGemm), _I32, C.POINTER(VsxGemmPlan)]),
@@ -107,6 +109,7 @@ _SIGS = {
     "vsx_fill_f32": (_I32, [_P, _I64, _F32, _P]),
     "vsx_mlp_supported": (_I32, [_I32, _I32, _I64, _I32]),
     "vsx_mlp_mode_supported": (_I32, [_I32, _I32, _I64, _I32, _I32]),
+    "vsx_mlp_det_floats": (_I64, [_I32, _I32, _I64, _I32]),
     "vsx_mlp_image_bytes": (_I64, [_I32]),
     "vsx_mlp_pack": (_I32, [_P, _P, _P, _I32, _P]),
     "vsx_mlp_fwd": (_I32, [_P] * 11 + [_I64, _I32, _I32, _I32, _I32, _P]),
@@ -161,6 +164,7 @@ _SIGS = {
     "vsx_masked_mse_fwd": (_I32, [_P] * 5 + [_I32] * 3 + [_I64, _P]),
     "vsx_masked_mse_bwd": (_I32, [_P] * 6 + [_I32] * 3 + [_I64, _P]),
     "vsx_head_conv_supported": (_I32, [_I32] * 6),
+    "vsx_head_conv_det_floats": (_I64, [_I32] * 3),
     "vsx_head_conv_fwd": (_I32, [_P] * 6 + [_I32] * 7 + [_P]),
     "vsx_head_conv_wgrad": (_I32, [_P] * 4 + [_I32] * 7 + [_P]),
     "vsx_head_conv_dgrad_prep": (_I32, [_P, _P, _I32, _P]),

@@ -31,8 +31,9 @@ int g_vsx_tn_contig = 1;  // lean TN kernel: contiguous step range per split
 int g_vsx_mlp_fused = 111;  // fused GRN-MLP kernels (csrc/mlp.hip): bit 0 = inference forward (statistics + output passes, hidden activation on chip), bit 1 = training fc1 (statistics pass that also stores h and g), bit 3 = block backward without a stored dz (statistics from the per-sample weight-gradient products or MODE 3, then MODE 4 writes dh once) — on the C = 96 / 192 / 224 blocks; bit 2 = the training passes also on the C = 384 blocks (same step time, 7.7 GB less traffic per step); (bit 4 was the inference pair on the C = 384 blocks, slower than the unfused GEMMs there: removed in round 4); bit 5 = the block LayerNorm in the prologue of the fused passes (vsx_mlp_fwd_ln / vsx_mlp_fc1_ln: no separate LayerNorm pass); bit 6 = the pre-activation h is never stored on the C <= 224 blocks: the training fc1 writes g only (MODE 6) and the dh pass recomputes h from the C-wide normalised rows (MODE 5, vsx_mlp_bwd_dh_re); bit 7 (with 5 and 6) = the normalised rows x^ are not stored either: the forward keeps the depthwise output y + the row mean / rstd, the dh pass re-normalises y and writes dh * rstd (MODE 7, vsx_mlp_bwd_dh_ln), the fc1 weight gradient is a plain TN GEMM on y with a rank-1 correction, the LayerNorm backward in the data-gradient GEMM re-forms x^ from y.  Round 6 ships 111 (bit 7 off: x^ stored again, MODE 5): 92.28 -> 91.72 ms on the bench step, 90.42 -> 89.95 ms on the gate shape, four alternating pairs each on one box (and -0.25 / -0.7 ms on two other boxes), for 5.2 GB / step more C-wide writes: at round 6's kernels the re-normalisation in the dh pass and the rank-1 correction cost more than the bytes they save
 int g_vsx_mlp_sf32 = 1 | 4 | 64;  // fused GRN-MLP kernels: bit m = MODE m runs the build without packed-fp32 VALU instructions (csrc/mlp.hip, round 5: a v_pk_*_f32 next to MFMAs costs ~15 cycles; the forward passes gain 6 - 20 %, the dh passes are VALU-bound and keep the packed build)
 int g_vsx_det_reduce = 0;  // 1: the forward's per-sample sums — GRN sum g^2 of the fused GRN-MLP passes and of gemm_nt2's GELU epilogue, InstanceNorm sum / sum^2 of the direct head convolution — are formed in a FIXED order (per-workgroup partials in a caller-owned workspace, vsx_det_workspace, then one ordered pass) instead of by fp32 atomics: the bf16 forward is then bit-identical from run to run (with atomics: 7e-3 of the output maximum at 2048^2).  Cost: one small launch per pass, tools/det_fwd.py
-thread_local float* g_vsx_det_ws = nullptr;
-thread_local long g_vsx_det_ws_floats = 0;
+static thread_local float* g_det_ws = nullptr;
+static thread_local long g_det_ws_floats = 0;
+thread_local int g_vsx_det_scope = 0;
 int g_vsx_nt2 = 17;  // second-generation NT kernel (gemm_nt2.hip: 256 x 128 tiles, LDS-DMA operand path, wave-private epilogue): bit 0 = on for the launches it supports, bit 1 = also below 512 tiles
 int g_vsx_head_rows = 63;  // PixelToVoxelHead tail on row tiles with the 1x1x1 contraction on the matrix cores (head.hip, round 6; bf16, 64 | W2, Z <= 8): bit 0 = forward, bit 1 = backward pass 2, bit 2 = backward pass 1 with the folded weight gradient; bits 3 / 4 = the pixel shuffle + pad-pool in front of the head convolution and its adjoint on column strips (spatial.hip head_shuffle_{fwd,bwd}_strip_kernel; bf16, pooled, C3 * D = 56, 64 | w); bit 5 = the direct head convolution forward as a persistent kernel that requests the next halo tile ahead (headconv.hip)
 int g_vsx_head_bps = 0;  // head backward pass 1: workgroups per sample (0 = max(32, 8192 / B)); a small value makes every workgroup walk several tiles (tests)
@@ -48,10 +49,25 @@ void vsx_set_error(const char* fmt, ...) {
 /* det_reduce: scratch for the per-workgroup partial sums of the NEXT launches on this thread (caller-owned, `floats` fp32 values;
  * each launch that needs it checks the size and says how much it wants).  NULL / 0 takes it away again. */
 extern "C" int32_t vsx_det_workspace(float* ws, int64_t floats) {
-  g_vsx_det_ws = ws;
-  g_vsx_det_ws_floats = ws ? (long)floats : 0;
+  g_det_ws = ws;
+  g_det_ws_floats = ws ? (long)floats : 0;
   return 0;
 }
+int vsx_det_take(const char* who, long need, float** ws) {
+  *ws = nullptr;
+  if (!vsx_det_on() || need <= 0) return 0;
+  VSX_CHECK(g_det_ws != nullptr && g_det_ws_floats >= need, "%s: det_reduce needs vsx_det_workspace(>= %ld floats)", who, need);
+  *ws = g_det_ws;
+  return 0;
+}
+/* fixed-order sums for the launches of THIS thread while the scope is open, whatever the det_reduce flag says; returns the
+ * previous value (scopes nest: hand it back to close) */
+extern "C" int32_t vsx_det_scope(int32_t on) {
+  const int prev = g_vsx_det_scope;
+  g_vsx_det_scope = on != 0;
+  return prev;
+}
+extern "C" int32_t vsx_det_active(void) { return vsx_det_on(); }
 extern "C" int32_t vsx_version(void) { return 1; }
 extern "C" const char* vsx_last_error(void) { return g_err; }
 extern "C" const char* vsx_last_kernel(void) { return g_vsx_last_kernel; }

@@ -3,7 +3,7 @@
 //     C[M, N] = A[M, K] . B[N, K]^T  (+ the fused epilogues of vsx_gemm_nt)
 //
 // What bounds the first-generation kernel (gemm.hip: 128 x 128 tile, global -> VGPR -> LDS staging) was measured in round 3
-// with probe builds of this kernel (MFMA off / DMA off / stores off, tools/perf_nt_gen2.py): the K loop runs at the speed of
+// with probe builds of this kernel (MFMA off / DMA off / stores off; docs/history/measured_properties_r1_r4.md): the K loop runs at the speed of
 // its OPERAND STREAM, L2 -> LDS, which saturates near 10 TB/s chip-wide however it is issued (register staging, LDS-DMA with
 // 64- or 128-byte row pieces, 1 or 2 workgroups per CU, rotated K order: all within 10 %), and the epilogue traffic adds to it
 // instead of hiding under it (they share the memory pipeline).  With MFMA switched off entirely a K = 1536 launch takes 96 %
@@ -632,8 +632,8 @@ bool vsx_gemm_nt2_ok(const VsxGemm* p) {
   if (g_vsx_nt2 & 2) return true;  // (tests / A-B runs: every supported launch)
   // det_reduce: this kernel is the one whose GELU / sum-of-squares epilogue has the fixed-order path (the first-generation kernels
   // reduce with atomics) — it takes every such launch it supports, also the small ones the heuristics below leave to them
-  if (g_vsx_det_reduce && p->epi == VSX_EPI_BIAS_GELU_SQ) return true;
-  // Where the wide tiles pay (tools/perf_nt_gen2.py, B = 512, against the first-generation kernel): the K-heavy launches
+  if (vsx_det_on() && p->epi == VSX_EPI_BIAS_GELU_SQ) return true;
+  // Where the wide tiles pay (measured in round 3 at B = 512, against the first-generation kernel): the K-heavy launches
   // whose output is C-wide — fc2 / fc1 data gradient of the C = 384 / 768 stages -10 .. -25 %, of the 224-channel decoder
   // stage -4 .. -10 % — and the C = 384 fc1 (-14 %).  Not the dz epilogue (its second operand stream eats the gain), not
   // K <= 384 with a narrow N (three slabs per tile at one workgroup per CU: +5 .. +25 %).
@@ -657,15 +657,14 @@ void vsx_gemm_nt2_plan(const VsxGemm* p, VsxGemmPlan& pl) {
   pl.block = 512;
   // det_reduce: per-tile column sums to a workspace, added in a fixed order afterwards (hw <= 256: at most two adds per
   // address — already independent of their order)
-  if (g_vsx_det_reduce && p->epi == VSX_EPI_BIAS_GELU_SQ && p->hw > 0 && p->hw % BM == 0 && p->hw > BM) pl.det_floats = (long)(p->M / BM) * p->N;
+  if (vsx_det_on() && p->epi == VSX_EPI_BIAS_GELU_SQ && p->hw > 0 && p->hw % BM == 0 && p->hw > BM) pl.det_floats = (long)(p->M / BM) * p->N;
 }
 
 int vsx_gemm_nt2_run(const VsxGemmPlan& pl, const VsxGemm* p, hipStream_t s) {
   VsxGemm q = *p;
-  if (pl.det_floats) {  // checked here, not in the plan: the workspace belongs to the calling thread
-    VSX_CHECK(g_vsx_det_ws != nullptr && g_vsx_det_ws_floats >= pl.det_floats, "vsx_gemm_nt: det_reduce needs vsx_det_workspace(>= %ld floats)", (long)pl.det_floats);
-    q.aux = g_vsx_det_ws;
-  }
+  float* det_ws;  // checked here, not in the plan: the workspace belongs to the calling thread
+  if (int e = vsx_det_take("vsx_gemm_nt", pl.det_floats, &det_ws)) return e;
+  if (det_ws) q.aux = det_ws;
   const dim3 grid(pl.grid[0]), block(pl.block);
 #define NT2(EPI, BN, PRO) case (EPI) << 12 | (BN) << 1 | (PRO): hipLaunchKernelGGL((gemm_nt2_kernel<EPI, BN, PRO>), grid, block, 0, s, q); break;
 #define NT2_BN(BN) /* the five epilogues; the GRN prologue exists for the two of the fc2 forward */ \
@@ -685,7 +684,7 @@ int vsx_gemm_nt2_run(const VsxGemmPlan& pl, const VsxGemm* p, hipStream_t s) {
 #undef NT2_LNBWD
   VSX_LAUNCH_CHECK();
   g_vsx_last_kernel = pl.family;
-  if (pl.det_floats) return vsx_det_group_sum(g_vsx_det_ws, p->N, 0, p->red0, p->M / p->hw, p->hw / BM, p->N, s);
+  if (det_ws) return vsx_det_group_sum(det_ws, p->N, 0, p->red0, p->M / p->hw, p->hw / BM, p->N, s);
   return 0;
 }
 

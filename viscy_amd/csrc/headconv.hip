@@ -608,20 +608,21 @@ static int hc_check(const char* who, int B, int H2, int W2, int c3, int cmid, in
 extern "C" int32_t vsx_head_conv_supported(int32_t H2, int32_t W2, int32_t c3, int32_t cmid, int32_t zo, int32_t dtype) {
   return dtype == VSX_BF16 && c3 == HC_C3 && cmid == HC_CMID && zo == HC_ZO && H2 > 0 && W2 > 0 && H2 % 16 == 0 && W2 % 16 == 0;
 }
+static int hc_tiles(int H2, int W2) { return (W2 / 16) * (H2 / HF_TY); }  // workgroups (or tiles of the persistent kernel) per sample
+static long hc_det_need(int B, int H2, int W2) { return (long)B * hc_tiles(H2, W2) * 64; }
+extern "C" int64_t vsx_head_conv_det_floats(int32_t B, int32_t H2, int32_t W2) {
+  return B > 0 && H2 > 0 && W2 > 0 && H2 % 16 == 0 && W2 % 16 == 0 ? hc_det_need(B, H2, W2) : 0;
+}
 extern "C" int32_t vsx_head_conv_fwd(const void* hin, const void* Wc, const float* bias, void* U, float* ssum, float* ssq,
                                      int32_t B, int32_t H2, int32_t W2, int32_t c3, int32_t cmid, int32_t zo, int32_t dtype,
                                      vsx_stream_t stream) {
   if (int e = hc_check("vsx_head_conv_fwd", B, H2, W2, c3, cmid, zo, dtype)) return e;
   VSX_CHECK(hin && Wc && U && ssum && ssq, "vsx_head_conv_fwd: null pointer");
-  float* det_ws = nullptr;
-  const int tiles = (W2 / 16) * (H2 / HF_TY);
-  if (g_vsx_det_reduce) {  // fixed-order InstanceNorm sums: 64 partials per workgroup, then one ordered pass per array
-    const long need = (long)B * tiles * 64;
-    VSX_CHECK(g_vsx_det_ws != nullptr && g_vsx_det_ws_floats >= need, "vsx_head_conv_fwd: det_reduce needs vsx_det_workspace(>= %ld floats)", need);
-    det_ws = g_vsx_det_ws;
-  }
+  float* det_ws;  // fixed-order InstanceNorm sums: 64 partials per workgroup, then one ordered pass per array
+  const int tiles = hc_tiles(H2, W2);
+  if (int e = vsx_det_take("vsx_head_conv_fwd", hc_det_need(B, H2, W2), &det_ws)) return e;
   const long ntiles = (long)B * tiles;
-  if ((g_vsx_head_rows & 32) && ntiles <= 0x7fffffffL) {  // persistent (round 6): three workgroups per CU, a contiguous tile range each
+  if ((g_vsx_head_rows & 32) && ntiles <= 0x7fffffffL) {  // persistent (round 6): HCF_WPE = 2 workgroups per CU, a contiguous tile range each
     const int tpw = vsx_cdiv(ntiles, 256L * HCF_WPE);
     hipLaunchKernelGGL(head_conv_fwd_persist_kernel, dim3(vsx_cdiv(ntiles, (long)tpw)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)hin, (const bf16_t*)Wc, bias, (bf16_t*)U, ssum, ssq, H2, W2, det_ws, (int)ntiles, tpw);

@@ -695,7 +695,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
   // every wave must be done reading sub-chunk 0's fragments out of buffer 1 before step 0 refills that buffer by LDS-DMA.  (This
   // barrier was missing until round 4: a fast wave's prefetch could overwrite the fragments a slow wave was still multiplying —
   // hidden by the DMA latency while one workgroup owned the CU, exposed as wrong hidden columns 16..31 of the first sub-chunk in
-  // whole 32-row groups once two workgroups shared a CU at C = 192 / 224: tools/probe_mode6.py, tools/det_fwd.py.)
+  // whole 32-row groups once two workgroups shared a CU at C = 192 / 224: tools/det_fwd.py.)
   __syncthreads();
 
   // column sums of the sub-chunk `hq` of dh (parked in `red` before the last barrier): one workspace row per workgroup, no
@@ -1018,14 +1018,8 @@ static int mlp_dispatch(const MlpCfg* c, const MlpArgs& a, hipStream_t s) {
 
 // det_reduce: the statistics passes (MODE 0 / 2 / 6) leave one row of column sums per workgroup in the thread's workspace
 // (vsx_det_workspace) and an ordered pass adds a sample's rows into colsq — no atomics, the same bits in every run
-static int mlp_det_begin(MlpArgs& a, const MlpCfg* c, const char* who) {
-  a.ws = nullptr;
-  if (!g_vsx_det_reduce) return 0;
-  const long need = (long)(a.M / (c->NW * 16 * c->MF)) * 4 * c->C;
-  VSX_CHECK(g_vsx_det_ws != nullptr && g_vsx_det_ws_floats >= need, "%s: det_reduce needs vsx_det_workspace(>= %ld floats)", who, need);
-  a.ws = g_vsx_det_ws;
-  return 0;
-}
+static long mlp_det_need(const MlpCfg* c, long M) { return M / (c->NW * 16 * c->MF) * 4 * c->C; }
+static int mlp_det_begin(MlpArgs& a, const MlpCfg* c, const char* who) { return vsx_det_take(who, mlp_det_need(c, a.M), &a.ws); }
 static int mlp_det_end(const MlpArgs& a, const MlpCfg* c, hipStream_t s) {
   if (!a.ws) return 0;
   const int bm = c->NW * 16 * c->MF;
@@ -1226,6 +1220,11 @@ extern "C" int32_t vsx_debug_mlp_ts(unsigned long long* host_out) {
   return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_mlp_ts), sizeof(g_mlp_ts)) == hipSuccess ? 0 : 1;
 }
 #endif
+
+extern "C" int64_t vsx_mlp_det_floats(int32_t C, int32_t hw, int64_t M, int32_t mode) {
+  const MlpCfg* c = mode == 0 || mode == 2 || mode == 6 ? mlp_cfg(C, hw, M, mode) : nullptr;
+  return c ? mlp_det_need(c, M) : 0;
+}
 
 extern "C" int32_t vsx_mlp_rows_per_workgroup(int32_t C, int32_t hw, int64_t M) {
   const MlpCfg* c = mlp_cfg(C, hw, M, 4);

@@ -19,8 +19,11 @@ extern int g_vsx_ln_fblk, g_vsx_ln_bblk, g_vsx_ln_ablk, g_vsx_ln_pack, g_vsx_ln_
 extern int g_vsx_grn_stream, g_vsx_ggb_contig, g_vsx_ggb_blocks;
 extern int g_vsx_dw_mfma, g_vsx_mlp_fused, g_vsx_mlp_sf32, g_vsx_loss_fused;
 extern int g_vsx_head_bps, g_vsx_head_rows, g_vsx_det_reduce;
-extern thread_local float* g_vsx_det_ws;     // api.hip: vsx_det_workspace
-extern thread_local long g_vsx_det_ws_floats;
+extern thread_local int g_vsx_det_scope;  // api.hip: vsx_det_scope
+// fixed-order sums wanted by the calling thread: the det_reduce flag (process) or an open vsx_det_scope (thread)
+static inline bool vsx_det_on() { return g_vsx_det_reduce || g_vsx_det_scope; }
+// *ws = the thread's vsx_det_workspace, which must hold `need` floats, or nullptr where det is off or the launch needs none (api.hip)
+int vsx_det_take(const char* who, long need, float** ws);
 // out[g * N + n] += sum over r < rows_per_group, IN ORDER, of ws[(g * rows_per_group + r) * ld + col0 + n]   (norm.hip)
 int vsx_det_group_sum(const float* ws, int ld, int col0, float* out, int groups, int rows_per_group, int N, hipStream_t s);
 extern thread_local const char* g_vsx_last_kernel;  // api.hip: set by the GEMM dispatchers, read by vsx_last_kernel()

@@ -654,19 +654,14 @@ class Engine:
     # ------------------------------------------------------------------ forward
     def forward(self, x: Tensor, dt: torch.dtype, need_bwd: bool, masks=None, bn_groups: int = 1):
         """A forward WITHOUT a backward behind it (predict / validation / `InferStep` captures) forms the per-sample GRN and
-        InstanceNorm sums in a fixed order (`det_reduce`), as the reference's CPU path is deterministic: with fp32 atomics the
-        bf16 forward at 2048^2 differs by 7e-3 of the output maximum from run to run, the fixed order costs 0.3 % of a pass
-        (profiles/r05_det_reduce.txt; VERDICT r5).  Training forwards keep the atomics unless the flag is set by hand;
+        InstanceNorm sums in a fixed order (`ops.det_scope`: what the `det_reduce` flag does, for this thread only), as the
+        reference's CPU path is deterministic: with fp32 atomics the bf16 forward at 2048^2 differs by 7e-3 of the output maximum
+        from run to run, the fixed order costs 0.3 % of a pass (profiles/r05_det_reduce.txt).  Training forwards
+        keep the atomics unless the `det_reduce` flag is set by hand;
         ``VSX_DET_INFER=0`` in the environment switches the automatic setting off."""
-        auto = (not need_bwd) and self._hip and os.environ.get("VSX_DET_INFER", "1") != "0" \
-            and L.lib().vsx_get_flag(b"det_reduce") == 0
-        if not auto:
+        auto = (not need_bwd) and self._hip and os.environ.get("VSX_DET_INFER", "1") != "0"
+        with hip_ops.det_scope(auto):  # per thread: the process-wide flag is left alone
             return self._forward(x, dt, need_bwd, masks, bn_groups)
-        L.lib().vsx_set_flag(b"det_reduce", 1)
-        try:
-            return self._forward(x, dt, need_bwd, masks, bn_groups)
-        finally:
-            L.lib().vsx_set_flag(b"det_reduce", 0)
 
     def _forward(self, x: Tensor, dt: torch.dtype, need_bwd: bool, masks=None, bn_groups: int = 1):
         """``masks``: None (dense) or, per encoder stage, ``(idx, inv, keep, L)`` int32 row maps of the FCMAE mask at that

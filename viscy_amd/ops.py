@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import threading
 from typing import Sequence
 
 import torch
@@ -18,30 +19,67 @@ from . import _lib as L
 from ._lib import VsxGemm, VsxGemmPlan, check, dtype_code, lib, ptr, stream
 
 
-_WS: dict = {}
+class Scratch:
+    """fp32 scratch of the two-stage reductions: the launches that write one row of partial sums per workgroup — into a workspace
+    argument, or into the thread's ``vsx_det_workspace`` — and then fold the rows in a fixed order.
+
+    One rule: a buffer that has been handed to a launch is never released for the life of the process.  The launch holds a raw
+    pointer, and a launch captured into a hipGraph replays with the pointer it was recorded with, however much later and whatever
+    has been requested in between.
+
+    There is one arena per (thread, device): the library's det workspace is per thread.  ``take`` answers with the arena's newest
+    buffer; where that is too small it appends a buffer of at least twice its size, so what an arena retains is at most twice
+    its largest buffer (s + s/2 + s/4 + ...).  ``held`` keeps every buffer of every thread, also those of threads that have ended.
+    Launches of one thread on different streams share the arena's buffer, as they shared the single workspace before this class:
+    the engine issues its reductions on one stream per thread.  No entry point takes both a workspace argument and the det
+    workspace, so one arena serves both."""
+
+    def __init__(self, alloc=None):
+        self._alloc = alloc or (lambda floats, dev: torch.empty(floats, dtype=torch.float32, device=dev))
+        self._tls = threading.local()
+        self.held: list = []
+
+    def take(self, dev, floats: int):
+        arenas = getattr(self._tls, "arenas", None)
+        if arenas is None:
+            arenas = self._tls.arenas = {}
+        last = arenas.get(dev)
+        if last is None or last.numel() < floats:
+            last = arenas[dev] = self._alloc(max(int(floats), 2 * last.numel() if last is not None else 0), dev)
+            self.held.append(last)
+        return last
 
 
-def _workspace(dev, numel: int) -> Tensor:
-    """fp32 scratch the two-stage reductions write their per-block partials into (caller-owned, reused)."""
-    w = _WS.get(dev)
-    if w is None or w.numel() < numel:
-        w = torch.empty(numel, dtype=torch.float32, device=dev)
-        _WS[dev] = w
-    return w
+_SCRATCH = Scratch()
 
 
-_DET_WS: dict = {}
+def _workspace(dev, floats: int) -> Tensor:
+    """>= ``floats`` fp32 values for the per-workgroup partials of the next launch"""
+    return _SCRATCH.take(dev, floats)
 
 
-def _det(dev, floats: int) -> None:
-    """``det_reduce`` flag on: hand the library the scratch for the per-workgroup partial sums of the next launch (grown, never
-    freed: a captured hipGraph keeps pointing at it)"""
-    if not lib().vsx_get_flag(b"det_reduce"):
+def _det(dev, floats) -> None:
+    """fixed-order sums active on this thread (``det_reduce`` flag or ``det_scope``): hand the library the scratch for the
+    per-workgroup partial sums of the next launch; ``floats()`` is the library's own size query for that launch"""
+    if not lib().vsx_det_active():
         return
-    held = _DET_WS.setdefault(dev, [])
-    if not held or held[-1].numel() < floats:
-        held.append(torch.empty(max(int(floats), 1 << 20), dtype=torch.float32, device=dev))
-    check(lib().vsx_det_workspace(ptr(held[-1]), held[-1].numel()), "det_workspace")
+    n = int(floats())
+    if n > 0:
+        ws = _workspace(dev, n)
+        check(lib().vsx_det_workspace(ptr(ws), ws.numel()), "det_workspace")
+
+
+@contextlib.contextmanager
+def det_scope(on: bool = True):
+    """the launches of this thread inside the block form their per-sample sums in a fixed order (vsx_det_scope); nests"""
+    if not on:
+        yield
+        return
+    prev = lib().vsx_det_scope(1)
+    try:
+        yield
+    finally:
+        lib().vsx_det_scope(prev)
 
 
 def _fill8(arr, vals: Sequence[int] | None):
@@ -119,9 +157,15 @@ def gemm(
     if plan is not None:
         return check(lib().vsx_gemm_plan(0 if kind == "nt" else 1, C.byref(p), dtype_code(dtype), C.byref(plan)), f"gemm_plan_{kind}")
     if kind == "nt" and epi == L.EPI_BIAS_GELU_SQ:
-        _det(A.device, (M // 256 + 1) * N)
+        _det(A.device, lambda: _gemm_det_floats(p, dtype))
     fn = lib().vsx_gemm_nt if kind == "nt" else lib().vsx_gemm_tn
     check(fn(C.byref(p), dtype_code(dtype), stream()), f"gemm_{kind}")
+
+
+def _gemm_det_floats(p: VsxGemm, dtype: torch.dtype) -> int:
+    plan = VsxGemmPlan()
+    check(lib().vsx_gemm_plan(0, C.byref(p), dtype_code(dtype), C.byref(plan)), "gemm_plan_nt")
+    return plan.det_floats
 
 
 def tn_grn_stats_ok(M: int, N: int, K: int, hw: int, dtype: torch.dtype) -> bool:
@@ -522,7 +566,7 @@ def _mlp_fwd(who: str, mode: int, xh: Tensor, ln_eps: float, img: Tensor, b1: Te
 def mlp_stats(xh: Tensor, img: Tensor, b1: Tensor, colsq: Tensor, M: int, C: int, hw: int, ln_eps: float = 0.0) -> None:
     """colsq[b, 4C] += per-sample column sums of gelu(fc1(xh))^2 — nothing 4C-wide is written.  ``ln_eps`` > 0: ``xh`` holds the
     UN-normalised rows and the kernel applies the block LayerNorm (no affine) in its prologue"""
-    _det(xh.device, (M // 256) * 4 * C)
+    _det(xh.device, lambda: lib().vsx_mlp_det_floats(C, hw, M, 0))
     _mlp_fwd("mlp_stats", 0, xh, ln_eps, img, b1, None, None, None, None, None, None, colsq, M=M, C=C, hw=hw)
 
 
@@ -531,7 +575,7 @@ def mlp_fc1(xh: Tensor, img: Tensor, b1: Tensor, colsq: Tensor, M: int, C: int, 
     (where ``mlp_supported(.., 6)``): h is None — the backward recomputes it (mlp_bwd_dh_re)"""
     h = torch.empty((M, 4 * C), dtype=xh.dtype, device=xh.device) if store_h else None
     g = torch.empty((M, 4 * C), dtype=xh.dtype, device=xh.device)
-    _det(xh.device, (M // 256) * 4 * C)
+    _det(xh.device, lambda: lib().vsx_mlp_det_floats(C, hw, M, 2 if store_h else 6))
     check(lib().vsx_mlp_fc1(ptr(xh), ptr(img), ptr(b1), ptr(colsq), ptr(_gelu_table(xh.device)), ptr(h), ptr(g), M, C, hw,
                             dtype_code(xh.dtype), stream()), "mlp_fc1")
     return h, g
@@ -548,7 +592,7 @@ def mlp_fc1_ln(y: Tensor, img: Tensor, b1: Tensor, colsq: Tensor, M: int, C: int
     rstd = torch.empty(M, dtype=torch.float32, device=y.device)
     h = torch.empty((M, 4 * C), dtype=y.dtype, device=y.device) if store_h else None
     g = torch.empty((M, 4 * C), dtype=y.dtype, device=y.device)
-    _det(y.device, (M // 256) * 4 * C)
+    _det(y.device, lambda: lib().vsx_mlp_det_floats(C, hw, M, 2 if store_h else 6))
     check(lib().vsx_mlp_fc1_ln(ptr(y), eps, ptr(xh), ptr(rstd), ptr(mean), ptr(img), ptr(b1), ptr(colsq), ptr(_gelu_table(y.device)),
                                ptr(h), ptr(g), M, C, hw, dtype_code(y.dtype), stream()), "mlp_fc1_ln")
     return (xh if store_xh else (y, mean)), rstd, h, g
@@ -630,7 +674,7 @@ def head_conv_supported(H2: int, W2: int, c3: int, cmid: int, zo: int, dtype: to
 def head_conv_fwd(hin: Tensor, Wc: Tensor, bias: Tensor | None, ssum: Tensor, ssq: Tensor, B: int, H2: int, W2: int, c3: int,
                   cmid: int, zo: int) -> Tensor:
     U = torch.empty((B * H2 * W2, zo * cmid), dtype=hin.dtype, device=hin.device)
-    _det(hin.device, B * (H2 // 8) * (W2 // 16) * 64)  # one row of 64 partials per 16 x 8-pixel workgroup
+    _det(hin.device, lambda: lib().vsx_head_conv_det_floats(B, H2, W2))
     check(lib().vsx_head_conv_fwd(ptr(hin), ptr(Wc), ptr(bias), ptr(U), ptr(ssum), ptr(ssq), B, H2, W2, c3, cmid, zo,
                                   dtype_code(hin.dtype), stream()), "head_conv_fwd")
     return U
@@ -778,18 +822,14 @@ def voxel_shuffle_bwd(dout: Tensor, B: int, h: int, w: int, Cout: int, D: int, s
 
 # ------------------------------------------------------------------ narrow-channel family (csrc/narrow.hip): the 2x2-stem FCMAE
 NARROW_STEM, NARROW_PROJ, NARROW_FWD1, NARROW_BWD_A, NARROW_BWD_B, NARROW_BWD_C = range(6)
-_NARROW_WS: dict = {}
 
 
 def _narrow_ws(dev, op: int, B: int, n: int, C: int, K: int = 0) -> Tensor:
-    """per-workgroup partials of a narrow launch (grown, never freed: a captured hipGraph keeps pointing at it)"""
+    """per-workgroup partials of a narrow launch, sized by the library"""
     floats = int(lib().vsx_narrow_ws_floats(op, B, n, C, K))
     if floats <= 0:
         raise ValueError(f"vsx_narrow_ws_floats({op}, {B}, {n}, {C}, {K}) = {floats}")
-    held = _NARROW_WS.setdefault(dev, [])
-    if not held or held[-1].numel() < floats:
-        held.append(torch.empty(max(floats, 1 << 16), dtype=torch.float32, device=dev))
-    return held[-1]
+    return _workspace(dev, floats)
 
 
 def narrow_stem_fwd(x: Tensor, W: Tensor, b: Tensor, kernel: tuple[int, int, int], dtype: torch.dtype) -> Tensor:
