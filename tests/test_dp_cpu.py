@@ -116,6 +116,7 @@ def test_device_side_schedule_matches_torch_adamw_with_warmup_cosine():
     n = 1000
     eng.flat = torch.randn(n)
     eng.flat_grad = torch.zeros(n)
+    eng.trainable_numel = eng.flat.numel
     ref_p = torch.nn.Parameter(eng.flat.clone())
     topt = torch.optim.AdamW([ref_p], lr=2e-3)
     total, warm, mult = 12, 3, 1e-3

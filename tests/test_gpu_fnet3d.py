@@ -181,6 +181,37 @@ def test_fp32_engine_matches_fixture(golden, name):
         assert _rel(m(case["x"].cuda()), case["out_eval"]) <= 1e-3
 
 
+def test_autograd_mode_equals_flat_mode_fp32(golden):
+    """the same net and input in ``grad_mode = "flat"`` and ``"autograd"``: equal up to the run-to-run floor of the atomic
+    reductions, measured here on two identical flat-mode runs, and every parameter receives a ``.grad``"""
+    case = golden["cases"]["d3_m2_out2"]
+    m = _gpu_model(case, torch.float32, "flat")
+    eng = m.engine()
+    x, gout = case["x"].cuda(), case["gout"].cuda()
+
+    def flat_run():
+        m.grad_mode = "flat"
+        eng.flat_grad.zero_()
+        m(x).backward(gout)
+        return eng.flat_grad.clone()
+
+    g1, g1b = flat_run(), flat_run()
+    m.grad_mode = "autograd"
+    for p in m.parameters():
+        p.grad = None
+    kept = eng.flat_grad.clone()
+    m(x).backward(gout)
+    assert all(p.grad is not None for p in m.parameters())
+    assert torch.equal(eng.flat_grad, kept)  # autograd mode leaves the flat buffer alone
+    ga = torch.zeros_like(g1)
+    for p, o in zip(eng.order, eng.offsets):
+        ga[o : o + p.numel()] = p.grad.flatten()
+    floor = torch.nn.functional.cosine_similarity(g1, g1b, dim=0).item()
+    cos = torch.nn.functional.cosine_similarity(g1, ga, dim=0).item()
+    print(f"flat vs flat {floor:.7f}, flat vs autograd {cos:.7f}")
+    assert cos > floor - 2e-3, (floor, cos)
+
+
 def test_fp32_engine_matches_statement_wider():
     """a wider net (vector paths, 64-column tiles, B = 1, deepest level Z = 1) against the statement in fp32"""
     from viscy_amd.unet3d import Unet3d

@@ -347,6 +347,47 @@ def test_full_size_gradient_is_linear_in_dout_bf16():
     assert abs((gs.norm() / g1.norm()).item() - 1.0) < 4e-2
 
 
+def test_autograd_mode_equals_flat_mode_fp32():
+    """the same model and input in ``grad_mode = "flat"`` (gradients accumulated into the zeroed flat buffer) and ``"autograd"``
+    (a zeroed buffer of the backward's own, handed to autograd): equal up to the run-to-run floor of the atomic reductions,
+    measured here on two identical flat-mode runs, and every parameter receives a ``.grad``"""
+    from viscy_amd.unext2 import UNeXt2
+
+    torch.manual_seed(5)
+    m = UNeXt2(in_channels=1, out_channels=2, in_stack_depth=5, backbone="convnextv2_femto").cuda()
+    with torch.no_grad():  # GRN starts at zero in timm: give it something to do
+        for n, p in m.named_parameters():
+            if ".grn." in n:
+                p.normal_(0.0, 0.2)
+    m.compute_dtype = torch.float32
+    eng = m.engine()
+    g = torch.Generator().manual_seed(14)
+    x = torch.randn(2, 1, 5, 64, 96, generator=g).cuda()
+    dout = torch.randn(2, 2, 5, 64, 96, generator=g).cuda()
+
+    def flat_run():
+        m.grad_mode = "flat"
+        eng.flat_grad.zero_()
+        m(x).backward(dout)
+        return eng.flat_grad.clone()
+
+    g1, g1b = flat_run(), flat_run()
+    m.grad_mode = "autograd"
+    for p in m.parameters():
+        p.grad = None
+    kept = eng.flat_grad.clone()
+    m(x).backward(dout)
+    assert all(p.grad is not None for p in m.parameters())
+    assert torch.equal(eng.flat_grad, kept)  # autograd mode leaves the flat buffer alone
+    ga = torch.zeros_like(g1)
+    for p, o in zip(eng.order, eng.offsets):
+        ga[o : o + p.numel()] = p.grad.flatten()
+    floor = torch.nn.functional.cosine_similarity(g1, g1b, dim=0).item()
+    cos = torch.nn.functional.cosine_similarity(g1, ga, dim=0).item()
+    print(f"flat vs flat {floor:.7f}, flat vs autograd {cos:.7f}")
+    assert cos > floor - 2e-3, (floor, cos)
+
+
 def test_full_size_mixed_loss_identities():
     """MixedLoss(t, t) = 0 with zero gradient for the MS-SSIM + L1 terms at full patch size; loss is symmetric under a
     permutation of the batch; the L1-only loss of (p, t) equals mean |p - t| computed by torch on the device."""

@@ -312,6 +312,7 @@ def test_unsynced_graph_replays_follow_the_warmup_cosine_schedule():
     eng = _Eng()
     eng.flat = torch.randn(n, device="cuda")
     eng.flat_grad = torch.zeros(n, device="cuda")
+    eng.trainable_numel = eng.flat.numel
     gsrc = torch.randn(n, device="cuda")
     p_ref = torch.nn.Parameter(eng.flat.detach().cpu().clone())
     topt = torch.optim.AdamW([p_ref], lr=3e-3)

@@ -129,6 +129,9 @@ class _FakeEngine:
         self.bucket_bounds = [(0, n // 3), (n // 3, 2 * n // 3), (2 * n // 3, n)]
         self.on_bucket_ready = None
 
+    def reset_pending(self):
+        pass
+
 
 class _FakeOpt:
     grad_scale = 1.0

@@ -28,7 +28,7 @@ def timed_forward():
     y, sv = eng.forward(x, torch.bfloat16, need_bwd=True)
     e1.record()
     torch.cuda.synchronize()
-    eng._pending_bwd = 0
+    eng.reset_pending()
     return y.clone(), e0.elapsed_time(e1)
 
 

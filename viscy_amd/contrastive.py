@@ -27,6 +27,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
+from .flat import CoreProxy
 from .unext2 import _Conv, _Core, _Encoder, _Holder, _LN, _Stem
 
 
@@ -64,9 +65,6 @@ class _EmbedCore(_Core):
         self.encoder_stages = _Encoder(depths, dims, False, v1=v1)
         self.stem = _Stem(in_channels, dims[0] // ratio, tuple(stem_kernel_size))
         self.tail = _Tail(dims[-1], embedding_dim, projection_dim)
-        self.compute_dtype = None
-        self.grad_mode = "autograd"
-        self._engine = None
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -80,7 +78,7 @@ class _EmbedCore(_Core):
             nn.init.uniform_(conv.bias, -bound, bound)
 
 
-class ContrastiveEncoder(nn.Module):
+class ContrastiveEncoder(CoreProxy, nn.Module):
     def __init__(self, backbone: Literal["convnext_tiny", "convnextv2_tiny", "resnet50"], in_channels: int, in_stack_depth: int,
                  stem_kernel_size: Sequence[int] = (5, 4, 4), stem_stride: Sequence[int] = (5, 4, 4), embedding_dim: int = 768,
                  projection_dim: int = 128, drop_path_rate: float = 0.0, pretrained: bool = False,
@@ -113,38 +111,6 @@ class ContrastiveEncoder(nn.Module):
         enc.head = head
         self.encoder = enc
         self.projection = nn.Sequential(core.tail.fc0, core.tail.bn1, nn.ReLU(inplace=True), core.tail.fc3, core.tail.bn4)
-
-    # ---- the engine's knobs live on the core
-    @property
-    def cfg(self):
-        return self._core.cfg
-
-    @property
-    def compute_dtype(self):
-        return self._core.compute_dtype
-
-    @compute_dtype.setter
-    def compute_dtype(self, v):
-        self._core.compute_dtype = v
-
-    @property
-    def grad_mode(self):
-        return self._core.grad_mode
-
-    @grad_mode.setter
-    def grad_mode(self, v):
-        self._core.grad_mode = v
-
-    def engine(self, ops=None):
-        return self._core.engine(ops)
-
-    def _apply(self, fn, *a, **k):
-        self._core._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def train(self, mode: bool = True):
-        self._core.train(mode)  # BatchNorm mode is read from the core by the engine
-        return super().train(mode)
 
     def forward(self, x: Tensor) -> tuple[Tensor, Tensor]:
         """(embedding [B, num_features], projection [B, projection_dim]) — encoder.py:138-154"""

@@ -16,36 +16,16 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
+from .flat import FlatEngine, engine_apply
 
-class Engine:
+
+class Engine(FlatEngine):
+    name = "Unet3d"
+
     def __init__(self, model, ops=None):
         if ops is None:
-            from . import ops as hip_ops
-
-            ops = hip_ops
-        self.ops = ops
-        self.model = model
-        params = list(model.parameters())
-        self.device = params[0].device
-        order = self._param_order()
-        assert len(order) == len(params) and len({id(p) for p in order}) == len(order)
-        offs, off = [], 0
-        for p in order:
-            offs.append(off)
-            off += (p.numel() + 3) // 4 * 4  # every slice 16-byte aligned
-        self.flat = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.grad_of = {}
-        with torch.no_grad():
-            for p, o in zip(order, offs):
-                v = self.flat[o : o + p.numel()].view(p.shape)
-                v.copy_(p.detach().to(torch.float32))
-                p.data = v
-                self.grad_of[id(p)] = self.flat_grad[o : o + p.numel()].view(p.shape)
-        self.order, self.offsets, self.numel = order, offs, sum(p.numel() for p in order)
-        self.bucket_bounds = self._bucket_bounds()
-        self.on_bucket_ready = None  # callable(bucket_index) set by viscy_amd.parallel
-        self._pending_bwd = 0        # forwards of the current step whose backward has not run yet
+            from . import ops
+        super().__init__(model, ops)
 
     # ------------------------------------------------------------------ parameter ordering (backward order)
     @staticmethod
@@ -74,25 +54,6 @@ class Engine:
         ps += self._conv_params(m._downsamples[0]) + self._block_params(m._encoder_blocks[0][0]) + self._conv_params(m.inconv)
         self._bucket_marks.append(len(ps))  # bucket 2 = encoder level 0 + inconv
         return ps
-
-    def _bucket_bounds(self):
-        b = []
-        for i in range(len(self._bucket_marks) - 1):
-            lo = self.offsets[self._bucket_marks[i]]
-            hi_idx = self._bucket_marks[i + 1]
-            hi = self.offsets[hi_idx] if hi_idx < len(self.offsets) else self.flat.numel()
-            b.append((lo, hi))
-        return b
-
-    def g(self, p) -> Tensor:
-        return self.grad_of[id(p)]
-
-    def trainable_numel(self) -> int:
-        return self.flat.numel()
-
-    def attach_grads(self) -> None:
-        for p in self.order:
-            p.grad = self.grad_of[id(p)]
 
     # ------------------------------------------------------------------ building blocks
     def _block_fwd(self, db, inp, icoff, cin, out, ocoff, cout, grid, dt, training, save):
@@ -177,18 +138,9 @@ class Engine:
         y = ops.c3_from_cl(yc, B, (D, H, W))
         sv = None
         if need_bwd:
-            self._pending_bwd += 1
+            self._count_forward()
             sv = dict(dt=dt, training=training, grids=grids, h0=h0, es=es, cats=cats, ds=ds_, enc=enc_sv, bot=bot_sv, dec=dec_sv)
         return y, sv
-
-    def backward(self, sv, dout: Tensor) -> None:
-        """accumulates the parameter gradients into the flat gradient buffer (the input stack never requires grad);
-        ``on_bucket_ready(i)`` fires as bucket i completes, during the last outstanding backward of the step only"""
-        last = self._pending_bwd <= 1
-        self._pending_bwd = max(self._pending_bwd - 1, 0)
-        for i in self.backward_stages(sv, dout):
-            if last and self.on_bucket_ready:
-                self.on_bucket_ready(i)
 
     def backward_stages(self, sv, dout: Tensor):
         ops, m = self.ops, self.model
@@ -236,41 +188,5 @@ class Engine:
         yield 2
 
 
-class _Unet3dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, dt, need_bwd, *params):
-        eng = model.engine()
-        out, sv = eng.forward(x, dt, need_bwd)
-        ctx.model, ctx.sv = model, sv
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        model, sv = ctx.model, ctx.sv
-        if sv is None:
-            raise RuntimeError("viscy_amd.Unet3d: backward called but the forward ran without gradient bookkeeping")
-        eng = model.engine()
-        ctx.sv = None
-        if model.grad_mode == "flat":
-            eng.backward(sv, dout)
-            return (None, None, None, None) + tuple(None for _ in eng.order)
-        saved = eng.flat_grad  # autograd mode: compute into a zeroed flat buffer and hand views back to autograd
-        eng.flat_grad = eng.ops.zeros(saved.numel(), device=saved.device) if hasattr(eng.ops, "zeros") else torch.zeros_like(saved)
-        old = eng.grad_of
-        eng.grad_of = {id(p): eng.flat_grad[o : o + p.numel()].view(p.shape) for p, o in zip(eng.order, eng.offsets)}
-        try:
-            eng.backward(sv, dout)
-            grads = tuple(eng.grad_of[id(p)] if p.requires_grad else None for p in eng.order)
-        finally:
-            eng.flat_grad, eng.grad_of = saved, old
-        return (None, None, None, None) + grads
-
-
 def unet3d_apply(model, x: Tensor) -> Tensor:
-    eng = model.engine()
-    dt = model._resolve_dtype()
-    if model.grad_mode == "flat":
-        eng.attach_grads()
-    need_bwd = torch.is_grad_enabled() and any(p.requires_grad for p in eng.order)
-    with torch.autocast("cuda", enabled=False):
-        return _Unet3dFn.apply(x.float().contiguous(), model, dt, need_bwd, *eng.order)
+    return engine_apply(model, x.float().contiguous())

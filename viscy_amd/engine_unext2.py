@@ -23,6 +23,7 @@ from torch import Tensor
 
 from . import _lib as L
 from . import ops as hip_ops
+from .flat import FlatEngine, engine_apply
 
 
 class _BlockW:
@@ -123,43 +124,21 @@ class _ZeroArena:
         return self._zeros(*shape)
 
 
-class Engine:
+class Engine(FlatEngine):
+    name = "UNeXt2"
+
     def __init__(self, model, ops=None):
-        self.ops = hip_ops if ops is None else ops
-        self._hip = self.ops is hip_ops  # the HIP backend: the only one that has the library's flags and fused GRN-MLP passes
-        self._mlp_flag = 0               # `mlp_fused` as read by the forward in flight (0 on any other backend)
-        self.model = model
+        ops = hip_ops if ops is None else ops
+        self._hip = ops is hip_ops  # the HIP backend: the only one that has the library's flags and fused GRN-MLP passes
+        self._mlp_flag = 0          # `mlp_fused` as read by the forward in flight (0 on any other backend)
         self.cfg = model.cfg
         self._zeros4c = {}       # C -> zeros(4C): the identity GRN of ConvNeXt-V1 blocks
         self._dp_inject = None   # tests: list of per-sample branch scales [B], consumed in forward block order
         self._za = None          # zero arena of the pass in flight
         self._za_need = {}       # (pass, B, H, W) -> fp32 elements the pass took last time
-        params = list(model.parameters())
-        self.device = params[0].device
-        # ---- flat parameter / gradient buffers, reverse forward order (head first, stem last)
-        order = self._param_order()
-        assert len(order) == len(params) and len({id(p) for p in order}) == len(order)
-        total = sum(p.numel() for p in order)
-        # keep every slice 16-byte aligned
-        offs, off = [], 0
-        for p in order:
-            offs.append(off)
-            off += (p.numel() + 3) // 4 * 4
-        self.flat = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.grad_of = {}
-        with torch.no_grad():
-            for p, o in zip(order, offs):
-                v = self.flat[o : o + p.numel()].view(p.shape)
-                v.copy_(p.detach().to(torch.float32))
-                p.data = v
-                self.grad_of[id(p)] = self.flat_grad[o : o + p.numel()].view(p.shape)
-        self.order, self.offsets, self.numel = order, offs, total
-        self.bucket_bounds = self._bucket_bounds()
-        self.on_bucket_ready = None  # callable(bucket_index) set by viscy_amd.parallel
-        self._pending_bwd = 0        # forwards of the current step whose backward has not run yet
         self._prepared_for = None
         self.W = None
+        super().__init__(model, ops)  # flat buffers in reverse forward order (head first, stem last)
 
     # ------------------------------------------------------------------ parameter ordering
     def _stage_params_rev(self, stage):
@@ -204,18 +183,6 @@ class Engine:
         self._bucket_marks.append(len(ps))  # bucket 2 = encoder stages 1, 0 + stem
         return ps
 
-    def _bucket_bounds(self):
-        b = []
-        for i in range(len(self._bucket_marks) - 1):
-            lo = self.offsets[self._bucket_marks[i]]
-            hi_idx = self._bucket_marks[i + 1]
-            hi = self.offsets[hi_idx] if hi_idx < len(self.offsets) else self.flat.numel()
-            b.append((lo, hi))
-        return b
-
-    def g(self, p) -> Tensor:
-        return self.grad_of[id(p)]
-
     def encoder_frozen(self) -> bool:
         """``model.encoder.requires_grad_(False)`` (cytoland engine.py:204-206, the FCMAE fine-tuning recipe): every
         parameter from the encoder bucket on (encoder stages + stem: the tail of the flat buffer) is frozen — the backward
@@ -230,10 +197,6 @@ class Engine:
 
     def trainable_numel(self) -> int:
         return self.offsets[self._bucket_marks[1]] if self.encoder_frozen() else self.flat.numel()
-
-    def attach_grads(self) -> None:
-        for p in self.order:
-            p.grad = self.grad_of[id(p)]
 
     # ------------------------------------------------------------------ weight preparation
     def _prep_block(self, blk, dt, need_bwd):
@@ -688,7 +651,7 @@ class Engine:
         # self.W, and the backward of THIS forward must still see its own transposed weights
         sv = {"shape": (B, H, Wd), "dt": dt, "masked": masks is not None, "W": W} if need_bwd else None
         if need_bwd:
-            self._pending_bwd += 1
+            self._count_forward()
         # ---- stem: patch gather + projection GEMM, then encoder stem_1 LayerNorm2d
         stem_W, stem_b = (W["stem2d_W"], W["stem2d_b"]) if flat_stem else (W["stem_W"], W["stem_b"])
         skern = (1 if flat_stem else kz, ky, kx)
@@ -930,17 +893,6 @@ class Engine:
         return d
 
     # ------------------------------------------------------------------ backward
-    def backward(self, sv, dout: Tensor) -> None:
-        """Accumulates parameter gradients into the flat gradient buffer (no input gradient:
-        the image stack never requires grad on this path).  ``on_bucket_ready(i)`` fires as bucket i completes — but only
-        during the LAST outstanding backward of the step: with several forwards per step (CombinedLoader batches, DynaCLR
-        with unpaired forwards) an earlier backward leaves buckets that later ones still accumulate into."""
-        last = self._pending_bwd <= 1
-        self._pending_bwd = max(self._pending_bwd - 1, 0)
-        for i in self.backward_stages(sv, dout):
-            if last and self.on_bucket_ready:
-                self.on_bucket_ready(i)
-
     def backward_stages(self, sv, dout: Tensor):
         """Generator form of the backward schedule: yields the bucket index (0 = head + decoder, 1 = encoder stages 3-2,
         2 = stages 1-0 + stem) right after the last launch that writes into that bucket of the flat gradient buffer.
@@ -1069,46 +1021,6 @@ class Engine:
         yield k
         self.ops.batch_open()
 
-# ------------------------------------------------------------------------------------------------
-class _UNeXt2Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, dt, need_bwd, masks, bn_groups, *params):
-        eng = model.engine()
-        out, sv = eng.forward(x, dt, need_bwd, masks, bn_groups)
-        ctx.model, ctx.sv = model, sv
-        return out
-
-    @staticmethod
-    def backward(ctx, *douts):
-        dout = douts[0] if len(douts) == 1 else douts  # the embedding tail returns (embedding, projection)
-        model, sv = ctx.model, ctx.sv
-        if sv is None:
-            raise RuntimeError("viscy_amd.UNeXt2: backward called but the forward ran without gradient bookkeeping")
-        eng = model.engine()
-        ctx.sv = None
-        if model.grad_mode == "flat":
-            eng.backward(sv, dout)
-            return (None, None, None, None, None, None) + tuple(None for _ in eng.order)
-        # autograd mode: compute into a zeroed flat buffer and hand views back to autograd
-        saved = eng.flat_grad
-        eng.flat_grad = torch.zeros_like(saved)
-        old = eng.grad_of
-        eng.grad_of = {}
-        for p, off in zip(eng.order, eng.offsets):
-            eng.grad_of[id(p)] = eng.flat_grad[off : off + p.numel()].view(p.shape)
-        try:
-            eng.backward(sv, dout)
-            grads = tuple(eng.grad_of[id(p)] if p.requires_grad else None for p in eng.order)
-        finally:
-            eng.flat_grad, eng.grad_of = saved, old
-        return (None, None, None, None, None, None) + grads
-
 
 def unext2_apply(model, x: Tensor, masks=None, bn_groups: int = 1) -> Tensor:
-    eng = model.engine()
-    dt = model._resolve_dtype()
-    if model.grad_mode == "flat":
-        eng.attach_grads()
-    need_bwd = torch.is_grad_enabled() and any(p.requires_grad for p in eng.order)
-    with torch.autocast("cuda", enabled=False):
-        return _UNeXt2Fn.apply(x.float(), model, dt, need_bwd, masks, bn_groups, *eng.order)
+    return engine_apply(model, x.float(), masks, bn_groups)

@@ -25,6 +25,7 @@ from typing import Sequence
 import torch
 from torch import Tensor, nn
 
+from .flat import CoreProxy
 from .unext2 import _Conv, _Core, _Holder
 
 
@@ -116,7 +117,7 @@ def stage_row_maps(unmasked: Tensor, shapes, kept_cells: int):
     return out
 
 
-class FullyConvolutionalMAE(nn.Module):
+class FullyConvolutionalMAE(CoreProxy, nn.Module):
     def __init__(self, in_channels: int, out_channels: int, encoder_blocks: Sequence[int] = (3, 3, 9, 3),
                  dims: Sequence[int] = (96, 192, 384, 768), encoder_drop_path_rate: float = 0.0,
                  stem_kernel_size: Sequence[int] = (5, 4, 4), in_stack_depth: int = 5, decoder_conv_blocks: int = 1,
@@ -149,38 +150,6 @@ class FullyConvolutionalMAE(nn.Module):
         self.pretraining = pretraining
         # fcmae.py:26-37 `_init_weights` over the encoder: trunc-normal Conv3d? no — Conv2d / Linear only; the stem Conv3d keeps
         # torch's default init (already applied by the core)
-
-    # ---- the engine's knobs live on the core
-    @property
-    def cfg(self):
-        return self._core.cfg
-
-    @property
-    def compute_dtype(self):
-        return self._core.compute_dtype
-
-    @compute_dtype.setter
-    def compute_dtype(self, v):
-        self._core.compute_dtype = v
-
-    @property
-    def grad_mode(self):
-        return self._core.grad_mode
-
-    @grad_mode.setter
-    def grad_mode(self, v):
-        self._core.grad_mode = v
-
-    def engine(self, ops=None):
-        return self._core.engine(ops)
-
-    def _apply(self, fn, *a, **k):
-        self._core._engine = None  # parameter storage moves: flat views must be rebuilt
-        return super()._apply(fn, *a, **k)
-
-    def train(self, mode: bool = True):
-        self._core.train(mode)  # stochastic depth is active in training mode only; the engine reads the core's flag
-        return super().train(mode)
 
     @property
     def total_stride(self) -> int:

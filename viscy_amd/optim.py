@@ -33,7 +33,7 @@ def warmup_cosine_lambda(step: int, warmup_steps: int, t_total: int, warmup_mult
 
 
 class FlatAdamW:
-    """AdamW over ``engine.flat`` / ``engine.flat_grad`` (see viscy_amd.engine_unext2.Engine)."""
+    """AdamW over ``engine.flat`` / ``engine.flat_grad`` (a ``viscy_amd.flat.FlatEngine``)."""
 
     def __init__(self, engine, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
                  schedule: str = "Constant", warmup_steps: int = 0, t_total: int = 0, warmup_multiplier: float = 0.0,
@@ -45,7 +45,7 @@ class FlatAdamW:
         dev = engine.flat.device
         # a frozen encoder (VSUNet / FcmaeUNet freeze_encoder=True: engine.py:204-206) sits at the tail of the flat buffer
         # (the order is head, decoder, encoder, stem): the fused launch then covers the trainable prefix only
-        self.n_active = engine.trainable_numel() if hasattr(engine, "trainable_numel") else engine.flat.numel()
+        self.n_active = engine.trainable_numel()
         self.m = torch.zeros(self.n_active, dtype=torch.float32, device=dev)
         self.v = torch.zeros(self.n_active, dtype=torch.float32, device=dev)
         self.t = 0                 # host mirror of the device step counter (logging, checkpoints)
@@ -68,8 +68,7 @@ class FlatAdamW:
 
     def zero_grad(self) -> None:
         self.ops.fill_(self.engine.flat_grad, 0.0)  # vsx_fill_f32 (no ATen launch in the captured step)
-        if hasattr(self.engine, "_pending_bwd"):
-            self.engine._pending_bwd = 0  # a new step: no forward of it is waiting for its backward yet
+        self.engine.reset_pending()  # a new step: no forward of it is waiting for its backward yet
 
     def host_prepare(self) -> None:
         """host half of a step: advance the mirror counter; upload the schedule CONSTANTS if one of them was changed since

@@ -56,7 +56,7 @@ class FlatDataParallel:
             w.wait()
         self.works.clear()
         self._reduced.clear()
-        self.engine._pending_bwd = 0
+        self.engine.reset_pending()
 
     def all_reduce_mean(self, t: torch.Tensor) -> torch.Tensor:
         """``self.log(..., sync_dist=True)`` equivalent for scalars (engine.py:294-303 of the reference)."""

@@ -126,7 +126,7 @@ class TrainStep:
 
         with quiet():
             out, sv = eng.forward(self.x.float(), dt, True)
-            eng._pending_bwd = 0  # this driver runs the backward itself
+            eng.reset_pending()  # this driver runs the backward itself
             loss, dout = self._loss_and_grad(out)
             self.loss = loss.detach()
             del out

@@ -19,7 +19,7 @@ from __future__ import annotations
 import torch
 from torch import Tensor, nn
 
-from . import _lib as L
+from .flat import NativeModule
 
 
 def _fnet_weights_init(m: nn.Module) -> None:
@@ -56,7 +56,7 @@ class _Bottleneck(nn.Module):
         self.block = _DoubleBlock(c, c)
 
 
-class Unet3d(nn.Module):
+class Unet3d(NativeModule, nn.Module):
     """MI355X-native FNet3D (see module docstring).  ``compute_dtype``: None -> bf16 under ``torch.autocast(bfloat16)``, fp32
     otherwise; or force ``torch.bfloat16`` / ``torch.float32``.  All of D, H and W must be divisible by ``2**depth``."""
 
@@ -80,9 +80,6 @@ class Unet3d(nn.Module):
         self.outconv = nn.Conv3d(dims[0], out_channels, 3, padding=1)
         self.in_stack_depth = in_stack_depth
         self.out_stack_depth = in_stack_depth
-        self.compute_dtype: torch.dtype | None = None
-        self.grad_mode = "autograd"  # or "flat": gradients are written straight into the flat buffer
-        self._engine = None
         self.apply(_fnet_weights_init)
 
     @property
@@ -90,39 +87,21 @@ class Unet3d(nn.Module):
         """number of spatial downsampling stages"""
         return len(self._encoder_blocks)
 
-    def _resolve_dtype(self) -> torch.dtype:
-        want = self.compute_dtype
-        if want is None:
-            want = torch.bfloat16 if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16 else torch.float32
-        return want
-
     def check_input(self, x: Tensor) -> None:
         for name, size in zip(("D", "H", "W"), x.shape[2:]):
             if size % self._divisor != 0:
                 raise ValueError(f"Spatial dim {name}={size} must be divisible by {self._divisor} (2^{self.num_blocks} levels).")
 
-    def engine(self, ops=None):
+    def _engine_class(self):
         from .engine_unet3d import Engine
 
-        dev = self.inconv.weight.device
-        if self._engine is None or self._engine.device != dev or (ops is not None and self._engine.ops is not ops):
-            self._engine = Engine(self, ops)
-        return self._engine
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None  # parameter storage moves: flat views must be rebuilt
-        return super()._apply(fn, *a, **k)
+        return Engine
 
     def forward(self, x: Tensor) -> Tensor:
         if x.ndim != 5:
             raise ValueError(f"Expected input with 5 dimensions (B, C, D, H, W), got {tuple(x.shape)}")
         self.check_input(x)
-        if not x.is_cuda:
-            raise RuntimeError(
-                f"viscy_amd.{type(self).__name__} runs on MI355X HIP kernels only (no CPU / eager fallback): move the model "
-                "and the input to a 'cuda' (ROCm) device"
-            )
-        L.lib()  # raises loudly when libvsx.so is missing
+        self._require_hip(x)
         from .engine_unet3d import unet3d_apply
 
         return unet3d_apply(self, x)

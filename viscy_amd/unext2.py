@@ -28,7 +28,7 @@ from typing import Literal
 import torch
 from torch import Tensor, nn
 
-from . import _lib as L
+from .flat import NativeModule
 
 CONVNEXTV2_CFGS = {  # timm convnextv2_* (depths, dims, conv_mlp)
     "convnextv2_atto": ((2, 2, 6, 2), (40, 80, 160, 320), True),
@@ -203,7 +203,7 @@ def _icnr_(weight: Tensor, scale: int) -> None:
 
 
 # ------------------------------------------------------------------------------------------------
-class _Core(nn.Module):
+class _Core(NativeModule, nn.Module):
     """Shared machinery of the ConvNeXt-V2 U-Net family on this path (UNeXt2, the dense FCMAE U-Net): parameter tree in the
     engine's naming, flat-buffer engine, HIP-only forward."""
 
@@ -254,9 +254,6 @@ class _Core(nn.Module):
         else:
             self.head = _ShuffleHead()
         self.out_stack_depth = out_stack_depth
-        self.compute_dtype: torch.dtype | None = None
-        self.grad_mode = "autograd"  # or "flat": gradients are written straight into the flat buffer
-        self._engine = None
         self.reset_parameters()
 
     # ---- reference-compatible initialisation (timm _init_weights, MONAI normal_init, ICNR, torch Conv3d default)
@@ -301,33 +298,13 @@ class _Core(nn.Module):
             widths += [dec[i] // 4 + skips[i] for i in range(len(skips))] + [c for c in dec if c not in (4, 8)]
         return all(w % 8 == 0 for w in widths)
 
-    def _resolve_dtype(self) -> torch.dtype:
-        want = self.compute_dtype
-        if want is None:
-            want = torch.bfloat16 if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16 else torch.float32
-        if want == torch.bfloat16 and not self._bf16_ok():
-            return torch.float32  # e.g. convnextv2_atto: exact fp32 kernels instead of failing on a 60-channel row
-        return want
-
-    def engine(self, ops=None):
+    def _engine_class(self):
         from .engine_unext2 import Engine
 
-        dev = self.stem.conv.weight.device
-        if self._engine is None or self._engine.device != dev or (ops is not None and self._engine.ops is not ops):
-            self._engine = Engine(self, ops)
-        return self._engine
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None  # parameter storage moves: flat views must be rebuilt
-        return super()._apply(fn, *a, **k)
+        return Engine
 
     def forward(self, x: Tensor, masks=None, bn_groups: int = 1) -> Tensor:
-        if not x.is_cuda:
-            raise RuntimeError(
-                f"viscy_amd.{type(self).__name__} runs on MI355X HIP kernels only (no CPU / eager fallback): move the model "
-                "and the input to a 'cuda' (ROCm) device"
-            )
-        L.lib()  # raises loudly when libvsx.so is missing
+        self._require_hip(x)
         from .engine_unext2 import unext2_apply
 
         return unext2_apply(self, x, masks, bn_groups)
