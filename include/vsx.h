@@ -301,6 +301,16 @@ int32_t vsx_ntxent_fwd(const float* E, const int32_t* labels, float* En, float* 
     int32_t N, int32_t D, float temperature, float beta, vsx_stream_t stream);
 int32_t vsx_ntxent_bwd(const float* dS, const float* En, const float* inv, const float* acc, const float* gout, float* dE,
     int32_t N, int32_t D, vsx_stream_t stream);
+/* torch.nn.TripletMarginLoss(margin, p = 2, eps, swap = False), the default loss of dynaclr.engine.ContrastiveModule
+ * (engine.py:39-41), with the per-row similarities its _log_metrics reports (engine.py:135-146).  A, P, N [B, D] fp32.
+ * rows [B, 5] = {d_ap, d_an, hinge, cos_ap, cos_an} per row: d = F.pairwise_distance (eps added to the difference),
+ * hinge = max(d_ap - d_an + margin, 0), cos = F.cosine_similarity.  acc [6] = {loss, mean cos_ap, mean d_ap, mean cos_an,
+ * mean d_an, share of rows with hinge > 0}, summed in a fixed order (bit-identical from run to run).  reduction: 0 = mean,
+ * 1 = sum.  vsx_triplet_bwd: dA, dP, dN [B, D] = gout[0] * d loss / d (A, P, N); rows without hinge get exact zeros. */
+int32_t vsx_triplet_fwd(const float* A, const float* P, const float* N, float* rows, float* acc, int32_t B, int32_t D,
+    float margin, float eps, int32_t reduction, vsx_stream_t stream);
+int32_t vsx_triplet_bwd(const float* A, const float* P, const float* N, const float* rows, const float* gout, float* dA,
+    float* dP, float* dN, int32_t B, int32_t D, float margin, float eps, int32_t reduction, vsx_stream_t stream);
 
 /* K13 (norm+act) + K14: MONAI Convolution ADN (InstanceNorm3d eps 1e-5 → PReLU) → nn.Conv3d(mid, 4*out, 1) → transpose /
  * nn.PixelShuffle(2) / transpose (viscy_models/components/heads.py:617-625,638-641).  U: [B,H2,W2,Z,Cmid] conv output;

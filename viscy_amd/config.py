@@ -43,6 +43,8 @@ CLASS_MAP = {
     "viscy_models.contrastive.encoder.ContrastiveEncoder": "viscy_amd.contrastive.ContrastiveEncoder",
     "viscy_models.contrastive.loss.NTXentLoss": "viscy_amd.contrastive.NTXentLoss",
     "viscy_models.contrastive.loss.NTXentHCL": "viscy_amd.contrastive.NTXentHCL",
+    "torch.nn.TripletMarginLoss": "viscy_amd.contrastive.TripletMarginLoss",  # dynaclr.engine.ContrastiveModule's default loss
+    "torch.nn.modules.loss.TripletMarginLoss": "viscy_amd.contrastive.TripletMarginLoss",
     "viscy_models.unet.UNeXt2": "viscy_amd.unext2.UNeXt2",
     "viscy_models.unet.unext2.UNeXt2": "viscy_amd.unext2.UNeXt2",
     "viscy_models.unet.FullyConvolutionalMAE": "viscy_amd.fcmae.FullyConvolutionalMAE",

@@ -2,11 +2,14 @@
 
   * ``viscy_models.contrastive.ContrastiveEncoder``  (/root/reference/packages/viscy-models/src/viscy_models/contrastive/encoder.py:52-154)
   * ``viscy_models.contrastive.loss.NTXentLoss`` / ``NTXentHCL``  (.../contrastive/loss.py:20-186)
-  * the NT-Xent branch of ``dynaclr.engine.ContrastiveModule``  (/root/reference/applications/dynaclr/src/dynaclr/engine.py:33-347)
+  * ``torch.nn.TripletMarginLoss`` (p = 2, no swap), the default ``loss_function`` of the reference's module
+  * both training branches of ``dynaclr.engine.ContrastiveModule``: triplet (its default) and NT-Xent
+    (applications/dynaclr/src/dynaclr/engine.py:33-347)
 
 The trunk is the same ConvNeXt kernel schedule as the UNeXt2 encoder (``viscy_amd.engine_unext2``: stem patch GEMM, depthwise
 7x7, LayerNorm, fc1 / GELU / GRN / fc2 GEMMs, 2x2 downsampling GEMMs); behind it ``vsx_avgpool_rows_*``, the LayerNorm kernel,
-two small fp32 GEMMs and ``vsx_bn1d_*`` produce ``(embedding, projection)``; ``vsx_ntxent_*`` is the loss.  Same constructor
+two small fp32 GEMMs and ``vsx_bn1d_*`` produce ``(embedding, projection)``; ``vsx_ntxent_*`` / ``vsx_triplet_*`` are the
+losses.  Same constructor
 keywords and ``state_dict()`` keys as the reference (timm names: ``stem.conv``, ``encoder.stem.1``,
 ``encoder.stages.i.{downsample.{0,1},blocks.j.{[gamma,]conv_dw,norm,mlp.fc1,[mlp.grn,]mlp.fc2}}``, ``encoder.head.norm``,
 ``projection.{0,1,3,4}`` incl. the BatchNorm buffers), parameters shared with the flat-buffer engine so the fused AdamW and
@@ -16,6 +19,10 @@ Built: ``backbone="convnext_tiny"`` (V1 blocks: layer scale ``gamma`` folded int
 ``_unfold``, identity GRN) and ``"convnextv2_tiny"`` (GRN blocks); ``resnet50`` raises ``NotImplementedError``;
 ``pretrained`` must be False (no network here); ``drop_path_rate`` is timm's linear stochastic-depth schedule (training mode).  BatchNorm is per process
 under data parallelism, as in the reference's default (no SyncBatchNorm in its recipes' trainer sections).
+
+Not built: ``TripletMarginLoss`` with ``swap=True``, ``p != 2`` or ``reduction="none"``; ``nn.CosineEmbeddingLoss``; the
+negative-pair matrices that the reference's ``_log_metrics`` adds for NT-Xent; auxiliary heads, image / PCA logging,
+``freeze_backbone``.
 """
 
 from __future__ import annotations
@@ -140,6 +147,27 @@ class _NTXentFn(torch.autograd.Function):
         return O.ntxent_bwd(ctx.saved, ctx.acc, gout.contiguous().float()).to(ctx.in_dtype), None, None, None
 
 
+class _TripletFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchor: Tensor, positive: Tensor, negative: Tensor, margin: float, eps: float, reduction: str):
+        from . import ops as O
+
+        a, p_, n = (t.contiguous().float() for t in (anchor, positive, negative))
+        rows, acc = O.triplet_fwd(a, p_, n, margin, eps, reduction)
+        ctx.save_for_backward(a, p_, n, rows)
+        ctx.args, ctx.in_dtypes = (margin, eps, reduction), (anchor.dtype, positive.dtype, negative.dtype)
+        ctx.mark_non_differentiable(acc)
+        return acc[0].clone(), acc
+
+    @staticmethod
+    def backward(ctx, gout: Tensor, _gacc):
+        from . import ops as O
+
+        a, p_, n, rows = ctx.saved_tensors
+        grads = O.triplet_bwd(a, p_, n, rows, gout.contiguous().float(), *ctx.args)
+        return (*(g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)), None, None, None)
+
+
 def cosine_anneal(start: float, end: float, epoch: int, warmup_epochs: int) -> float:
     """viscy_models/schedule.py:8-33"""
     if epoch >= warmup_epochs:
@@ -185,12 +213,49 @@ class NTXentHCL(NTXentLoss):
         self.beta = beta
 
 
+class TripletMarginLoss(nn.Module):
+    """``torch.nn.TripletMarginLoss`` with its keywords and defaults: ``loss(anchor, positive, negative)`` on ``(B, D)``
+    tensors, mean or sum over rows of ``max(d(a, p) - d(a, n) + margin, 0)`` with ``d = F.pairwise_distance``.  Built: ``p = 2``,
+    ``swap=False``, ``reduction`` "mean" / "sum".  After a forward ``last_stats`` holds, detached, the six numbers that
+    ``vsx_triplet_fwd`` sums in a fixed order: {loss, mean cosine similarity (a, p), mean distance (a, p), mean cosine
+    similarity (a, n), mean distance (a, n), share of rows with a positive hinge}."""
+
+    def __init__(self, margin: float = 1.0, p: float = 2.0, eps: float = 1e-6, swap: bool = False, reduction: str = "mean"):
+        super().__init__()
+        if float(p) != 2.0:
+            raise NotImplementedError(f"TripletMarginLoss p={p}: viscy_amd builds the Euclidean distance (p=2)")
+        if swap:
+            raise NotImplementedError("TripletMarginLoss swap=True (distance swap) is not built")
+        if reduction == "none":
+            raise NotImplementedError('TripletMarginLoss reduction="none" is not built ("mean" / "sum")')
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        self.margin, self.p, self.eps, self.swap, self.reduction = float(margin), 2.0, float(eps), False, reduction
+        self.last_stats: Tensor | None = None
+
+    @classmethod
+    def from_torch(cls, loss: nn.TripletMarginLoss) -> "TripletMarginLoss":
+        return cls(margin=loss.margin, p=loss.p, eps=loss.eps, swap=loss.swap, reduction=loss.reduction)
+
+    def forward(self, anchor: Tensor, positive: Tensor, negative: Tensor) -> Tensor:
+        if anchor.ndim != 2 or positive.shape != anchor.shape or negative.shape != anchor.shape or anchor.numel() == 0:
+            raise ValueError("anchor, positive and negative must be non-empty (B, D) tensors of equal shape, got "
+                             f"{tuple(anchor.shape)} / {tuple(positive.shape)} / {tuple(negative.shape)}")
+        if not (anchor.is_cuda and positive.is_cuda and negative.is_cuda):
+            raise RuntimeError(f"viscy_amd.{type(self).__name__} runs on MI355X HIP kernels only (no CPU / eager fallback)")
+        L.lib()
+        loss, acc = _TripletFn.apply(anchor, positive, negative, self.margin, self.eps, self.reduction)
+        self.last_stats = acc.detach()
+        return loss
+
+
 # ------------------------------------------------------------------------------------------------ engine
 class ContrastiveModule(nn.Module):
-    """``dynaclr.engine.ContrastiveModule`` for the NT-Xent family (engine.py:33-347): ``training_step`` /
-    ``validation_step`` on a ``TripletSample`` (``anchor``, ``positive``), ``predict_step`` -> features / projections,
-    ``on_train_epoch_start`` temperature schedule, ``configure_optimizers`` -> fused flat AdamW.  Triplet / cosine-embedding
-    losses, auxiliary heads and image / PCA logging are not built."""
+    """``dynaclr.engine.ContrastiveModule`` (engine.py:33-347): ``training_step`` / ``validation_step`` on a ``TripletSample``
+    (``anchor``, ``positive`` and, for the triplet branch, ``negative``), ``predict_step`` -> features / projections,
+    ``on_train_epoch_start`` temperature schedule, ``configure_optimizers`` -> fused flat AdamW.  ``loss_function``: the
+    NT-Xent family (the default here) or ``TripletMarginLoss`` (the reference's default; a ``torch.nn.TripletMarginLoss``
+    instance is converted).  The cosine-embedding loss, auxiliary heads and image / PCA logging are not built."""
 
     def __init__(self, encoder: ContrastiveEncoder, loss_function: nn.Module | None = None, lr: float = 1e-3,
                  schedule: Literal["WarmupCosine", "Constant"] = "Constant", log_batches_per_epoch: int = 8,
@@ -200,16 +265,25 @@ class ContrastiveModule(nn.Module):
         if freeze_backbone:
             raise NotImplementedError("freeze_backbone is not built (the fused flat-buffer optimiser updates every parameter)")
         self.model = encoder
+        if isinstance(loss_function, nn.TripletMarginLoss):  # the reference's default / YAML class_path
+            loss_function = TripletMarginLoss.from_torch(loss_function)
         self.loss_function = loss_function if loss_function is not None else NTXentLoss()
-        if not isinstance(self.loss_function, NTXentLoss):
-            raise NotImplementedError(f"{type(self.loss_function).__name__}: viscy_amd builds the NT-Xent family of the DynaCLR losses")
+        if isinstance(self.loss_function, nn.CosineEmbeddingLoss):
+            raise NotImplementedError("CosineEmbeddingLoss is not built: the reference's non-NT-Xent branch calls loss(anchor, "
+                                      "positive, negative), which hands the negative projection to it as its `target`")
+        if not isinstance(self.loss_function, (NTXentLoss, TripletMarginLoss)):
+            raise NotImplementedError(f"{type(self.loss_function).__name__}: viscy_amd builds the NT-Xent family and "
+                                      "TripletMarginLoss of the DynaCLR losses")
+        self.triplet = isinstance(self.loss_function, TripletMarginLoss)
+        if self.triplet and gather_embeddings:
+            raise NotImplementedError("gather_embeddings widens the NT-Xent negatives; a triplet row has its own negative")
         self.lr, self.schedule = lr, schedule
         self.log_batches_per_epoch, self.log_samples_per_batch = log_batches_per_epoch, log_samples_per_batch
         self.example_input_array = torch.rand(*example_input_array_shape)
         # extension beyond the reference (BASELINE config 5): under torch.distributed the projections of all ranks are
         # all-gathered so that every anchor sees world * 2B - 2 negatives instead of 2B - 2; False = the reference's behaviour
         self.gather_embeddings = gather_embeddings
-        self.paired_forward = True  # False: two separate forwards, literally as the reference does
+        self.paired_forward = True  # False: separate forwards per view, literally as the reference does
         self.current_epoch = 0
         self._logging = True
         self.logged: dict[str, list] = {}
@@ -221,28 +295,59 @@ class ContrastiveModule(nn.Module):
             self.logged.setdefault(key, []).append(value.detach() if torch.is_tensor(value) else value)
 
     def make_train_step(self, optimizer, ddp=None, use_graph: bool = True):
-        """the whole contrastive step (zero-grad, two forwards, NT-Xent, backward, fused AdamW) as ONE hipGraph replay per batch
-        (``viscy_amd.step.TrainStep``); call ``step(anchor, positive) -> loss`` with fixed shapes"""
+        """the whole contrastive step (zero-grad, the forwards, the loss, backward, fused AdamW) as ONE hipGraph replay per batch
+        (``viscy_amd.step.TrainStep``); call ``step(anchor, positive) -> loss`` with fixed shapes, or, with a triplet loss,
+        ``step(anchor, positive, negative) -> loss``"""
         from .step import TrainStep
 
-        def loss_fn(anchor, positive):
+        def loss_fn(anchor, other):
+            batch = {"anchor": anchor, "positive": other}
+            if self.triplet:  # TrainStep carries two tensors: (positive, negative) travel stacked
+                batch = {"anchor": anchor, "positive": other[0], "negative": other[1]}
             was, self._logging = self._logging, False  # the captured tensors must not pile up in the log
             try:
-                return self._step({"anchor": anchor, "positive": positive}, "train")
+                return self._step(batch, "train")
             finally:
                 self._logging = was
 
-        return TrainStep(self.model, None, optimizer, ddp=ddp, use_graph=use_graph, loss_fn=loss_fn)
+        step = TrainStep(self.model, None, optimizer, ddp=ddp, use_graph=use_graph, loss_fn=loss_fn)
+        if self.triplet:
+            return lambda anchor, positive, negative: step(anchor, torch.stack((positive, negative)))
+        return step
 
     def on_train_epoch_start(self) -> None:
         if hasattr(self.loss_function, "step"):
             self.loss_function.step(self.current_epoch)
-        self._log("hparams/temperature", self.loss_function.temperature)
+        if hasattr(self.loss_function, "temperature"):
+            self._log("hparams/temperature", self.loss_function.temperature)
 
     def forward(self, x: Tensor) -> tuple[Tensor, Tensor]:
         return self.model(x)
 
+    def _step_triplet(self, batch: dict, stage: str) -> Tensor:
+        if "negative" not in batch:
+            raise KeyError("negative: the triplet branch needs batch['negative'] next to 'anchor' and 'positive'")
+        views = (batch["anchor"], batch["positive"], batch["negative"])
+        if self.paired_forward and views[0].shape == views[1].shape == views[2].shape:
+            # one trunk pass over [anchor; positive; negative]; BatchNorm statistics and running-statistics updates per view,
+            # in this order, as the reference's three calls make them (dynaclr/engine.py:265-266,276)
+            _, proj = self.model.forward_groups(torch.cat(views), 3)
+            projections = proj.chunk(3)
+        else:
+            projections = tuple(self(v)[1] for v in views)
+        loss = self.loss_function(*projections)
+        self._log(f"loss/{stage}", loss)
+        if self._logging:  # engine.py:135-146, from the sums the loss kernels formed anyway
+            st = self.loss_function.last_stats
+            self._log(f"metrics/cosine_similarity/positive/{stage}", st[1])
+            self._log(f"metrics/euclidean_distance/positive/{stage}", st[2])
+            self._log(f"metrics/cosine_similarity_negative/{stage}", st[3])
+            self._log(f"metrics/euclidean_distance_negative/{stage}", st[4])
+        return loss
+
     def _step(self, batch: dict, stage: str) -> Tensor:
+        if self.triplet:
+            return self._step_triplet(batch, stage)
         a, p_ = batch["anchor"], batch["positive"]
         if self.paired_forward and a.shape == p_.shape:
             # one trunk pass over [anchor; positive]; BatchNorm statistics stay per call (dynaclr/engine.py:265-266)

@@ -304,3 +304,136 @@ extern "C" int32_t vsx_ntxent_bwd(const float* dS, const float* En, const float*
   VSX_LAUNCH_CHECK();
   return 0;
 }
+
+// ------------------------------------------------------------------ TripletMarginLoss (p = 2, no swap)
+// nn.TripletMarginLoss(margin) on (anchor, positive, negative) [B, D], the default loss of dynaclr.engine.ContrastiveModule
+// (engine.py:39-41), plus the per-row cosine similarities its _log_metrics reports (engine.py:135-146).
+//   d_xy    = sqrt(sum_k (x_k - y_k + eps)^2)                          F.pairwise_distance (eps is added to the difference)
+//   hinge_i = max(d_ap - d_an + margin, 0)
+//   cos_xy  = <x, y> / (max(|x|, 1e-8) max(|y|, 1e-8))                 F.cosine_similarity
+#define TRIPLET_ROW 5  // floats per row of `rows`: d_ap, d_an, hinge, cos_ap, cos_an
+__device__ __forceinline__ float triplet_gap(float d_ap, float d_an, float margin) { return d_ap - d_an + margin; }
+
+struct TripletSums {
+  float dap, dan, ap, an, aa, pp, nn;
+  __device__ __forceinline__ void add(float a, float p, float n, float eps) {
+    const float u = (a - p) + eps, v = (a - n) + eps;
+    dap = fmaf(u, u, dap);
+    dan = fmaf(v, v, dan);
+    ap = fmaf(a, p, ap);
+    an = fmaf(a, n, an);
+    aa = fmaf(a, a, aa);
+    pp = fmaf(p, p, pp);
+    nn = fmaf(n, n, nn);
+  }
+};
+
+// one wave per row, four rows per workgroup; lanes stride over D (16-byte loads when `vec`: D % 4 == 0 and aligned bases),
+// seven wave butterflies (DPP / shuffles: no LDS, no atomics); lane 0 writes the row's five numbers
+__global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restrict__ A, const float* __restrict__ P,
+                                                           const float* __restrict__ N, float* __restrict__ rows, int B, int D,
+                                                           float margin, float eps, int vec) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= B) return;  // wave-uniform; nothing below synchronises across waves
+  const float *a = A + (size_t)i * D, *p = P + (size_t)i * D, *n = N + (size_t)i * D;
+  TripletSums s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int D4 = vec ? D >> 2 : 0;
+  for (int q = lane; q < D4; q += 64) {
+    const float4 va = ldvec<float>(a + 4 * q), vp = ldvec<float>(p + 4 * q), vn = ldvec<float>(n + 4 * q);
+    s.add(va.x, vp.x, vn.x, eps);
+    s.add(va.y, vp.y, vn.y, eps);
+    s.add(va.z, vp.z, vn.z, eps);
+    s.add(va.w, vp.w, vn.w, eps);
+  }
+  for (int k = 4 * D4 + lane; k < D; k += 64) s.add(a[k], p[k], n[k], eps);
+  const float d_ap = sqrtf(wave_sum(s.dap)), d_an = sqrtf(wave_sum(s.dan));
+  const float ap = wave_sum(s.ap), an = wave_sum(s.an);
+  const float na = fmaxf(sqrtf(wave_sum(s.aa)), 1e-8f), np = fmaxf(sqrtf(wave_sum(s.pp)), 1e-8f),
+              nn = fmaxf(sqrtf(wave_sum(s.nn)), 1e-8f);
+  if (lane == 0) {
+    float* r = rows + (size_t)i * TRIPLET_ROW;
+    r[0] = d_ap;
+    r[1] = d_an;
+    r[2] = fmaxf(triplet_gap(d_ap, d_an, margin), 0.f);
+    r[3] = ap / (na * np);
+    r[4] = an / (na * nn);
+  }
+}
+
+// acc = {loss, mean cos_ap, mean d_ap, mean cos_an, mean d_an, share of rows with hinge > 0};  loss = mean or sum of hinge.
+// ONE workgroup, a fixed order: thread t adds rows t, t + 256, ... in ascending order, then the 256 partial sums of each
+// quantity are combined by a binary tree in LDS (stride 128, 64, ... 1) — no atomics, the same bits in every run
+__global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __restrict__ rows, float* __restrict__ acc, int B,
+                                                               int sum_reduction) {
+  __shared__ float red[6][256];
+  const int t = threadIdx.x;
+  float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = t; i < B; i += 256) {
+    const float* r = rows + (size_t)i * TRIPLET_ROW;
+    v[0] += r[2];
+    v[1] += r[3];
+    v[2] += r[0];
+    v[3] += r[4];
+    v[4] += r[1];
+    v[5] += r[2] > 0.f ? 1.f : 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) red[q][t] = v[q];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int q = 0; q < 6; ++q) red[q][t] += red[q][t + o];
+    }
+    __syncthreads();
+  }
+  if (t < 6) acc[t] = (t == 0 && sum_reduction) ? red[0][0] : red[t][0] / (float)B;
+}
+
+// elementwise over [B, D].  s = gout (sum) or gout / B (mean).  Row with d_ap - d_an + margin > 0:
+//   dP = -s (a - p + eps) / d_ap,  dN = +s (a - n + eps) / d_an,  dA = -dP - dN;   a term whose distance is exactly 0
+// contributes 0 (torch's norm backward); every other row gets exact zeros
+__global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restrict__ A, const float* __restrict__ P,
+                                                          const float* __restrict__ N, const float* __restrict__ rows,
+                                                          const float* __restrict__ gout, float* __restrict__ dA,
+                                                          float* __restrict__ dP, float* __restrict__ dN, long total, int D,
+                                                          float margin, float eps, float scale) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const float* r = rows + (size_t)(idx / D) * TRIPLET_ROW;
+  const float d_ap = r[0], d_an = r[1];
+  float ga = 0.f, gp = 0.f, gn = 0.f;
+  if (triplet_gap(d_ap, d_an, margin) > 0.f) {
+    const float s = gout[0] * scale, a = A[idx];
+    if (d_ap > 0.f) gp = -s * ((a - P[idx]) + eps) / d_ap;
+    if (d_an > 0.f) gn = s * ((a - N[idx]) + eps) / d_an;
+    ga = -gp - gn;
+  }
+  dA[idx] = ga;
+  dP[idx] = gp;
+  dN[idx] = gn;
+}
+
+extern "C" int32_t vsx_triplet_fwd(const float* A, const float* P, const float* N, float* rows, float* acc, int32_t B, int32_t D,
+                                   float margin, float eps, int32_t reduction, vsx_stream_t stream) {
+  VSX_CHECK(A && P && N && rows && acc && B >= 1 && D >= 1, "vsx_triplet_fwd: bad arguments");
+  VSX_CHECK(reduction == 0 || reduction == 1, "vsx_triplet_fwd: unknown reduction %d (0 = mean, 1 = sum)", reduction);
+  hipStream_t s = (hipStream_t)stream;
+  const int vec = D % 4 == 0 && (((uintptr_t)A | (uintptr_t)P | (uintptr_t)N) & 15) == 0;
+  hipLaunchKernelGGL(triplet_rows_kernel, dim3(vsx_cdiv(B, 4)), dim3(256), 0, s, A, P, N, rows, B, D, margin, eps, vec);
+  hipLaunchKernelGGL(triplet_finalize_kernel, dim3(1), dim3(256), 0, s, rows, acc, B, reduction);
+  VSX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int32_t vsx_triplet_bwd(const float* A, const float* P, const float* N, const float* rows, const float* gout, float* dA,
+                                   float* dP, float* dN, int32_t B, int32_t D, float margin, float eps, int32_t reduction,
+                                   vsx_stream_t stream) {
+  VSX_CHECK(A && P && N && rows && gout && dA && dP && dN && B >= 1 && D >= 1, "vsx_triplet_bwd: bad arguments");
+  VSX_CHECK(reduction == 0 || reduction == 1, "vsx_triplet_bwd: unknown reduction %d (0 = mean, 1 = sum)", reduction);
+  const long total = (long)B * D;
+  VSX_CHECK(total / 256 < 0x7fffffffL, "vsx_triplet_bwd: %d x %d elements exceed one launch", B, D);
+  hipLaunchKernelGGL(triplet_bwd_kernel, dim3(vsx_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, A, P, N, rows, gout, dA, dP,
+                     dN, total, D, margin, eps, reduction == 1 ? 1.f : 1.f / (float)B);
+  VSX_LAUNCH_CHECK();
+  return 0;
+}

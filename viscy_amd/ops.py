@@ -775,6 +775,28 @@ def ntxent_bwd(saved, acc: Tensor, gout: Tensor) -> Tensor:
     return dE
 
 
+TRIPLET_REDUCTIONS = {"mean": 0, "sum": 1}  # the `reduction` argument of vsx_triplet_*
+
+
+def triplet_fwd(A: Tensor, P: Tensor, N: Tensor, margin: float, eps: float, reduction: str):
+    """rows [B, 5] = {d_ap, d_an, hinge, cos_ap, cos_an}, acc [6] = {loss, mean cos_ap, mean d_ap, mean cos_an, mean d_an,
+    share of rows with hinge > 0} (include/vsx.h)"""
+    B, D = A.shape
+    rows = torch.empty((B, 5), dtype=torch.float32, device=A.device)
+    acc = torch.empty(6, dtype=torch.float32, device=A.device)
+    check(lib().vsx_triplet_fwd(ptr(A), ptr(P), ptr(N), ptr(rows), ptr(acc), B, D, float(margin), float(eps),
+                                TRIPLET_REDUCTIONS[reduction], stream()), "triplet_fwd")
+    return rows, acc
+
+
+def triplet_bwd(A: Tensor, P: Tensor, N: Tensor, rows: Tensor, gout: Tensor, margin: float, eps: float, reduction: str):
+    B, D = A.shape
+    dA, dP, dN = torch.empty_like(A), torch.empty_like(A), torch.empty_like(A)
+    check(lib().vsx_triplet_bwd(ptr(A), ptr(P), ptr(N), ptr(rows), ptr(gout), ptr(dA), ptr(dP), ptr(dN), B, D, float(margin),
+                                float(eps), TRIPLET_REDUCTIONS[reduction], stream()), "triplet_bwd")
+    return dA, dP, dN
+
+
 def scale_rows_samples(x: Tensor, scale: Tensor, M: int, C: int, hw: int) -> Tensor:
     out = torch.empty_like(x)
     check(lib().vsx_scale_rows_samples(ptr(x), ptr(scale), ptr(out), M, C, hw, dtype_code(x.dtype), stream()), "scale_rows_samples")
