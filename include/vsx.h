@@ -633,6 +633,32 @@ int32_t vsx_sample_index(const float* wpool, const float* u, int32_t* idx, int32
 int32_t vsx_crop3d(const float* x, float* y, const int32_t* starts, int32_t B, int32_t C, int32_t Z, int32_t Y, int32_t X,
     int32_t cz, int32_t cy, int32_t cx, vsx_stream_t stream);
 
+/* Per-row order statistics by radix select (the quantiles of BatchedScaleIntensityRangePercentiles, _percentile_scale.py:59-68,
+ * without torch.quantile's sort and its 2^24-element limit).  x: rows contiguous rows of n fp32 values, any alignment of the
+ * row starts; ranks[nranks] (host array, 1 <= nranks <= 4, 0 <= rank < n <= 2^31 - 1): zero-based positions in the sorted row,
+ * the same for every row; out[rows][nranks] = exactly the element torch.sort(row).values[rank] holds (-0.0 / +0.0 may come
+ * back as either).  A row that holds a NaN yields NaN for all its ranks.  ws: caller-owned device scratch of
+ * vsx_row_select_ws_bytes(rows, nranks) bytes, initialised by the call.  Integer atomics only: bit-identical from run to run;
+ * 9 launches whatever the data, no allocation, synchronisation or device-to-host copy. */
+int64_t vsx_row_select_ws_bytes(int64_t rows, int32_t nranks);
+int32_t vsx_row_select(const float* x, float* out, void* ws, int64_t ws_bytes, int64_t rows, int64_t n, const int64_t* ranks,
+    int32_t nranks, vsx_stream_t stream);
+
+/* BatchedScaleIntensityRangePercentiles._normalize (_percentile_scale.py:78-90) on rows contiguous rows of n values with
+ * per-row bounds a_min / a_max [rows]:  y = (x - a_min) / (a_max - a_min); flags bit 0: then * (b_max - b_min) + b_min;
+ * bit 1 / bit 2: then clip below at b_min / above at b_max.  Where degenerate[row] != 0 (int32 [rows], the reference's
+ * batch-wide `(a_min == a_max).any()` expanded by the caller): y = x - a_min, + b_min with bit 3.  Every operation is rounded on
+ * its own (no contraction, IEEE division), so the result equals the reference's tensor expressions bit for bit. */
+int32_t vsx_percentile_scale(const float* x, float* y, const float* a_min, const float* a_max, const int32_t* degenerate,
+    int64_t rows, int64_t n, double b_min, double b_max, int32_t flags, vsx_stream_t stream);
+
+/* BatchedRandSpatialCrop's gather (_crop.py:98-125) followed by BatchedChannelWiseZReduction (_z_reduction.py:49-61) in one
+ * pass: y[b,c,0,yy,xx] over the window (cz,cy,cx) at starts[b] (int32 [B,3]; NULL = zeros), each start clamped into
+ * [0, dim - c] inside the kernel; mode[b] (int32 [B]) 0 = maximum over the window's Z (NaN propagates, as amax), 1 = its
+ * centre plane cz / 2.  Only the window is read. */
+int32_t vsx_crop_zreduce(const float* x, float* y, const int32_t* starts, const int32_t* mode, int32_t B, int32_t C, int32_t Z,
+    int32_t Y, int32_t X, int32_t cz, int32_t cy, int32_t cx, vsx_stream_t stream);
+
 /* K18 kornia warp_affine3d as used by BatchedRandAffined (viscy_transforms/_affine.py:33-47,358-393): trilinear (or
  * nearest) resampling; Minv[B][3][4] maps output-voxel to input-voxel coordinates (x, y, z order).
  * The kernel applies Minv as given; the caller folds kornia's align_corners convention into it (with align_corners=False — kornia's

@@ -174,6 +174,10 @@ _SIGS = {
     "vsx_crop_weights": (_I32, [_P, _P, _P] + [_I32] * 6 + [_P]),
     "vsx_sample_index": (_I32, [_P, _P, _P, _I32, _I64, _P]),
     "vsx_crop3d": (_I32, [_P, _P, _P] + [_I32] * 8 + [_P]),
+    "vsx_row_select_ws_bytes": (_I64, [_I64, _I32]),
+    "vsx_row_select": (_I32, [_P, _P, _P, _I64, _I64, _I64, C.POINTER(_I64), _I32, _P]),
+    "vsx_percentile_scale": (_I32, [_P] * 5 + [_I64, _I64, C.c_double, C.c_double, _I32, _P]),
+    "vsx_crop_zreduce": (_I32, [_P] * 4 + [_I32] * 8 + [_P]),
     "vsx_warp_affine3d": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vsx_warp_affine3d_roi": (_I32, [_P, _P, _P] + [_I32] * 12 + [_P]),
     "vsx_conv1d_axis": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I64, _I32, _P]),

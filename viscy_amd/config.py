@@ -57,7 +57,8 @@ CLASS_MAP = {
 for _t in ("NormalizeSampled", "MinMaxSampled", "RandWeightedCropd", "CenterSpatialCropd", "BatchedCenterSpatialCropd",
            "BatchedRandAffined", "BatchedRandAdjustContrastd", "BatchedRandScaleIntensityd", "BatchedRandGaussianNoised",
            "BatchedRandGaussianSmoothd", "BatchedRandFlipd", "BatchedRandWeightedCropd", "BatchedRandInvertIntensityd",
-           "BatchedStackChannelsd"):
+           "BatchedStackChannelsd", "BatchedScaleIntensityRangePercentiles", "BatchedScaleIntensityRangePercentilesd",
+           "BatchedRandSpatialCrop", "BatchedRandSpatialCropd", "BatchedChannelWiseZReduction", "BatchedChannelWiseZReductiond"):
     CLASS_MAP[f"viscy_transforms.{_t}"] = f"viscy_amd.transforms.{_t}"
 
 

@@ -848,3 +848,367 @@ class BatchedStackChannelsd:
 
     def __call__(self, sample: dict) -> dict:
         return {key: torch.cat([sample[ch] for ch in chans], dim=1) for key, chans in self.channel_map.items()}
+
+
+# ------------------------------------------------------------------------------------------------
+# DynaCLR bag-of-channels augmentations: percentile scaling (_percentile_scale.py), random crop (_crop.py:24-160) and
+# channel-wise Z-reduction (_z_reduction.py).  Device tensors go through csrc/boc_transforms.hip; CPU tensors (DataLoader
+# workers, the goldens) take the same lines in torch, as the normalisations above do.
+# ------------------------------------------------------------------------------------------------
+def _dev_ok(x: Tensor) -> bool:
+    """a batch the kernels of csrc/boc_transforms.hip take as it is (any row length: they handle their own alignment)"""
+    return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+
+
+def _need_dev(x: Tensor, what: str) -> None:
+    if x.is_cuda and not _dev_ok(x):
+        raise RuntimeError(f"{what} needs a contiguous float32 batch on the HIP device (no eager fallback for other layouts)")
+
+
+def quantile_ranks(q: float, n: int) -> tuple[int, int, float]:
+    """(lo, hi, w) of ``torch.quantile(row, q)`` on a row of ``n`` values, from the shape alone: the value is
+    ``lerp(sorted[lo], sorted[hi], w)``.  float32 throughout, as torch computes it for a float32 input:
+    r = float32(q) * (n - 1), lo = floor(r), hi = ceil(r), w = r - lo.  Above 2^24 elements (where torch.quantile refuses the
+    input) a float32 r can round past n - 1: both ranks are then held at n - 1."""
+    r = torch.tensor(q, dtype=torch.float32) * (n - 1)
+    lo = torch.floor(r)
+    w = float(r - lo)
+    return min(int(lo), n - 1), min(int(torch.ceil(r)), n - 1), w
+
+
+def row_select(x: Tensor, ranks: Sequence[int]) -> Tensor:
+    """(rows, len(ranks)) order statistics of a contiguous float32 (rows, n) device tensor: ``sort(row)[rank]`` exactly, by
+    radix select (``vsx_row_select``); NaN for every rank of a row that holds one."""
+    if not (_dev_ok(x) and x.ndim == 2):
+        raise RuntimeError("row_select needs a contiguous float32 (rows, n) tensor on the HIP device (no CPU fallback)")
+    rows, n = x.shape
+    rk = (L._I64 * len(ranks))(*[int(r) for r in ranks])
+    nbytes = lib().vsx_row_select_ws_bytes(rows, len(ranks))
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=x.device)
+    out = torch.empty((rows, len(ranks)), dtype=torch.float32, device=x.device)
+    check(lib().vsx_row_select(ptr(x), ptr(out), ptr(ws), nbytes, rows, n, rk, len(ranks), stream()), "row_select")
+    return out
+
+
+def percentile_bounds(rows2d: Tensor, q_low: float, q_high: float) -> tuple[Tensor, Tensor]:
+    """``torch.quantile(rows2d, [q_low, q_high], dim=1)`` of a (rows, n) device tensor without the sort: the four order
+    statistics from one ``row_select``, then the same lerp on the (rows,) results."""
+    n = rows2d.shape[1]
+    (l0, h0, w0), (l1, h1, w1) = quantile_ranks(q_low, n), quantile_ranks(q_high, n)
+    s = row_select(rows2d, (l0, h0, l1, h1))
+    a_min = s[:, 0].clone() if w0 == 0.0 else torch.lerp(s[:, 0], s[:, 1], w0)
+    a_max = s[:, 2].clone() if w1 == 0.0 else torch.lerp(s[:, 2], s[:, 3], w1)
+    return a_min, a_max
+
+
+def percentile_scale(x2d: Tensor, a_min: Tensor, a_max: Tensor, degenerate: Tensor, b_min: float | None, b_max: float | None,
+                     clip: bool) -> Tensor:
+    """the arithmetic of ``_normalize`` after the quantiles, one pass (``vsx_percentile_scale``): rows of ``x2d`` (rows, n)
+    with bounds ``a_min`` / ``a_max`` (rows,); ``degenerate`` (rows,) selects ``x - a_min (+ b_min)`` instead."""
+    if not (_dev_ok(x2d) and x2d.ndim == 2):
+        raise RuntimeError("percentile_scale needs a contiguous float32 (rows, n) tensor on the HIP device (no CPU fallback)")
+    if clip and b_min is None and b_max is None:
+        raise ValueError("clip=True needs b_min or b_max")  # torch.clip(None, None) refuses too
+    rows, n = x2d.shape
+    flags = (1 if (b_min is not None and b_max is not None) else 0) | (2 if (clip and b_min is not None) else 0) \
+        | (4 if (clip and b_max is not None) else 0) | (8 if b_min is not None else 0)
+    lo_d, hi_d = a_min.to(x2d.device, torch.float32).contiguous(), a_max.to(x2d.device, torch.float32).contiguous()
+    dg_d = degenerate.to(x2d.device, torch.int32).contiguous()
+    y = torch.empty_like(x2d)
+    check(lib().vsx_percentile_scale(ptr(x2d), ptr(y), ptr(lo_d), ptr(hi_d), ptr(dg_d), rows, n,
+                                     0.0 if b_min is None else float(b_min), 0.0 if b_max is None else float(b_max), flags,
+                                     stream()), "percentile_scale")
+    return y
+
+
+class BatchedScaleIntensityRangePercentiles:
+    """``viscy_transforms.BatchedScaleIntensityRangePercentiles`` (_percentile_scale.py:22-109): each sample of a
+    (B, C, Z, Y, X) batch — each (sample, channel) with ``channel_wise`` — is mapped from its [``lower``, ``upper``] percentile
+    range to [``b_min``, ``b_max``] (``relative``: to that share of the range), optionally clipped.  If any row of a call has
+    equal bounds, the whole call returns ``img - a_min (+ b_min)``, as the reference does (per channel with ``channel_wise``,
+    whose channels the reference normalises in separate calls).
+
+    On the device the percentiles are exact order statistics from a radix select (no sort, no 2^24-element limit) and the
+    degenerate case is a device flag the scale kernel reads: no host synchronisation, so the reference's
+    "Divide by zero (a_min == a_max)" warning is not issued there.  ``dtype`` is accepted and, as in the reference's
+    ``__call__``, not applied."""
+
+    def __init__(self, lower: float, upper: float, b_min: float | None, b_max: float | None, clip: bool = False,
+                 relative: bool = False, channel_wise: bool = False, dtype=None):
+        if lower < 0.0 or lower > 100.0:
+            raise ValueError("Percentiles must be in the range [0, 100]")
+        if upper < 0.0 or upper > 100.0:
+            raise ValueError("Percentiles must be in the range [0, 100]")
+        self.lower, self.upper, self.b_min, self.b_max = lower, upper, b_min, b_max
+        self.clip, self.relative, self.channel_wise, self.dtype = clip, relative, channel_wise, dtype
+
+    def _targets(self):
+        q_low, q_high = self.lower / 100.0, self.upper / 100.0
+        b_min, b_max = self.b_min, self.b_max
+        if self.relative:
+            if (self.b_min is None) or (self.b_max is None):
+                raise ValueError("If it is relative, b_min and b_max should not be None.")
+            b_min = ((self.b_max - self.b_min) * (q_low)) + self.b_min
+            b_max = ((self.b_max - self.b_min) * (q_high)) + self.b_min
+        return q_low, q_high, b_min, b_max
+
+    def _normalize_host(self, img: Tensor) -> Tensor:
+        from warnings import warn
+
+        q_low, q_high, b_min, b_max = self._targets()
+        batch = img.shape[0]
+        a_min, a_max = torch.quantile(img.reshape(batch, -1), torch.tensor([q_low, q_high], dtype=img.dtype, device=img.device),
+                                      dim=1).reshape(2, batch, 1, 1, 1, 1)
+        if (a_min == a_max).any():
+            warn("Divide by zero (a_min == a_max)")
+            if b_min is None:
+                return img - a_min
+            return img - a_min + b_min
+        img = (img - a_min) / (a_max - a_min)
+        if (b_min is not None) and (b_max is not None):
+            img = img * (b_max - b_min) + b_min
+        if self.clip:
+            img = img.clip(b_min, b_max)
+        return img
+
+    def __call__(self, img: Tensor) -> Tensor:
+        if not img.is_cuda:
+            if self.channel_wise:
+                return torch.cat([self._normalize_host(img[:, c : c + 1]) for c in range(img.shape[1])], dim=1)
+            return self._normalize_host(img)
+        _need_dev(img, "BatchedScaleIntensityRangePercentiles")
+        if img.ndim != 5:
+            raise ValueError(f"BatchedScaleIntensityRangePercentiles requires 5D input (B, C, Z, Y, X), got {img.ndim}D.")
+        q_low, q_high, b_min, b_max = self._targets()
+        B, C = img.shape[:2]
+        rows = img.view(B * C, -1) if self.channel_wise else img.view(B, -1)
+        a_min, a_max = percentile_bounds(rows, q_low, q_high)
+        eq = a_min == a_max
+        deg = eq.view(B, C).any(dim=0, keepdim=True).expand(B, C).reshape(-1) if self.channel_wise else eq.any().expand(B)
+        return percentile_scale(rows, a_min, a_max, deg, b_min, b_max, self.clip).view(img.shape)
+
+
+class BatchedScaleIntensityRangePercentilesd:
+    """dict form of ``BatchedScaleIntensityRangePercentiles`` (_percentile_scale.py:112-187), the reference's keywords"""
+
+    is_spatial = False
+
+    def __init__(self, keys, lower: float, upper: float, b_min: float | None, b_max: float | None, clip: bool = False,
+                 relative: bool = False, channel_wise: bool = False, dtype=None, allow_missing_keys: bool = False):
+        self.keys, self.allow_missing_keys = _keys(keys), allow_missing_keys
+        self.scaler = BatchedScaleIntensityRangePercentiles(lower, upper, b_min, b_max, clip, relative, channel_wise, dtype)
+
+    def __call__(self, data: dict) -> dict:
+        d = dict(data)
+        for k in self.keys:
+            if k not in d:
+                if self.allow_missing_keys:
+                    continue
+                raise KeyError(k)
+            d[k] = self.scaler(d[k])
+        return d
+
+
+def _roi3(roi_size, dims) -> tuple[int, int, int]:
+    """MONAI's fall_back_tuple + the clamp of RandSpatialCrop: non-positive entries keep the axis, larger ones are cut to it"""
+    roi = [roi_size] * 3 if isinstance(roi_size, int) else list(roi_size)
+    if len(roi) != 3 or len(dims) != 3:
+        raise ValueError("BatchedRandSpatialCrop only supports 3D data")
+    return tuple(d if int(s) <= 0 else min(int(s), d) for s, d in zip(roi, dims))
+
+
+class BatchedRandSpatialCrop:
+    """``viscy_transforms.BatchedRandSpatialCrop`` (_crop.py:24-125): one (Z, Y, X) window of ``roi_size`` per sample of a
+    (B, C, Z, Y, X) batch, at a random position (``random_center``) or at the centre.  ``randomize(shape)`` returns the
+    (B, 3) window starts; ``params=`` injects them.  The draws are this class' own stream (``generator``), not MONAI's:
+    only the gather is the reference's."""
+
+    def __init__(self, roi_size, max_roi_size=None, random_center: bool = True, random_size: bool = False):
+        if random_size:
+            raise ValueError("Batched transform does not support random size.")
+        self.roi_size, self.max_roi_size, self.random_center = roi_size, max_roi_size, random_center
+        self.generator: torch.Generator | None = None
+
+    def randomize(self, shape) -> Tensor:
+        if len(shape) != 5:
+            raise ValueError("BatchedRandSpatialCrop only supports 3D data")
+        B, dims = shape[0], tuple(shape[2:])
+        size = _roi3(self.roi_size, dims)
+        if self.random_center:
+            u = torch.rand(B, 3, generator=self.generator, dtype=torch.float64)
+            span = torch.tensor([d - s + 1 for d, s in zip(dims, size)], dtype=torch.float64)
+            return torch.minimum((u * span).long(), (span - 1).long())
+        # MONAI CenterSpatialCrop: SpatialCrop(roi_center = dim // 2, roi_size)
+        return torch.tensor([[max(d // 2 - s // 2, 0) for d, s in zip(dims, size)]] * B, dtype=torch.long)
+
+    def __call__(self, img: Tensor, params: Tensor | None = None) -> Tensor:
+        if img.ndim != 5:
+            raise ValueError("BatchedRandSpatialCrop only supports 3D data")
+        starts = params if params is not None else self.randomize(img.shape)
+        return _crop_at(img, starts, _roi3(self.roi_size, tuple(img.shape[2:])))
+
+
+def _clamped_starts(starts, dims, size, device) -> Tensor:
+    """(B, 3) starts held inside [0, dim - size] (injected ones included), on ``device``, without a host round trip"""
+    st = torch.as_tensor(starts).to(device=device, dtype=torch.long)
+    hi = torch.tensor([d - s for d, s in zip(dims, size)], dtype=torch.long, device=device)
+    return torch.minimum(st.clamp_min(0), hi)
+
+
+def _crop_at(img: Tensor, starts, size) -> Tensor:
+    dims = tuple(img.shape[2:])
+    if img.is_cuda:
+        _need_dev(img, "BatchedRandSpatialCrop")
+        return crop3d(img, _clamped_starts(starts, dims, size, img.device), size)
+    st = _clamped_starts(starts, dims, size, img.device).tolist()
+    return torch.stack([img[b, :, z : z + size[0], y : y + size[1], x : x + size[2]] for b, (z, y, x) in enumerate(st)]).contiguous()
+
+
+class BatchedRandSpatialCropd:
+    """dict form (_crop.py:128-148): one draw per sample from the first key's shape, shared by all keys"""
+
+    is_spatial = True
+
+    def __init__(self, keys, roi_size, max_roi_size=None, random_center: bool = True, random_size: bool = False,
+                 allow_missing_keys: bool = False):
+        self.keys, self.allow_missing_keys = _keys(keys), allow_missing_keys
+        self.cropper = BatchedRandSpatialCrop(roi_size, max_roi_size, random_center, random_size)
+
+    def randomize(self, shape) -> Tensor:
+        return self.cropper.randomize(shape)
+
+    def _present(self, data: dict) -> list[str]:
+        missing = [k for k in self.keys if k not in data]
+        if missing and not self.allow_missing_keys:
+            raise KeyError(missing[0])
+        return [k for k in self.keys if k in data]
+
+    def __call__(self, data: dict, params: Tensor | None = None) -> dict:
+        keys = self._present(data)
+        if not keys:
+            return data
+        starts = params if params is not None else self.randomize(data[keys[0]].shape)
+        for k in keys:
+            data[k] = self.cropper(data[k], params=starts)
+        return data
+
+
+def crop_zreduce(x: Tensor, starts, size, mode: Tensor) -> Tensor:
+    """(B, C, 1, cy, cx): the (cz, cy, cx) window at ``starts`` (B, 3; None = zeros; clamped into the volume by the kernel)
+    reduced over Z — ``mode[b]`` 0: maximum (NaN propagates), 1: the window's centre plane ``cz // 2`` (``vsx_crop_zreduce``)"""
+    if not (_dev_ok(x) and x.ndim == 5):
+        raise RuntimeError("crop_zreduce needs a contiguous float32 (B,C,Z,Y,X) batch on the HIP device (no CPU fallback)")
+    B, C, Z, Y, X = x.shape
+    cz, cy, cx = (int(v) for v in size)
+    st = None if starts is None else torch.as_tensor(starts).to(x.device, torch.int32).contiguous()
+    md = mode.to(x.device, torch.int32).contiguous()
+    y = torch.empty((B, C, 1, cy, cx), dtype=torch.float32, device=x.device)
+    check(lib().vsx_crop_zreduce(ptr(x), ptr(y), ptr(st), ptr(md), B, C, Z, Y, X, cz, cy, cx, stream()), "crop_zreduce")
+    return y
+
+
+def _z_modes(B: int, is_labelfree, default_center: bool) -> Tensor:
+    if is_labelfree is None:
+        return torch.full((B,), int(default_center), dtype=torch.int32)
+    return torch.as_tensor(is_labelfree).reshape(B).to(torch.int32)
+
+
+class BatchedChannelWiseZReduction:
+    """``viscy_transforms.BatchedChannelWiseZReduction`` (_z_reduction.py:14-61): (B, C, Z, Y, X) -> (B, C, 1, Y, X); label-free
+    samples (``is_labelfree[b]``) keep the centre slice ``Z // 2``, the others the maximum over Z; without a mask
+    ``default_strategy`` ("mip" / "center") holds for the batch.  ``Z == 1`` passes through."""
+
+    def __init__(self, default_strategy: str = "mip"):
+        if default_strategy not in ("mip", "center"):
+            raise ValueError(f"default_strategy must be 'mip' or 'center', got '{default_strategy}'")
+        self.default_strategy = default_strategy
+
+    def __call__(self, img: Tensor, is_labelfree: Tensor | None = None) -> Tensor:
+        z = img.shape[2]
+        if z == 1:
+            return img
+        if img.is_cuda:
+            _need_dev(img, "BatchedChannelWiseZReduction")
+            return crop_zreduce(img, None, img.shape[2:], _z_modes(img.shape[0], is_labelfree, self.default_strategy == "center"))
+        if is_labelfree is None:
+            if self.default_strategy == "center":
+                return img[:, :, z // 2 : z // 2 + 1]
+            return img.amax(dim=2, keepdim=True)
+        center = img[:, :, z // 2 : z // 2 + 1]
+        mip = img.amax(dim=2, keepdim=True)
+        return torch.where(is_labelfree.view(-1, 1, 1, 1, 1), center, mip)
+
+
+class BatchedChannelWiseZReductiond:
+    """dict form (_z_reduction.py:64-117).  Bag-of-channels mode: the per-sample ``_is_labelfree`` mask is popped from the
+    dict; all-channels mode: the keys named in ``labelfree_keys`` keep the centre slice, the others the maximum."""
+
+    is_spatial = False  # as in the reference, which declares nothing here: foreground masks do not follow it
+
+    def __init__(self, keys, labelfree_keys=None, default_strategy: str = "mip", allow_missing_keys: bool = False):
+        self.keys, self.allow_missing_keys = _keys(keys), allow_missing_keys
+        self.labelfree_keys = set(labelfree_keys) if labelfree_keys is not None else None
+        self.reducer = BatchedChannelWiseZReduction(default_strategy=default_strategy)
+        self._center, self._mip = BatchedChannelWiseZReduction("center"), BatchedChannelWiseZReduction("mip")
+
+    def _plan(self, data: dict):
+        """[(key, reducer, mask)] of this call; pops ``_is_labelfree``"""
+        is_labelfree = data.pop("_is_labelfree", None)
+        plan = []
+        for k in self.keys:
+            if k not in data:
+                if self.allow_missing_keys:
+                    continue
+                raise KeyError(k)
+            if self.labelfree_keys is not None:
+                plan.append((k, self._center if k in self.labelfree_keys else self._mip, None))
+            else:
+                plan.append((k, self.reducer, is_labelfree))
+        return plan
+
+    def __call__(self, data: dict) -> dict:
+        for k, reducer, mask in self._plan(data):
+            data[k] = reducer(data[k], is_labelfree=mask)
+        return data
+
+
+class _CropThenZReduce:
+    """``BatchedRandSpatialCropd`` immediately followed by ``BatchedChannelWiseZReductiond`` over the same keys: one
+    ``vsx_crop_zreduce`` per key, which reads the window and writes its projection — the Z-deep crop is never stored.  Missing keys are treated as the two
+    transforms treat them one after the other."""
+
+    def __init__(self, crop: "BatchedRandSpatialCropd", zreduce: "BatchedChannelWiseZReductiond"):
+        self.crop, self.zreduce = crop, zreduce
+
+    def __call__(self, data: dict, params: Tensor | None = None) -> dict:
+        keys = self.crop._present(data)
+        starts = params if params is not None else (self.crop.randomize(data[keys[0]].shape) if keys else None)
+        for k, reducer, mask in self.zreduce._plan(data):
+            x = data[k]
+            if x.ndim != 5:
+                raise ValueError("BatchedRandSpatialCrop only supports 3D data")
+            if x.is_cuda:
+                _need_dev(x, "BatchedRandSpatialCrop -> BatchedChannelWiseZReduction")
+                size = _roi3(self.crop.cropper.roi_size, tuple(x.shape[2:]))
+                data[k] = crop_zreduce(x, starts, size, _z_modes(x.shape[0], mask, reducer.default_strategy == "center"))
+            else:
+                data[k] = reducer(self.crop.cropper(x, params=starts), is_labelfree=mask)
+        return data
+
+
+def fuse_crop_zreduce(transforms: Sequence) -> list:
+    """Peephole like ``fuse_affine_crop``: a random crop whose output is Z-reduced next over the same keys (the 2-D MIP
+    recipes end their augmentations with exactly this pair) becomes one gather.  Same values, same RNG consumption."""
+    out, i = [], 0
+    ts = list(transforms)
+    while i < len(ts):
+        t = ts[i]
+        nxt = ts[i + 1] if i + 1 < len(ts) else None
+        if (isinstance(t, BatchedRandSpatialCropd) and isinstance(nxt, BatchedChannelWiseZReductiond)
+                and list(nxt.keys) == list(t.keys)):
+            out.append(_CropThenZReduce(t, nxt))
+            i += 2
+        else:
+            out.append(t)
+            i += 1
+    return out
