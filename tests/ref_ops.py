@@ -464,6 +464,61 @@ def head_conv_supported(H2, W2, c3, cmid, zo, dtype) -> bool:
     return False
 
 
+# The direct kernels themselves, stated from the layouts of csrc/headconv.hip for the exact-arithmetic tests
+# (tests/ref_exact_head.py): hin [B*H2*W2, (zo+2)*c3], U / dU [B*H2*W2, zo*cmid], Wc [cmid][27*c3] with
+# k = ((dy*3 + dx)*3 + dz)*c3 + c.  One shifted slice and one small matrix product per tap; no convolution routine.
+def _head_taps():
+    return [(dy, dx, dz) for dy in range(3) for dx in range(3) for dz in range(3)]
+
+
+def _head_halo(t, B, H2, W2, planes, ch):
+    """[B*H2*W2, planes*ch] -> [B, H2 + 2, W2 + 2, planes, ch] with a one-pixel ring of zeros"""
+    return F.pad(t.float().view(B, H2, W2, planes, ch), (0, 0, 0, 0, 1, 1, 1, 1))
+
+
+def head_conv_fwd(hin, Wc, bias, ssum, ssq, B, H2, W2, c3, cmid, zo):
+    """U[p, z, n] = b[n] + sum_{dy, dx, dz, c} hin[p + (dy - 1, dx - 1), z + dz, c] Wc[n, (dy, dx, dz), c]; ssum / ssq += the
+    per-sample sums of the stored values and of their squares"""
+    x = _head_halo(hin, B, H2, W2, zo + 2, c3)
+    W = Wc.float().view(cmid, 3, 3, 3, c3)
+    U = torch.zeros(B, H2, W2, zo, cmid)
+    for dy, dx, dz in _head_taps():
+        U += x[:, dy:dy + H2, dx:dx + W2, dz:dz + zo, :] @ W[:, dy, dx, dz, :].t()
+    if bias is not None:
+        U += bias.float()
+    U = U.to(hin.dtype)
+    s = U.float().view(B, H2 * W2 * zo, cmid)
+    ssum += s.sum(1)
+    ssq += (s * s).sum(1)
+    return U.view(B * H2 * W2, zo * cmid)
+
+
+def head_conv_wgrad(hin, dU, dW, db, B, H2, W2, c3, cmid, zo):
+    """dW[n, (dy, dx, dz), c] += sum_{p, z} dU[p, z, n] hin[p + (dy - 1, dx - 1), z + dz, c]; db[n] += sum_{p, z} dU[p, z, n]"""
+    x = _head_halo(hin, B, H2, W2, zo + 2, c3)
+    g = dU.float().view(B * H2 * W2 * zo, cmid)
+    out = dW.view(cmid, 27, c3)
+    for t, (dy, dx, dz) in enumerate(_head_taps()):
+        out[:, t, :] += g.t() @ x[:, dy:dy + H2, dx:dx + W2, dz:dz + zo, :].reshape(-1, c3)
+    if db is not None:
+        db += g.sum(0)
+
+
+def head_conv_dgrad_prep(Wc):
+    """the kernel re-packs the weights per (tap, plane) step; this backend reads them where they are"""
+    return Wc
+
+
+def head_conv_dgrad(dU, Wp, B, H2, W2, c3, cmid, zo):
+    """dhin[q, z', c] = sum_{ey, ex, z, n} dU[q + (ey - 1, ex - 1), z, n] Wc[n, (2 - ey, 2 - ex, z' - z), c]"""
+    g = _head_halo(dU, B, H2, W2, zo, cmid)
+    W = Wp.float().view(cmid, 3, 3, 3, c3)
+    dhin = torch.zeros(B, H2, W2, zo + 2, c3)
+    for ey, ex, dz in _head_taps():
+        dhin[:, :, :, dz:dz + zo, :] += g[:, ey:ey + H2, ex:ex + W2] @ W[:, 2 - ey, 2 - ex, dz, :]
+    return dhin.view(B * H2 * W2, (zo + 2) * c3).to(dU.dtype)
+
+
 def scale_weight_samples(W, s, dtype):
     return (W.detach().float().reshape(W.shape[0], -1)[None, :, :] * s.float()[:, None, :]).to(dtype)
 
