@@ -269,6 +269,43 @@ int32_t vsx_masked_mse_fwd(const float* pred, const float* orig, const uint8_t* 
 int32_t vsx_masked_mse_bwd(const float* pred, const float* orig, const uint8_t* mask, const float* acc, const float* gout,
     float* dpred, int32_t B, int32_t C, int32_t Z, int64_t HW, vsx_stream_t stream);
 
+/* viscy_utils.losses.SpotlightLoss.forward (packages/viscy-utils/src/viscy_utils/losses/spotlight.py:161-225) on `rows` = B*C
+ * contiguous rows of n = Z*Y*X voxels:
+ *   m = mask weight;  d = p - t;  s = clamp((p - k p) / (k - 2k|p| + 1), 0, 1)
+ *   F = sum m, Em = sum m d^2, E = sum d^2, S = sum s, I = sum s m                                     (per row)
+ *   mse_r = F > 0 ? Em / (F + eps) : E / n;  dice_r = 1 - 2 I / (S + F + eps);  real_r = 0 < F < n
+ *   loss = lambda_mse * mean_r mse_r + (1 - lambda_mse) * (n_real > 0 ? sum_r real_r dice_r / n_real : 0)
+ * pred: fp32 or bf16 (dtype), read as stored; target fp32.  mask_mode selects m: VSX_SPOTLIGHT_THRESHOLD m = t >= thr[row]
+ * (thr: `rows` floats on the device: a fixed threshold repeated, or vsx_otsu_threshold's; mask unused), VSX_SPOTLIGHT_MASK_U8
+ * m = (float)byte of a uint8 / bool mask, VSX_SPOTLIGHT_MASK_F32 m = an fp32 weight (thr unused).  Row starts may have any
+ * alignment (odd n); 16-byte loads are used where all array bases are 16-byte aligned.
+ * One workgroup sums one chunk of VSX_SPOTLIGHT_CHUNK voxels of one row and stores its five partial sums into ws (plain stores,
+ * every word written before it is read: ws needs no initialisation); the finalise kernel folds them in float64 in a fixed
+ * order, so loss and gradient are bit-identical from run to run.  ws: vsx_spotlight_workspace(VSX_SPOTLIGHT_WS_FWD, rows, n)
+ * bytes, 8-byte aligned.  loss: 1 float.  coef: 4 floats per row {a, b, c, e}, kept for the backward:
+ *   dpred = gout[0] * (d * (a m + b) + s' * (c m + e)),   s' = (1 - k^2) / (k - 2k|p| + 1)^2 on 0 <= p <= 1, else 0
+ * (dpred in pred's dtype; gout: 1 float on the device). */
+#define VSX_SPOTLIGHT_CHUNK 16384
+#define VSX_SPOTLIGHT_THRESHOLD 0
+#define VSX_SPOTLIGHT_MASK_U8 1
+#define VSX_SPOTLIGHT_MASK_F32 2
+#define VSX_SPOTLIGHT_WS_FWD 0
+#define VSX_SPOTLIGHT_WS_OTSU 1
+int64_t vsx_spotlight_workspace(int32_t op, int64_t rows, int64_t n);
+int32_t vsx_spotlight_fwd(const void* pred, int32_t dtype, const float* target, const void* mask, int32_t mask_mode,
+    const float* thr, int64_t rows, int64_t n, double lambda_mse, double sigmoid_k, double eps, void* ws, float* loss,
+    float* coef, vsx_stream_t stream);
+int32_t vsx_spotlight_bwd(const void* pred, int32_t dtype, const float* target, const void* mask, int32_t mask_mode,
+    const float* thr, const float* coef, const float* gout, void* dpred, int64_t rows, int64_t n, double sigmoid_k,
+    vsx_stream_t stream);
+/* Otsu threshold of each of `rows` contiguous rows of n fp32 values (spotlight.py:50-110): row min / max, an n_bins-bin
+ * histogram (2 <= n_bins <= 1024; bin = min((int)((x - lo) * n_bins / (hi - lo)), n_bins - 1) in fp32, integer counts), the
+ * reference's inter-class variance on cumulative counts and means in float64, first maximum; thr[row] = the centre of that bin,
+ * lo + (idx + 0.5) * (hi - lo) / n_bins, or lo for a constant row.  ws: vsx_spotlight_workspace(VSX_SPOTLIGHT_WS_OTSU, rows, n)
+ * bytes, 4-byte aligned, no initialisation needed. */
+int32_t vsx_otsu_threshold(const float* target, float* thr, void* ws, int64_t rows, int64_t n, int32_t n_bins,
+    vsx_stream_t stream);
+
 /* ConvNeXt-V1 layer scale (timm ConvNeXtBlock.gamma, ls_init_value 1e-6; the `convnext_tiny` trunk of
  * viscy_models.contrastive.ContrastiveEncoder, encoder.py:93-99) folded into the block's second pointwise layer:
  * Ws = diag(gamma) W [R,K], bs = gamma * b; unfold ADDS dW += diag(gamma) dWs, db += gamma dbs,

@@ -5,7 +5,7 @@
 See DESIGN.md (what is built and why) and INTEGRATION.md (how it binds to the reference).
 """
 
-__all__ = ["UNeXt2", "MixedLoss", "VSUNet", "HCSDataModule", "HCSPredictionWriter", "FcmaeUNet", "FullyConvolutionalMAE", "MaskedMSELoss", "ContrastiveEncoder", "ContrastiveModule", "NTXentLoss", "NTXentHCL", "TripletMarginLoss", "FlatAdamW", "FlatDataParallel", "TrainStep"]
+__all__ = ["UNeXt2", "MixedLoss", "VSUNet", "HCSDataModule", "HCSPredictionWriter", "FcmaeUNet", "FullyConvolutionalMAE", "MaskedMSELoss", "SpotlightLoss", "ContrastiveEncoder", "ContrastiveModule", "NTXentLoss", "NTXentHCL", "TripletMarginLoss", "FlatAdamW", "FlatDataParallel", "TrainStep"]
 
 
 def __getattr__(name):
@@ -19,6 +19,8 @@ def __getattr__(name):
         from .fcmae import FullyConvolutionalMAE as v
     elif name == "MaskedMSELoss":
         from .losses import MaskedMSELoss as v
+    elif name == "SpotlightLoss":
+        from .losses import SpotlightLoss as v
     elif name in ("ContrastiveEncoder", "ContrastiveModule", "NTXentLoss", "NTXentHCL", "TripletMarginLoss"):
         from . import contrastive as _c
 

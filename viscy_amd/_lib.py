@@ -19,6 +19,9 @@ A_ROWS, A_PATCH2, A_CONV3 = 0, 1, 2
 PRO_NONE, PRO_GRN = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU_SQ, EPI_BIAS_RES, EPI_DZ, EPI_BIAS_STATS, EPI_LN_BWD = 0, 1, 2, 3, 4, 5, 6
 LOSS_SLOTS, LOSS_SLOT_STRIDE = 64, 32  # VSX_LOSS_SLOTS / VSX_LOSS_SLOT_STRIDE of include/vsx.h
+SPOTLIGHT_CHUNK = 16384  # VSX_SPOTLIGHT_CHUNK: voxels one workgroup of the SpotlightLoss passes sums
+SPOTLIGHT_THRESHOLD, SPOTLIGHT_MASK_U8, SPOTLIGHT_MASK_F32 = 0, 1, 2  # VSX_SPOTLIGHT_* mask modes
+SPOTLIGHT_WS_FWD, SPOTLIGHT_WS_OTSU = 0, 1
 
 _I32, _F32, _P, _I64 = C.c_int32, C.c_float, C.c_void_p, C.c_int64
 
@@ -165,6 +168,10 @@ _SIGS = {
     "vsx_rows_select": (_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "vsx_masked_mse_fwd": (_I32, [_P] * 5 + [_I32] * 3 + [_I64, _P]),
     "vsx_masked_mse_bwd": (_I32, [_P] * 6 + [_I32] * 3 + [_I64, _P]),
+    "vsx_spotlight_workspace": (_I64, [_I32, _I64, _I64]),
+    "vsx_spotlight_fwd": (_I32, [_P, _I32, _P, _P, _I32, _P, _I64, _I64, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "vsx_spotlight_bwd": (_I32, [_P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I64, _I64, C.c_double, _P]),
+    "vsx_otsu_threshold": (_I32, [_P, _P, _P, _I64, _I64, _I32, _P]),
     "vsx_head_conv_supported": (_I32, [_I32] * 6),
     "vsx_head_conv_det_floats": (_I64, [_I32] * 3),
     "vsx_head_conv_fwd": (_I32, [_P] * 6 + [_I32] * 7 + [_P]),

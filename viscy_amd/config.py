@@ -29,6 +29,8 @@ CLASS_MAP = {
     "cytoland.engine.MaskedMSELoss": "viscy_amd.losses.MaskedMSELoss",
     "viscy_utils.losses.MixedLoss": "viscy_amd.losses.MixedLoss",
     "viscy_utils.losses.mixed_loss.MixedLoss": "viscy_amd.losses.MixedLoss",
+    "viscy_utils.losses.SpotlightLoss": "viscy_amd.losses.SpotlightLoss",
+    "viscy_utils.losses.spotlight.SpotlightLoss": "viscy_amd.losses.SpotlightLoss",
     "viscy_data.hcs.HCSDataModule": "viscy_amd.data.hcs.HCSDataModule",
     "viscy_data.HCSDataModule": "viscy_amd.data.hcs.HCSDataModule",
     "viscy_data.combined.CombinedDataModule": "viscy_amd.data.combined.CombinedDataModule",

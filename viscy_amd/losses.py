@@ -198,3 +198,80 @@ class MaskedMSELoss(nn.Module):
             raise ValueError(f"mask must be (B,1,Y,X) = {(preds.shape[0], 1, preds.shape[3], preds.shape[4])}, got {tuple(mask.shape)}")
         L.lib()
         return _MaskedMSEFn.apply(preds, original, mask)
+
+
+class _SpotlightFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred: Tensor, target: Tensor, fg_mask: Tensor | None, lambda_mse: float, sigmoid_k: float, eps: float,
+                fg_threshold: float | None):
+        from . import ops as O
+
+        P = pred.detach()
+        if P.dtype not in (torch.float32, torch.bfloat16):
+            P = P.float()
+        P = P.contiguous()  # fp32 or bf16, read by the kernels as stored
+        T = target.detach().float().contiguous()
+        rows = P.shape[0] * P.shape[1]
+        M = thr = None
+        if fg_mask is not None:
+            M = fg_mask.detach()
+            if M.dtype not in (torch.bool, torch.uint8, torch.float32):
+                M = M.float()  # the reference's fg_mask.float(); bool / uint8 / float32 masks are read without a conversion pass
+            M = M.contiguous()
+        elif fg_threshold is not None:
+            thr = torch.empty(rows, dtype=torch.float32, device=P.device)
+            check(lib().vsx_fill_f32(ptr(thr), rows, float(fg_threshold), stream()), "fill")
+        else:
+            thr = O.otsu_threshold(T)
+        loss, coef = O.spotlight_fwd(P, T, M, thr, lambda_mse=lambda_mse, sigmoid_k=sigmoid_k, eps=eps)
+        # scratch this Function alone writes and reads (detached, never exposed): plain attributes, as in _MixedLossFn
+        ctx.saved = (P, T, M, thr, coef, sigmoid_k, pred.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout: Tensor):
+        from . import ops as O
+
+        P, T, M, thr, coef, sigmoid_k, in_dtype = ctx.saved
+        go = gout.detach().float().reshape(1).contiguous()  # stays on the device: no host sync
+        dP = O.spotlight_bwd(P, T, M, thr, coef, go, sigmoid_k)
+        return dP.to(in_dtype), None, None, None, None, None, None
+
+
+class SpotlightLoss(nn.Module):
+    """``viscy_utils.losses.SpotlightLoss`` (packages/viscy-utils/src/viscy_utils/losses/spotlight.py:113-225 of the reference):
+    masked MSE over the foreground plus Dice on the soft-thresholded prediction, per (batch, channel) row.  Same constructor and
+    ``forward(pred, target, fg_mask=None) -> scalar`` for (B,C,Z,Y,X) or (B,C,Y,X) inputs.  The foreground is ``fg_mask`` (bool /
+    uint8 / float32 read as stored), else ``target >= fg_threshold``, else ``target >= otsu`` with the per-row Otsu thresholds
+    computed on the device.  One reduction pass and a finalise kernel forward, one elementwise pass backward
+    (``vsx_spotlight_*``, ``vsx_otsu_threshold``); nothing synchronises with the host, so the loss runs inside a captured step.
+    A batch without any row that has both foreground and background gives a Dice term of exactly 0, decided on the device;
+    the reference's one-time warning for that case is not issued."""
+
+    def __init__(self, lambda_mse: float = 0.5, sigmoid_k: float = -0.95, eps: float = 1e-6, fg_threshold: float | None = None) -> None:
+        super().__init__()
+        if not -1 < sigmoid_k < 0:
+            raise ValueError(f"sigmoid_k must be in (-1, 0), got {sigmoid_k}")
+        if not 0 < lambda_mse < 1:
+            raise ValueError(f"lambda_mse must be in (0, 1), got {lambda_mse}")
+        if eps <= 0:
+            raise ValueError(f"eps must be > 0, got {eps}")
+        self.lambda_mse = lambda_mse
+        self.sigmoid_k = sigmoid_k
+        self.eps = eps
+        self.fg_threshold = fg_threshold
+
+    def forward(self, pred: Tensor, target: Tensor, fg_mask: Tensor | None = None) -> Tensor:
+        if pred.shape != target.shape:
+            raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} must have the same shape")
+        if pred.ndim not in (4, 5):
+            raise ValueError(f"pred / target must be (B,C,Z,Y,X) or (B,C,Y,X), got {pred.ndim} dimensions")
+        if pred.numel() == 0:
+            raise ValueError(f"pred / target must not be empty, got shape {tuple(pred.shape)}")
+        if fg_mask is not None and fg_mask.shape != target.shape:
+            raise ValueError(f"fg_mask {tuple(fg_mask.shape)} must have the shape of target {tuple(target.shape)}")
+        if not (pred.is_cuda and target.is_cuda and (fg_mask is None or fg_mask.is_cuda)):
+            raise RuntimeError("viscy_amd.SpotlightLoss runs on MI355X HIP kernels only (no CPU / eager fallback)")
+        L.lib()
+        return _SpotlightFn.apply(pred, target, fg_mask, float(self.lambda_mse), float(self.sigmoid_k), float(self.eps),
+                                  None if self.fg_threshold is None else float(self.fg_threshold))

@@ -828,6 +828,80 @@ def masked_mse_bwd(pred: Tensor, orig: Tensor, mask_u8: Tensor, acc: Tensor, gou
     return dpred
 
 
+# ------------------------------------------------------------------ SpotlightLoss (csrc/spotlight.hip)
+SPOTLIGHT_CHUNK = L.SPOTLIGHT_CHUNK  # voxels per workgroup: a row longer than this is summed by several workgroups
+
+
+def _rows_n(t: Tensor) -> tuple[int, int]:
+    rows = t.shape[0] * t.shape[1]
+    return rows, t.numel() // rows
+
+
+def _spotlight_mask(pred: Tensor, target: Tensor, mask: Tensor | None, thr: Tensor | None, rows: int):
+    """(mask operand, thresholds, mask mode) of the vsx_spotlight_* calls: a bool mask is read as its bytes, no copy"""
+    if target.dtype != torch.float32 or target.shape != pred.shape:
+        raise ValueError(f"spotlight: target must be float32 of pred's shape {tuple(pred.shape)}, got {target.dtype} {tuple(target.shape)}")
+    if mask is not None:
+        if mask.shape != target.shape:
+            raise ValueError(f"spotlight: mask shape {tuple(mask.shape)} differs from target's {tuple(target.shape)}")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype == torch.uint8:
+            return mask, None, L.SPOTLIGHT_MASK_U8
+        if mask.dtype == torch.float32:
+            return mask, None, L.SPOTLIGHT_MASK_F32
+        raise TypeError(f"spotlight: the mask must be bool, uint8 or float32, got {mask.dtype}")
+    if thr is None or thr.dtype != torch.float32 or thr.numel() != rows:  # (B, C) or flat
+        raise ValueError(f"spotlight: without a mask, {rows} float32 thresholds (one per row) are required")
+    return None, thr, L.SPOTLIGHT_THRESHOLD
+
+
+def spotlight_workspace_floats(rows: int, n: int, op: int = L.SPOTLIGHT_WS_FWD) -> int:
+    """fp32 words of workspace of ``spotlight_fwd`` (or, with ``op=SPOTLIGHT_WS_OTSU``, of ``otsu_threshold``)"""
+    return (int(lib().vsx_spotlight_workspace(op, rows, n)) + 3) // 4
+
+
+def spotlight_fwd(pred: Tensor, target: Tensor, mask: Tensor | None = None, thr: Tensor | None = None, *, lambda_mse: float = 0.5,
+                  sigmoid_k: float = -0.95, eps: float = 1e-6, workspace: Tensor | None = None):
+    """-> (loss (), coef (rows, 4)).  ``pred`` fp32 or bf16 (B, C, ...), ``target`` fp32; ``mask`` (bool / uint8 / float32, the
+    shape of target) or ``thr`` (one float32 threshold per (b, c) row).  ``workspace``: float32, at least
+    ``spotlight_workspace_floats`` words, any contents (every word is written before it is read)."""
+    rows, n = _rows_n(pred)
+    mask, thr, mode = _spotlight_mask(pred, target, mask, thr, rows)
+    need = spotlight_workspace_floats(rows, n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=pred.device)
+    elif workspace.dtype != torch.float32 or workspace.numel() < need:
+        raise ValueError(f"spotlight_fwd: the workspace must hold {need} float32 words")
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    coef = torch.empty((rows, 4), dtype=torch.float32, device=pred.device)
+    check(lib().vsx_spotlight_fwd(ptr(pred), dtype_code(pred.dtype), ptr(target), ptr(mask), mode, ptr(thr), rows, n, lambda_mse,
+                                  sigmoid_k, eps, ptr(workspace), ptr(loss), ptr(coef), stream()), "spotlight_fwd")
+    return loss, coef
+
+
+def spotlight_bwd(pred: Tensor, target: Tensor, mask: Tensor | None, thr: Tensor | None, coef: Tensor, gout: Tensor,
+                  sigmoid_k: float = -0.95) -> Tensor:
+    """d loss / d pred * gout, in pred's dtype; ``gout`` is one float32 on the device"""
+    rows, n = _rows_n(pred)
+    mask, thr, mode = _spotlight_mask(pred, target, mask, thr, rows)
+    dpred = torch.empty_like(pred)
+    check(lib().vsx_spotlight_bwd(ptr(pred), dtype_code(pred.dtype), ptr(target), ptr(mask), mode, ptr(thr), ptr(coef), ptr(gout),
+                                  ptr(dpred), rows, n, sigmoid_k, stream()), "spotlight_bwd")
+    return dpred
+
+
+def otsu_threshold(target: Tensor, n_bins: int = 256) -> Tensor:
+    """Otsu threshold of every (b, c) row of a float32 (B, C, ...) tensor -> (B, C) float32, computed on the device"""
+    if target.dtype != torch.float32:
+        raise TypeError(f"otsu_threshold: target must be float32, got {target.dtype}")
+    rows, n = _rows_n(target)
+    ws = torch.empty(spotlight_workspace_floats(rows, n, L.SPOTLIGHT_WS_OTSU), dtype=torch.float32, device=target.device)
+    thr = torch.empty((target.shape[0], target.shape[1]), dtype=torch.float32, device=target.device)
+    check(lib().vsx_otsu_threshold(ptr(target), ptr(thr), ptr(ws), rows, n, n_bins, stream()), "otsu_threshold")
+    return thr
+
+
 def voxel_shuffle_fwd(feat: Tensor, B: int, h: int, w: int, Cout: int, D: int, s: int, pool: bool) -> Tensor:
     out = torch.empty((B, Cout, D, s * h, s * w), dtype=torch.float32, device=feat.device)
     check(lib().vsx_voxel_shuffle_fwd(ptr(feat), ptr(out), B, h, w, Cout, D, s, int(pool), dtype_code(feat.dtype), stream()),
