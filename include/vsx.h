@@ -752,6 +752,23 @@ int32_t vsx_bn3d_bwd(const void* dy, int32_t ldy, int32_t ycoff, const void* z, 
 int32_t vsx_conv3d_to_cl(const float* x, void* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream);
 int32_t vsx_conv3d_from_cl(const void* y, float* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream);
 
+/* OnlineEvalCallback (csrc/online_eval.hip): cosine k-NN probe, neighbour vote, pair distances; fp32 throughout (exact f32 MFMA).
+ * row_inv_norm: inv[i] = 1 / (||x_i||_2 + eps), 0 where that denominator is 0 (an all-zero row with eps = 0).
+ * knn_topk: row j is a candidate of query i iff group[j] >= 0 && group[j] != group[i]; s_ij = fl32(fl32(dot_ij * inv[i]) * inv[j]),
+ * dot accumulated in fp32.  Per query: its min(k, #candidates) best candidates in the total order (s descending, j ascending) in
+ * idx / sim [N][k], their number in cnt[N]; unused slots idx = -1, sim = -inf.  1 <= k <= 64, any d >= 1 and N >= 1.  No N x N buffer:
+ * ws (4-byte aligned) holds vsx_knn_topk_ws_bytes(N, d, k) = O(N k) bytes, any contents.
+ * knn_vote: pred[i] = the most frequent label among labels[idx[i][0 .. cnt[i])], ties to the smallest label; -1 for cnt[i] = 0.
+ * pair_cosine_dist: out[p] = 1 - fl32(fl32(dot(x_pi[p], x_pj[p]) * inv[pi[p]]) * inv[pj[p]]). */
+int32_t vsx_row_inv_norm(const float* x, float* inv, int32_t N, int32_t d, float eps, vsx_stream_t stream);
+int64_t vsx_knn_topk_ws_bytes(int32_t N, int32_t d, int32_t k);
+int32_t vsx_knn_topk(const float* x, const float* inv, const int32_t* group, int32_t N, int32_t d, int32_t k, int32_t* idx, float* sim,
+    int32_t* cnt, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int32_t vsx_knn_vote(const int32_t* idx, const int32_t* cnt, const int32_t* labels, int32_t N, int32_t k, int32_t* pred,
+    vsx_stream_t stream);
+int32_t vsx_pair_cosine_dist(const float* x, const float* inv, const int32_t* pi, const int32_t* pj, int64_t P, int32_t d, float* out,
+    vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

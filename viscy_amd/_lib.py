@@ -201,6 +201,11 @@ _SIGS = {
     "vsx_bn3d_bwd": (_I32, [_P, _I32, _I32] + [_P] * 7 + [_I64, _I32, _I32, _I32, _P]),
     "vsx_conv3d_to_cl": (_I32, [_P, _P, _I32, _I32, _I64, _I32, _P]),
     "vsx_conv3d_from_cl": (_I32, [_P, _P, _I32, _I32, _I64, _I32, _P]),
+    "vsx_row_inv_norm": (_I32, [_P, _P, _I32, _I32, _F32, _P]),
+    "vsx_knn_topk_ws_bytes": (_I64, [_I32, _I32, _I32]),
+    "vsx_knn_topk": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "vsx_knn_vote": (_I32, [_P, _P, _P, _I32, _I32, _P, _P]),
+    "vsx_pair_cosine_dist": (_I32, [_P, _P, _P, _P, _I64, _I32, _P, _P]),
 }
 
 _lib = None

@@ -9,7 +9,7 @@
   the file, deep dict merge (lists REPLACE), top-level ``_private`` keys stripped at every level, circular references rejected.
 * ``CLASS_MAP`` — the reference ``class_path`` of every class this build provides -> the MI355X class.  Trainer sections
   keep ``max_epochs`` / ``precision`` / ``fast_dev_run`` / ``limit_train_batches`` and the mapped callbacks
-  (``HCSPredictionWriter``); Lightning loggers / checkpoint callbacks / strategies have no counterpart here and are
+  (``HCSPredictionWriter``, ``OnlineEvalCallback``); Lightning loggers / checkpoint callbacks / strategies have no counterpart here and are
   reported, not instantiated.
 Host-side plumbing only.
 """
@@ -40,6 +40,8 @@ CLASS_MAP = {
     "viscy_data.BatchedConcatDataModule": "viscy_amd.data.combined.BatchedConcatDataModule",
     "viscy_utils.callbacks.prediction_writer.HCSPredictionWriter": "viscy_amd.prediction_writer.HCSPredictionWriter",
     "viscy_utils.callbacks.HCSPredictionWriter": "viscy_amd.prediction_writer.HCSPredictionWriter",
+    "viscy_utils.callbacks.OnlineEvalCallback": "viscy_amd.online_eval.OnlineEvalCallback",
+    "viscy_utils.callbacks.online_eval.OnlineEvalCallback": "viscy_amd.online_eval.OnlineEvalCallback",
     "dynaclr.engine.ContrastiveModule": "viscy_amd.contrastive.ContrastiveModule",
     "viscy_models.contrastive.ContrastiveEncoder": "viscy_amd.contrastive.ContrastiveEncoder",
     "viscy_models.contrastive.encoder.ContrastiveEncoder": "viscy_amd.contrastive.ContrastiveEncoder",

@@ -1,0 +1,401 @@
+// viscy_amd — the device side of OnlineEvalCallback (viscy_utils/callbacks/online_eval.py): cosine k-nearest neighbours among the
+// rows of OTHER groups (cross-validation folds, or the train part of a holdout split), the neighbours' majority vote, and the
+// cosine distance of listed row pairs.  All arithmetic is fp32; dot products run on the exact f32-in / f32-accumulate MFMA
+// (v_mfma_f32_32x32x2_f32), so neighbour ranks do not depend on a reduced-precision rounding.
+//
+//   inv_i  = 1 / (||x_i|| + eps)                       (0 where the denominator is 0)
+//   s_ij   = fl32(fl32(dot_ij * inv_i) * inv_j)        candidate iff group[j] >= 0 && group[j] != group[i]
+//   result = the min(k, #candidates) best candidates of every row in the total order (s descending, j ascending)
+//
+// vsx_knn_topk never stores an N x N matrix.  A workgroup owns KT_TQ = 128 query rows and one contiguous range of candidate tiles
+// (KT_TC = 128 rows each).  Per tile it stages both operands through LDS in chunks of KT_KC = 32 features, forms the 128 x 128
+// tile of dot products in registers (four waves, a 64 x 64 quadrant of four 32 x 32 accumulators each), writes the scaled and
+// masked similarities to LDS one 64-column half at a time, and thread r < 128 scans row r of that half against the row's k-th
+// best, which it keeps in registers; the few survivors are inserted into the row's sorted list in LDS.  The candidate range of
+// a query tile is split over up to KT_MAX_SPLITS workgroups to fill the machine; every split stores its sorted list to the
+// workspace (O(N k)), and a second kernel merges the splits' lists per row in the same total order.  Since the order is total,
+// the result does not depend on the split count or on the order in which survivors were inserted.
+//
+// A masked entry travels through LDS as NaN: every comparison with it is false, so it is never inserted (a NaN similarity of
+// non-finite input rows is dropped in the same way).
+//
+// The feature index inside a chunk is permuted between the MFMA steps (lane half h, step s of group p reads feature 8p + 4h + s,
+// for both operands alike), so that each lane fetches four steps' operands with one 16-byte LDS read; a sum over k does not
+// care which k meets which step.
+#include "vsx_common.h"
+#include "../../include/vsx.h"
+
+#include <math.h>
+
+#define KT_TQ 128
+#define KT_TC 128
+#define KT_KC 32
+#define KT_LD 36         // floats per staged row: 32 + 4, keeps 16-byte alignment and spreads rows over the banks
+#define KT_SLD 65        // floats per row of the similarity half-tile
+#define KT_THREADS 256
+#define KT_STAGE (2 * KT_TQ * KT_LD)   // floats of the staging area (query chunk | candidate chunk); the half-tile (128 x 65) reuses it
+#define KT_MAX_SPLITS 8
+#define KT_MAX_K 64
+
+typedef float kt_f32x16 __attribute__((ext_vector_type(16)));
+
+static_assert(KT_TQ * KT_SLD <= KT_STAGE, "the similarity half-tile must fit the staging area");
+
+// ------------------------------------------------------------------ (a) inverse row norms: one wave per row
+__global__ __launch_bounds__(256) void row_inv_norm_kernel(const float* __restrict__ x, float* __restrict__ inv, int N, int d, float eps) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= N) return;
+  const float* xr = x + (size_t)row * d;
+  float ss = 0.f;
+  for (int c = lane; c < d; c += 64) ss = fmaf(xr[c], xr[c], ss);
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  const float den = __fadd_rn(sqrtf(ss), eps);
+  if (lane == 0) inv[row] = den == 0.f ? 0.f : __fdiv_rn(1.f, den);
+}
+
+// ------------------------------------------------------------------ (d) cosine distance of listed pairs: one wave per pair
+__global__ __launch_bounds__(256) void pair_cosine_dist_kernel(const float* __restrict__ x, const float* __restrict__ inv,
+                                                               const int* __restrict__ pi, const int* __restrict__ pj, long P, int d,
+                                                               float* __restrict__ out) {
+  const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (p >= P) return;
+  const int i = pi[p], j = pj[p];
+  const float* xi = x + (size_t)i * d;
+  const float* xj = x + (size_t)j * d;
+  float dot = 0.f;
+  for (int c = lane; c < d; c += 64) dot = fmaf(xi[c], xj[c], dot);
+  for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+  if (lane == 0) out[p] = __fsub_rn(1.f, __fmul_rn(__fmul_rn(dot, inv[i]), inv[j]));
+}
+
+// ------------------------------------------------------------------ (b) streaming similarity + top-k
+__device__ __forceinline__ bool kt_better(float s, int j, float s0, int j0) { return s > s0 || (s == s0 && j < j0); }
+
+// one thread's share of a chunk: 8 x 4 features; f = t + 256 u -> operand f >> 10, row (f & 1023) >> 3, feature quad f & 7, so
+// that 8 consecutive lanes read 128 contiguous bytes of one row
+template <bool VEC>
+__device__ __forceinline__ void kt_fetch(float4* r, const float* __restrict__ x, int q0, int c0, int kc0, int N, int d, int t) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int f = t + KT_THREADS * u;
+    const int g = f & 1023;
+    const int row = ((f >> 10) ? c0 : q0) + (g >> 3);
+    const int kk = kc0 + 4 * (g & 7);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row < N) {
+      const float* src = x + (size_t)row * d + kk;
+      if (VEC) {
+        if (kk < d) v = *reinterpret_cast<const float4*>(src);  // d % 4 == 0 and x 16-byte aligned
+      } else {
+        if (kk < d) v.x = src[0];
+        if (kk + 1 < d) v.y = src[1];
+        if (kk + 2 < d) v.z = src[2];
+        if (kk + 3 < d) v.w = src[3];
+      }
+    }
+    r[u] = v;
+  }
+}
+
+// KB: the list capacity the LDS is sized for (k <= KB); the lists themselves are laid out for the k of the call
+template <bool VEC, int KB>
+__global__ __launch_bounds__(KT_THREADS, KB <= 24 ? 2 : 1) void knn_topk_kernel(const float* __restrict__ x, const float* __restrict__ inv,
+                                                                const int* __restrict__ group, int N, int d, int k,
+                                                                int tiles_per_split, int* __restrict__ pidx,
+                                                                float* __restrict__ psim, int* __restrict__ pcnt) {
+  __shared__ __attribute__((aligned(16))) float kt_smem[KT_STAGE + 2 * KB * KT_TQ];
+  float* stage = kt_smem;                       // [2][KT_TQ][KT_LD]; later the similarity half-tile [KT_TQ][KT_SLD]
+  float* ls = kt_smem + KT_STAGE;               // [k][KT_TQ] sorted similarities of every query row
+  int* li = reinterpret_cast<int*>(ls + (size_t)k * KT_TQ);  // [k][KT_TQ] their row indices
+  __shared__ float invq[KT_TQ], invc[KT_TC];
+  __shared__ int gq[KT_TQ], gc[KT_TC];
+
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int wq = wave & 1, wc = wave >> 1;      // this wave's 64 x 64 quadrant of the tile
+  const int r32 = lane & 31, hh = lane >> 5;
+  const int q0 = blockIdx.x * KT_TQ;
+  const int ntiles = (N + KT_TC - 1) / KT_TC;
+  const int ct0 = blockIdx.y * tiles_per_split;
+  const int ct1 = min(ct0 + tiles_per_split, ntiles);
+  const int nchunks = (d + KT_KC - 1) / KT_KC;
+
+  if (t < KT_TQ) {
+    const int i = q0 + t;
+    gq[t] = i < N ? group[i] : -1;
+    invq[t] = i < N ? inv[i] : 0.f;
+  }
+  // the owner of query row t keeps the row's count and its k-th best in registers
+  const bool owner = t < KT_TQ && q0 + t < N;
+  int cnt = 0;
+  float thr_s = 0.f;
+  int thr_j = 0;
+
+  for (int ct = ct0; ct < ct1; ++ct) {
+    const int c0 = ct * KT_TC;
+    kt_f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+
+    float4 pre[8];
+    kt_fetch<VEC>(pre, x, q0, c0, 0, N, d, t);
+    for (int ch = 0; ch < nchunks; ++ch) {
+      __syncthreads();  // the previous chunk's reads (or the previous tile's scan of the half-tile) are done
+      if (ch == 0 && t < KT_TC) {
+        const int j = c0 + t;
+        gc[t] = j < N ? group[j] : -1;
+        invc[t] = j < N ? inv[j] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int f = t + KT_THREADS * u;
+        *reinterpret_cast<float4*>(stage + (size_t)(f >> 3) * KT_LD + 4 * (f & 7)) = pre[u];  // row f >> 3 of [query | candidate]
+      }
+      __syncthreads();
+      if (ch + 1 < nchunks) kt_fetch<VEC>(pre, x, q0, c0, (ch + 1) * KT_KC, N, d, t);
+      const float* qa = stage + (size_t)(wq * 64 + r32) * KT_LD + 4 * hh;
+      const float* cb = stage + (size_t)(KT_TQ + wc * 64 + r32) * KT_LD + 4 * hh;
+#pragma unroll
+      for (int p = 0; p < KT_KC / 8; ++p) {
+        const float4 a0 = *reinterpret_cast<const float4*>(qa + 8 * p);
+        const float4 a1 = *reinterpret_cast<const float4*>(qa + 32 * KT_LD + 8 * p);
+        const float4 b0 = *reinterpret_cast<const float4*>(cb + 8 * p);
+        const float4 b1 = *reinterpret_cast<const float4*>(cb + 32 * KT_LD + 8 * p);
+        const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
+        const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], bv0[s], acc[0][0], 0, 0, 0);
+          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], bv1[s], acc[0][1], 0, 0, 0);
+          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], bv0[s], acc[1][0], 0, 0, 0);
+          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], bv1[s], acc[1][1], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();  // every wave is done with the staged chunk: the half-tile takes its place
+
+    for (int h = 0; h < 2; ++h) {
+      if (wc == h) {
+        // C/D map of the 32 x 32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const int col = b * 32 + r32;        // within this half
+            const int gj = gc[h * 64 + col];
+            const float ij = invc[h * 64 + col];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const int row = wq * 64 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+              const bool ok = gj >= 0 && gj != gq[row];
+              const float s = __fmul_rn(__fmul_rn(acc[a][b][e], invq[row]), ij);
+              stage[(size_t)row * KT_SLD + col] = ok ? s : __builtin_nanf("");
+            }
+          }
+      }
+      __syncthreads();
+      if (owner) {
+        const float* srow = stage + (size_t)t * KT_SLD;
+        const int jbase = c0 + h * 64;
+        for (int c = 0; c < 64; ++c) {
+          const float s = srow[c];
+          const int j = jbase + c;
+          if (!(s == s)) continue;
+          if (cnt == k && !kt_better(s, j, thr_s, thr_j)) continue;
+          int p = cnt < k ? cnt++ : k - 1;        // a full list drops its last entry
+          while (p > 0) {
+            const float sp = ls[(size_t)(p - 1) * KT_TQ + t];
+            const int jp = li[(size_t)(p - 1) * KT_TQ + t];
+            if (!kt_better(s, j, sp, jp)) break;
+            ls[(size_t)p * KT_TQ + t] = sp;
+            li[(size_t)p * KT_TQ + t] = jp;
+            --p;
+          }
+          ls[(size_t)p * KT_TQ + t] = s;
+          li[(size_t)p * KT_TQ + t] = j;
+          if (cnt == k) {
+            thr_s = ls[(size_t)(k - 1) * KT_TQ + t];
+            thr_j = li[(size_t)(k - 1) * KT_TQ + t];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  if (owner) {
+    const size_t base = ((size_t)blockIdx.y * N + (size_t)(q0 + t)) * k;
+    for (int p = 0; p < cnt; ++p) {
+      psim[base + p] = ls[(size_t)p * KT_TQ + t];
+      pidx[base + p] = li[(size_t)p * KT_TQ + t];
+    }
+    pcnt[(size_t)blockIdx.y * N + q0 + t] = cnt;
+  }
+}
+
+// merges the splits' sorted lists of every row; writes every slot of idx / sim and cnt
+__global__ __launch_bounds__(256) void knn_merge_kernel(const int* __restrict__ pidx, const float* __restrict__ psim,
+                                                        const int* __restrict__ pcnt, int N, int k, int splits, int* __restrict__ idx,
+                                                        float* __restrict__ sim, int* __restrict__ cnt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  int head[KT_MAX_SPLITS], len[KT_MAX_SPLITS];
+#pragma unroll
+  for (int s = 0; s < KT_MAX_SPLITS; ++s) {
+    head[s] = 0;
+    len[s] = s < splits ? pcnt[(size_t)s * N + i] : 0;
+  }
+  int total = 0;
+  for (int p = 0; p < k; ++p) {
+    int best = -1, bj = 0;
+    float bs = 0.f;
+#pragma unroll
+    for (int s = 0; s < KT_MAX_SPLITS; ++s) {
+      if (head[s] < len[s]) {
+        const size_t at = ((size_t)s * N + i) * k + head[s];
+        const float v = psim[at];
+        const int j = pidx[at];
+        if (best < 0 || kt_better(v, j, bs, bj)) {
+          best = s;
+          bs = v;
+          bj = j;
+        }
+      }
+    }
+    if (best >= 0) {
+#pragma unroll
+      for (int s = 0; s < KT_MAX_SPLITS; ++s) head[s] += (s == best);
+      ++total;
+    }
+    idx[(size_t)i * k + p] = best >= 0 ? bj : -1;
+    sim[(size_t)i * k + p] = best >= 0 ? bs : -INFINITY;
+  }
+  cnt[i] = total;
+}
+
+// ------------------------------------------------------------------ (c) majority vote: most frequent label, ties to the smallest
+#define KV_THREADS 64
+__global__ __launch_bounds__(KV_THREADS) void knn_vote_kernel(const int* __restrict__ idx, const int* __restrict__ cnt,
+                                                              const int* __restrict__ labels, int N, int k, int* __restrict__ pred) {
+  __shared__ int lab[KT_MAX_K][KV_THREADS];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * KV_THREADS + tid;
+  if (i >= N) return;
+  const int c = min(cnt[i], k);
+  for (int q = 0; q < c; ++q) lab[q][tid] = labels[idx[(size_t)i * k + q]];
+  int best_n = 0, best_l = -1;
+  for (int p = 0; p < c; ++p) {
+    const int l = lab[p][tid];
+    int n = 0;
+    for (int q = 0; q < c; ++q) n += lab[q][tid] == l;
+    if (n > best_n || (n == best_n && l < best_l)) {
+      best_n = n;
+      best_l = l;
+    }
+  }
+  pred[i] = best_l;
+}
+
+// ------------------------------------------------------------------ host
+static int kt_range(const char* who, int64_t N, int64_t d, int64_t k) {
+  VSX_CHECK(N >= 1 && N <= (1 << 30), "%s: N=%ld must be in [1, 2^30]", who, (long)N);
+  VSX_CHECK(d >= 1 && d <= (1 << 20), "%s: d=%ld must be in [1, 2^20]", who, (long)d);
+  VSX_CHECK(k >= 1 && k <= KT_MAX_K, "%s: k=%ld must be in [1, %d]", who, (long)k, KT_MAX_K);
+  return 0;
+}
+
+extern "C" int32_t vsx_row_inv_norm(const float* x, float* inv, int32_t N, int32_t d, float eps, vsx_stream_t stream) {
+  VSX_CHECK(x && inv && N >= 1 && d >= 1, "vsx_row_inv_norm: bad arguments");
+  hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, inv, N, d, eps);
+  VSX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int64_t vsx_knn_topk_ws_bytes(int32_t N, int32_t d, int32_t k) {
+  if (N < 1 || d < 1 || k < 1 || k > KT_MAX_K) return 0;
+  return (int64_t)KT_MAX_SPLITS * N * ((int64_t)k * 8 + 4);  // per split: idx[N][k], sim[N][k], cnt[N]
+}
+
+// how many workgroups share the candidate range of one query tile: the count in 1 .. KT_MAX_SPLITS that leaves the fewest idle
+// workgroup slots in the last round (two workgroups per compute unit), the smaller count on a tie
+static int kt_splits(int qtiles, int ctiles, int cus) {
+  const long slots = 2L * (cus > 0 ? cus : 256);
+  int best = 1;
+  double best_eff = 0.0;
+  for (int s = 1; s <= KT_MAX_SPLITS && s <= ctiles; ++s) {
+    const int tps = (ctiles + s - 1) / s;
+    if ((long)(s - 1) * tps >= ctiles) continue;  // the last split would be empty
+    const long wgs = (long)qtiles * s;
+    const double eff = (double)wgs / (double)(((wgs + slots - 1) / slots) * slots);
+    if (eff > best_eff * 1.02) {
+      best_eff = eff;
+      best = s;
+    }
+  }
+  return best;
+}
+
+extern "C" int32_t vsx_knn_topk(const float* x, const float* inv, const int32_t* group, int32_t N, int32_t d, int32_t k, int32_t* idx,
+                                float* sim, int32_t* cnt, void* ws, int64_t ws_bytes, vsx_stream_t stream) {
+  if (int rc = kt_range("vsx_knn_topk", N, d, k)) return rc;
+  VSX_CHECK(x && inv && group && idx && sim && cnt && ws, "vsx_knn_topk: null argument");
+  VSX_CHECK(ws_bytes >= vsx_knn_topk_ws_bytes(N, d, k) && ((uintptr_t)ws & 3) == 0,
+            "vsx_knn_topk: the workspace must be 4-byte aligned and hold vsx_knn_topk_ws_bytes = %ld bytes (got %ld)",
+            (long)vsx_knn_topk_ws_bytes(N, d, k), (long)ws_bytes);
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+      cus = n;
+    else
+      cus = 256;
+  }
+  const int qtiles = (N + KT_TQ - 1) / KT_TQ, ctiles = (N + KT_TC - 1) / KT_TC;
+  const int splits = kt_splits(qtiles, ctiles, cus);
+  const int tps = (ctiles + splits - 1) / splits;
+  int* pidx = (int*)ws;
+  float* psim = (float*)(pidx + (size_t)splits * N * k);
+  int* pcnt = (int*)(psim + (size_t)splits * N * k);
+  const bool vec = d % 4 == 0 && ((uintptr_t)x & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)qtiles, (unsigned)splits), block(KT_THREADS);
+#define KT_GO(VEC, KB) hipLaunchKernelGGL((knn_topk_kernel<VEC, KB>), grid, block, 0, s, x, inv, group, N, d, k, tps, pidx, psim, pcnt)
+  if (k <= 8) {
+    if (vec) KT_GO(true, 8); else KT_GO(false, 8);
+  } else if (k <= 24) {
+    if (vec) KT_GO(true, 24); else KT_GO(false, 24);
+  } else {
+    if (vec) KT_GO(true, 64); else KT_GO(false, 64);
+  }
+#undef KT_GO
+  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const int*)pidx, (const float*)psim,
+                     (const int*)pcnt, N, k, splits, idx, sim, cnt);
+  VSX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t vsx_knn_vote(const int32_t* idx, const int32_t* cnt, const int32_t* labels, int32_t N, int32_t k, int32_t* pred,
+                                vsx_stream_t stream) {
+  if (int rc = kt_range("vsx_knn_vote", N, 1, k)) return rc;
+  VSX_CHECK(idx && cnt && labels && pred, "vsx_knn_vote: null argument");
+  hipLaunchKernelGGL(knn_vote_kernel, dim3((unsigned)((N + KV_THREADS - 1) / KV_THREADS)), dim3(KV_THREADS), 0, (hipStream_t)stream,
+                     idx, cnt, labels, N, k, pred);
+  VSX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t vsx_pair_cosine_dist(const float* x, const float* inv, const int32_t* pi, const int32_t* pj, int64_t P, int32_t d,
+                                        float* out, vsx_stream_t stream) {
+  VSX_CHECK(x && inv && pi && pj && out && d >= 1, "vsx_pair_cosine_dist: bad arguments");
+  VSX_CHECK(P >= 1 && P < (1L << 33), "vsx_pair_cosine_dist: P=%ld must be in [1, 2^33)", (long)P);
+  hipLaunchKernelGGL(pair_cosine_dist_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, inv, pi, pj,
+                     (long)P, d, out);
+  VSX_LAUNCH_CHECK();
+  return 0;
+}

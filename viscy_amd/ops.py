@@ -1140,3 +1140,77 @@ def c3_from_cl(y: Tensor, B: int, spatial: Sequence[int]) -> Tensor:
     S = out[0, 0].numel()
     check(lib().vsx_conv3d_from_cl(ptr(y), ptr(out), B, C, S, dtype_code(y.dtype), stream()), "conv3d_from_cl")
     return out
+
+
+# ------------------------------------------------------------------ OnlineEvalCallback (csrc/online_eval.hip)
+KNN_MAX_K = 64
+
+
+def _rows_f32(x: Tensor, what: str) -> tuple[int, int]:
+    ptr(x)  # raises for a CPU or non-contiguous tensor
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise TypeError(f"{what}: features must be a float32 (N, d) tensor, got {x.dtype} {tuple(x.shape)}")
+    return x.shape[0], x.shape[1]
+
+
+def _i32(t: Tensor, n: int, what: str) -> Tensor:
+    ptr(t)
+    if t.dtype != torch.int32 or t.numel() != n:
+        raise TypeError(f"{what} must be {n} int32 values, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def row_inv_norm(x: Tensor, eps: float = 0.0) -> Tensor:
+    """inv[i] = 1 / (||x_i||_2 + eps); 0 where that denominator is 0 (an all-zero row with eps = 0, as sklearn's ``normalize``)"""
+    n, d = _rows_f32(x, "row_inv_norm")
+    inv = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(lib().vsx_row_inv_norm(ptr(x), ptr(inv), n, d, eps, stream()), "row_inv_norm")
+    return inv
+
+
+def knn_topk(x: Tensor, inv: Tensor, group: Tensor, k: int):
+    """-> (idx (N, k) int32, sim (N, k) float32, cnt (N,) int32): for every row its min(k, #candidates) most similar rows of the
+    OTHER groups (``group[j] >= 0 and group[j] != group[i]``), s = fl32(fl32(dot * inv_i) * inv_j), in the total order
+    (s descending, j ascending); unused slots idx = -1, sim = -inf.  No N x N buffer: the workspace is O(N k)."""
+    n, d = _rows_f32(x, "knn_topk")
+    if inv.dtype != torch.float32 or inv.numel() != n:
+        raise TypeError(f"knn_topk: inv must be {n} float32 values")
+    _i32(group, n, "knn_topk: group")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:  # the library refuses it too; here before anything is allocated
+        raise ValueError(f"knn_topk: k={k} must be in [1, {KNN_MAX_K}]")
+    nbytes = int(lib().vsx_knn_topk_ws_bytes(n, d, k))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=x.device)
+    idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
+    sim = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    cnt = torch.empty(n, dtype=torch.int32, device=x.device)
+    check(lib().vsx_knn_topk(ptr(x), ptr(inv), ptr(group), n, d, k, ptr(idx), ptr(sim), ptr(cnt), ptr(ws), ws.numel() * 4, stream()),
+          "knn_topk")
+    return idx, sim, cnt
+
+
+def knn_vote(idx: Tensor, cnt: Tensor, labels: Tensor) -> Tensor:
+    """pred[i] = the most frequent of labels[idx[i, :cnt[i]]], ties to the smallest label; -1 where cnt[i] = 0"""
+    ptr(idx)
+    if idx.dtype != torch.int32 or idx.dim() != 2:
+        raise TypeError("knn_vote: idx must be an int32 (N, k) tensor")
+    n, k = idx.shape
+    _i32(cnt, n, "knn_vote: cnt")
+    _i32(labels, labels.numel(), "knn_vote: labels")
+    pred = torch.empty(n, dtype=torch.int32, device=idx.device)
+    check(lib().vsx_knn_vote(ptr(idx), ptr(cnt), ptr(labels), n, k, ptr(pred), stream()), "knn_vote")
+    return pred
+
+
+def pair_cosine_dist(x: Tensor, inv: Tensor, pi: Tensor, pj: Tensor) -> Tensor:
+    """out[p] = 1 - fl32(fl32(dot(x[pi[p]], x[pj[p]]) * inv[pi[p]]) * inv[pj[p]])"""
+    n, d = _rows_f32(x, "pair_cosine_dist")
+    if inv.dtype != torch.float32 or inv.numel() != n:
+        raise TypeError(f"pair_cosine_dist: inv must be {n} float32 values")
+    p = pi.numel()
+    _i32(pi, p, "pair_cosine_dist: pi")
+    _i32(pj, p, "pair_cosine_dist: pj")
+    out = torch.empty(p, dtype=torch.float32, device=x.device)
+    if p:
+        check(lib().vsx_pair_cosine_dist(ptr(x), ptr(inv), ptr(pi), ptr(pj), p, d, ptr(out), stream()), "pair_cosine_dist")
+    return out

@@ -33,6 +33,7 @@ class Trainer:
         self.limit_train_batches = limit_train_batches
         self.finished = False
         self.global_step = 0
+        self.current_epoch, self.sanity_checking, self.global_rank, self.world_size = 0, False, 0, 1
         self.graph_step = graph_step   # False: always the eager zero_grad / training_step / backward / step loop
         self.graph_steps = 0           # optimisation steps taken through the captured TrainStep (tests, logs)
         self._train_steps: dict = {}   # batch signature -> TrainStep
@@ -110,6 +111,13 @@ class Trainer:
             hits[key] = hits.get(key, 0) + 1
         return step
 
+    def _call_hook(self, name: str, module, *args) -> None:
+        """Lightning's callback hooks of the validation loop, on every callback that has them (none by default)"""
+        for cb in self.callbacks:
+            fn = getattr(cb, name, None)
+            if fn is not None:
+                fn(self, module, *args)
+
     def fit(self, module, datamodule) -> None:
         module.to(self.device)
         module.trainer = self
@@ -133,7 +141,12 @@ class Trainer:
         use_bf16 = self.precision.startswith("bf16") and self.device.type == "cuda"
         from .data.combined import CombinedLoader
 
+        # what Lightning callbacks read off the trainer (OnlineEvalCallback: the epoch gate, the rank-0 log lines, the gather)
+        self.sanity_checking = False
+        self.global_rank = dist.get_rank() if dist.is_initialized() else 0
+        self.world_size = dist.get_world_size() if dist.is_initialized() else 1
         for epoch in range(1 if self.fast_dev_run else self.max_epochs):
+            self.current_epoch = epoch
             module.train()
             datamodule.training = True
             if hasattr(module, "on_train_epoch_start"):
@@ -167,10 +180,12 @@ class Trainer:
                         ddp.finish()
                     opt.step()
                 self.global_step += 1
-            module.on_train_epoch_end()
+            if hasattr(module, "on_train_epoch_end"):  # ContrastiveModule has none
+                module.on_train_epoch_end()
             module.eval()
             datamodule.training = False
             with torch.no_grad():
+                self._call_hook("on_validation_epoch_start", module)
                 val_dl = datamodule.val_dataloader()
                 for j, batch in enumerate(val_dl):
                     di = 0
@@ -178,11 +193,14 @@ class Trainer:
                         batch, j, di = batch
                     batch = datamodule.on_after_batch_transfer(self._to_device(batch), di)
                     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_bf16):
-                        module.validation_step(batch, j, di)
+                        out = module.validation_step(batch, j, di)
+                    self._call_hook("on_validation_batch_end", module, out, batch, j, di)
                     if self.fast_dev_run:
                         break
+                self._call_hook("on_validation_epoch_end", module)
             datamodule.training = True
-            module.on_validation_epoch_end()
+            if hasattr(module, "on_validation_epoch_end"):
+                module.on_validation_epoch_end()
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         self.finished = True
