@@ -769,6 +769,34 @@ int32_t vsx_knn_vote(const int32_t* idx, const int32_t* cnt, const int32_t* labe
 int32_t vsx_pair_cosine_dist(const float* x, const float* inv, const int32_t* pi, const int32_t* pj, int64_t P, int32_t d, float* out,
     vsx_stream_t stream);
 
+/* ClassificationHead's classifier + cross-entropy (csrc/aux_head.hip; heads.py:159-272, 420-453); fp32 throughout, dot products
+ * on the exact f32 MFMA.  h [B, H], W [C, H], labels [B] int64.  Cosine classifier: inv_h [B], inv_w [C] from vsx_cls_inv_norm
+ * (inv = 1 / max(||x||, 1e-12), F.normalize's rule: a zero row gives zero logits and finite gradients) and the device scalar
+ * log_scale; bias must be null.  Linear: inv_h = inv_w = log_scale = null, bias [C] or null.
+ *   cosine  z_bc = fl32(fl32(fl32(dot_bc * inv_h[b]) * inv_w[c]) * expf(log_scale[0]));   linear  z_bc = fl32(dot_bc + bias[c])
+ * vsx_cls_ce_fwd: rows [B, 4] = {lse, target logit, rank, valid}, acc [4] = {loss, top-1, top-k, n_valid}; rank = the number of
+ * classes ahead of the target in the total order (logit descending, class ascending), a top-k hit is rank < k; loss =
+ * sum_valid (lse - z_y) / n_valid, top-1 / top-k are divided by B.  No [B, C] buffer, no atomics; rows and acc are bit-identical
+ * from run to run and for every `splits` (how many workgroups share the class range of 128 rows; 0 = chosen by the library).
+ * Label -100 = ignore_index: valid = 0, the row counts in no sum and has exactly zero gradient (all ignored: loss NaN).  Any other
+ * label outside [0, C) never indexes memory: valid = -1 and the loss is NaN.  Non-finite logits reach the loss as in torch.
+ * vsx_cls_logits: Z [B, C], the same logits materialised (inference).
+ * vsx_cls_ce_bwd: dh [B, H] = gout[0] * d loss / d h (written); dW [C, H], dbias [C] (linear, may be null), dlog_scale [1]
+ * (cosine) are ACCUMULATED into; the two normalisations' backward is included.  All gradients are sums in a fixed order:
+ * bit-reproducible.  Served: H % 4 == 0, 1 <= k <= C, any C >= 1 and B >= 1; h, W, dh, dW 16-byte aligned; anything else is
+ * refused with a non-zero status and no launch.  Workspaces: any contents, vsx_cls_ce_{fwd,bwd}_ws_bytes. */
+int32_t vsx_cls_inv_norm(const float* x, float* inv, int32_t N, int32_t d, vsx_stream_t stream);
+int64_t vsx_cls_ce_fwd_ws_bytes(int32_t B, int32_t H, int32_t C);
+int32_t vsx_cls_ce_fwd(const float* h, const float* W, const int64_t* labels, const float* inv_h, const float* inv_w,
+    const float* log_scale, const float* bias, int32_t B, int32_t H, int32_t C, int32_t k, int32_t splits, float* rows, float* acc,
+    void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int32_t vsx_cls_logits(const float* h, const float* W, const float* inv_h, const float* inv_w, const float* log_scale,
+    const float* bias, int32_t B, int32_t H, int32_t C, float* Z, vsx_stream_t stream);
+int64_t vsx_cls_ce_bwd_ws_bytes(int32_t B, int32_t H, int32_t C);
+int32_t vsx_cls_ce_bwd(const float* h, const float* W, const int64_t* labels, const float* inv_h, const float* inv_w,
+    const float* log_scale, const float* bias, const float* rows, const float* acc, const float* gout, int32_t B, int32_t H,
+    int32_t C, float* dh, float* dW, float* dbias, float* dlog_scale, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

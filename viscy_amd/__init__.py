@@ -5,7 +5,7 @@
 See DESIGN.md (what is built and why) and INTEGRATION.md (how it binds to the reference).
 """
 
-__all__ = ["UNeXt2", "MixedLoss", "VSUNet", "HCSDataModule", "HCSPredictionWriter", "FcmaeUNet", "FullyConvolutionalMAE", "MaskedMSELoss", "SpotlightLoss", "ContrastiveEncoder", "ContrastiveModule", "NTXentLoss", "NTXentHCL", "TripletMarginLoss", "OnlineEvalCallback", "FlatAdamW", "FlatDataParallel", "TrainStep"]
+__all__ = ["UNeXt2", "MixedLoss", "VSUNet", "HCSDataModule", "HCSPredictionWriter", "FcmaeUNet", "FullyConvolutionalMAE", "MaskedMSELoss", "SpotlightLoss", "ContrastiveEncoder", "ContrastiveModule", "NTXentLoss", "NTXentHCL", "TripletMarginLoss", "ClassificationHead", "OnlineEvalCallback", "FlatAdamW", "FlatDataParallel", "TrainStep"]
 
 
 def __getattr__(name):
@@ -25,6 +25,8 @@ def __getattr__(name):
         from . import contrastive as _c
 
         v = getattr(_c, name)
+    elif name == "ClassificationHead":
+        from .heads import ClassificationHead as v
     elif name == "OnlineEvalCallback":
         from .online_eval import OnlineEvalCallback as v
     elif name == "VSUNet":

@@ -206,6 +206,12 @@ _SIGS = {
     "vsx_knn_topk": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "vsx_knn_vote": (_I32, [_P, _P, _P, _I32, _I32, _P, _P]),
     "vsx_pair_cosine_dist": (_I32, [_P, _P, _P, _P, _I64, _I32, _P, _P]),
+    "vsx_cls_inv_norm": (_I32, [_P, _P, _I32, _I32, _P]),
+    "vsx_cls_ce_fwd_ws_bytes": (_I64, [_I32, _I32, _I32]),
+    "vsx_cls_ce_fwd": (_I32, [_P] * 7 + [_I32] * 5 + [_P, _P, _P, _I64, _P]),
+    "vsx_cls_logits": (_I32, [_P] * 6 + [_I32] * 3 + [_P, _P]),
+    "vsx_cls_ce_bwd_ws_bytes": (_I64, [_I32, _I32, _I32]),
+    "vsx_cls_ce_bwd": (_I32, [_P] * 10 + [_I32] * 3 + [_P] * 5 + [_I64, _P]),
 }
 
 _lib = None

@@ -49,6 +49,13 @@ CLASS_MAP = {
     "viscy_models.contrastive.loss.NTXentHCL": "viscy_amd.contrastive.NTXentHCL",
     "torch.nn.TripletMarginLoss": "viscy_amd.contrastive.TripletMarginLoss",  # dynaclr.engine.ContrastiveModule's default loss
     "torch.nn.modules.loss.TripletMarginLoss": "viscy_amd.contrastive.TripletMarginLoss",
+    "viscy_models.components.heads.ClassificationHead": "viscy_amd.heads.ClassificationHead",  # auxiliary_heads of the OPS recipes
+    "viscy_models.components.ClassificationHead": "viscy_amd.heads.ClassificationHead",
+    "viscy_models.components.heads.BaseHead": "viscy_amd.heads.BaseHead",
+    "viscy_models.components.BaseHead": "viscy_amd.heads.BaseHead",
+    "viscy_models.components.heads.CosineClassifier": "viscy_amd.heads.CosineClassifier",
+    "viscy_models.components.heads.MLP": "viscy_amd.heads.MLP",  # classification mode; projection mode refuses itself
+    "viscy_models.components.heads.CrossModalContrastiveHead": "viscy_amd.heads.CrossModalContrastiveHead",  # refuses itself
     "viscy_models.unet.UNeXt2": "viscy_amd.unext2.UNeXt2",
     "viscy_models.unet.unext2.UNeXt2": "viscy_amd.unext2.UNeXt2",
     "viscy_models.unet.FullyConvolutionalMAE": "viscy_amd.fcmae.FullyConvolutionalMAE",

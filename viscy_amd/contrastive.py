@@ -20,9 +20,15 @@ Built: ``backbone="convnext_tiny"`` (V1 blocks: layer scale ``gamma`` folded int
 ``pretrained`` must be False (no network here); ``drop_path_rate`` is timm's linear stochastic-depth schedule (training mode).  BatchNorm is per process
 under data parallelism, as in the reference's default (no SyncBatchNorm in its recipes' trainer sections).
 
+``auxiliary_heads`` (``viscy_amd.heads.ClassificationHead``, the ``OPS-*`` recipes' gene classifier) run on the anchor's
+embedding in the training and validation steps: total = contrastive + sum of weight * head loss, the head's gradient of the
+embedding goes back through the trunk with the projection's, the heads' parameters live in a flat buffer of their own that the
+module's one optimiser updates with the encoder's (one step count, one schedule).  The captured step (``make_train_step``) is
+for modules without heads.
+
 Not built: ``TripletMarginLoss`` with ``swap=True``, ``p != 2`` or ``reduction="none"``; ``nn.CosineEmbeddingLoss``; the
-negative-pair matrices that the reference's ``_log_metrics`` adds for NT-Xent; auxiliary heads, image / PCA logging,
-``freeze_backbone``.
+negative-pair matrices that the reference's ``_log_metrics`` adds for NT-Xent; a replacement ``projection``; image / PCA
+logging, ``freeze_backbone``.
 """
 
 from __future__ import annotations
@@ -255,16 +261,30 @@ class ContrastiveModule(nn.Module):
     (``anchor``, ``positive`` and, for the triplet branch, ``negative``), ``predict_step`` -> features / projections,
     ``on_train_epoch_start`` temperature schedule, ``configure_optimizers`` -> fused flat AdamW.  ``loss_function``: the
     NT-Xent family (the default here) or ``TripletMarginLoss`` (the reference's default; a ``torch.nn.TripletMarginLoss``
-    instance is converted).  The cosine-embedding loss, auxiliary heads and image / PCA logging are not built."""
+    instance is converted), ``auxiliary_heads``: ``{name: viscy_amd.heads.ClassificationHead}``.  The cosine-embedding loss, a
+    replacement ``projection`` and image / PCA logging are not built."""
 
     def __init__(self, encoder: ContrastiveEncoder, loss_function: nn.Module | None = None, lr: float = 1e-3,
                  schedule: Literal["WarmupCosine", "Constant"] = "Constant", log_batches_per_epoch: int = 8,
                  log_samples_per_batch: int = 1, example_input_array_shape: Sequence[int] = (1, 2, 15, 256, 256),
-                 ckpt_path: str | None = None, freeze_backbone: bool = False, gather_embeddings: bool = False, **unused) -> None:
+                 ckpt_path: str | None = None, freeze_backbone: bool = False, gather_embeddings: bool = False,
+                 projection: nn.Module | None = None, auxiliary_heads: dict | None = None, **unused) -> None:
         super().__init__()
         if freeze_backbone:
             raise NotImplementedError("freeze_backbone is not built (the fused flat-buffer optimiser updates every parameter)")
+        if projection is not None:
+            raise NotImplementedError("projection: replacing the encoder's projection MLP is not built (the embedding tail is "
+                                      "part of the encoder's kernel schedule)")
         self.model = encoder
+        from .heads import BaseHead, ClassificationHead
+
+        for name, head in (auxiliary_heads or {}).items():
+            if not isinstance(head, BaseHead):
+                raise TypeError(f"auxiliary_heads[{name!r}] must be a viscy_amd.heads.BaseHead, got {type(head).__name__}")
+            if not isinstance(head, ClassificationHead):
+                raise NotImplementedError(f"auxiliary_heads[{name!r}]: {type(head).__name__} is not built (ClassificationHead is)")
+        self.auxiliary_heads = nn.ModuleDict(auxiliary_heads or {})
+        self._heads_engine = None
         if isinstance(loss_function, nn.TripletMarginLoss):  # the reference's default / YAML class_path
             loss_function = TripletMarginLoss.from_torch(loss_function)
         self.loss_function = loss_function if loss_function is not None else NTXentLoss()
@@ -300,6 +320,10 @@ class ContrastiveModule(nn.Module):
         ``step(anchor, positive, negative) -> loss``"""
         from .step import TrainStep
 
+        if len(self.auxiliary_heads):
+            raise NotImplementedError("auxiliary heads run on the eager step (training_step / Trainer.fit): the captured step "
+                                      "carries (anchor, positive[, negative]) and no labels")
+
         def loss_fn(anchor, other):
             batch = {"anchor": anchor, "positive": other}
             if self.triplet:  # TrainStep carries two tensors: (positive, negative) travel stacked
@@ -320,6 +344,56 @@ class ContrastiveModule(nn.Module):
             self.loss_function.step(self.current_epoch)
         if hasattr(self.loss_function, "temperature"):
             self._log("hparams/temperature", self.loss_function.temperature)
+        for head in self.auxiliary_heads.values():
+            head.step(self.current_epoch)
+            self._log(f"hparams/loss_weight/{head.head_name}", head.get_weight())
+
+    # ------------------------------------------------------------------ auxiliary heads (engine.py:227-260)
+    def heads_engine(self, ops=None):
+        """the ``AuxHeadsEngine`` over all heads of this module (one flat fp32 parameter / gradient buffer); None without heads"""
+        heads = list(self.auxiliary_heads.values())
+        if not heads:
+            return None
+        from .heads import AuxHeadsEngine
+
+        eng = self._heads_engine
+        dev = next(self.auxiliary_heads.parameters()).device
+        if eng is None or eng.device != dev or (ops is not None and eng.ops is not ops) or any(h._engine is not eng for h in heads):
+            eng = self._heads_engine = AuxHeadsEngine(self.auxiliary_heads, ops)
+        return eng
+
+    def _get_labels(self, batch: dict, batch_key: str) -> Tensor | None:
+        """a top-level batch key first, then ``anchor_meta[i]["labels"][batch_key]`` as a long tensor; None where neither has it"""
+        if batch_key in batch:
+            y = batch[batch_key]
+        else:
+            meta = batch.get("anchor_meta")
+            if not meta or "labels" not in meta[0] or batch_key not in meta[0]["labels"]:
+                return None
+            vals = [m["labels"][batch_key] for m in meta]
+            if isinstance(vals[0], (list, tuple)) or getattr(vals[0], "ndim", 0) > 0:   # the reference stacks these as floats
+                raise NotImplementedError(f"vector-valued labels ({batch_key!r}) belong to CrossModalContrastiveHead, which is not built")
+            y = torch.tensor([int(v) for v in vals], dtype=torch.long, device=batch["anchor"].device)
+        if not torch.is_tensor(y) or y.ndim != 1 or y.is_floating_point():
+            raise NotImplementedError(f"vector-valued labels ({batch_key!r}) belong to CrossModalContrastiveHead, which is not built")
+        return y
+
+    def _run_auxiliary_heads(self, anchor_features: Tensor, batch: dict, stage: str) -> Tensor | None:
+        """sum of weight * loss over the heads whose labels the batch carries (None if there is none), logging each head's
+        loss and accuracies"""
+        aux = None
+        if len(self.auxiliary_heads):
+            self.heads_engine()
+        for head in self.auxiliary_heads.values():
+            y = self._get_labels(batch, head.batch_key)
+            if y is None:
+                continue
+            head_loss, stats = head.loss_and_stats(anchor_features, y)
+            term = head.get_weight() * head_loss
+            aux = term if aux is None else aux + term
+            if self._logging:
+                head.log_metrics({"loss": head_loss, "stats": stats}, self._log, stage)
+        return aux
 
     def forward(self, x: Tensor) -> tuple[Tensor, Tensor]:
         return self.model(x)
@@ -331,10 +405,11 @@ class ContrastiveModule(nn.Module):
         if self.paired_forward and views[0].shape == views[1].shape == views[2].shape:
             # one trunk pass over [anchor; positive; negative]; BatchNorm statistics and running-statistics updates per view,
             # in this order, as the reference's three calls make them (dynaclr/engine.py:265-266,276)
-            _, proj = self.model.forward_groups(torch.cat(views), 3)
-            projections = proj.chunk(3)
+            emb, proj = self.model.forward_groups(torch.cat(views), 3)
+            projections, anchor_features = proj.chunk(3), emb[: views[0].shape[0]]
         else:
-            projections = tuple(self(v)[1] for v in views)
+            outs = tuple(self(v) for v in views)
+            projections, anchor_features = tuple(o[1] for o in outs), outs[0][0]
         loss = self.loss_function(*projections)
         self._log(f"loss/{stage}", loss)
         if self._logging:  # engine.py:135-146, from the sums the loss kernels formed anyway
@@ -343,7 +418,8 @@ class ContrastiveModule(nn.Module):
             self._log(f"metrics/euclidean_distance/positive/{stage}", st[2])
             self._log(f"metrics/cosine_similarity_negative/{stage}", st[3])
             self._log(f"metrics/euclidean_distance_negative/{stage}", st[4])
-        return loss
+        aux = self._run_auxiliary_heads(anchor_features, batch, stage)
+        return loss if aux is None else loss + aux
 
     def _step(self, batch: dict, stage: str) -> Tensor:
         if self.triplet:
@@ -351,10 +427,11 @@ class ContrastiveModule(nn.Module):
         a, p_ = batch["anchor"], batch["positive"]
         if self.paired_forward and a.shape == p_.shape:
             # one trunk pass over [anchor; positive]; BatchNorm statistics stay per call (dynaclr/engine.py:265-266)
-            _, proj = self.model.forward_groups(torch.cat((a, p_)), 2)
+            emb, proj = self.model.forward_groups(torch.cat((a, p_)), 2)
             anchor_projection, positive_projection = proj[: a.shape[0]], proj[a.shape[0]:]
+            anchor_features = emb[: a.shape[0]]
         else:
-            _, anchor_projection = self(a)
+            anchor_features, anchor_projection = self(a)
             _, positive_projection = self(p_)
         if self.gather_embeddings:
             from .parallel import all_gather_with_local_grad, scale_for_mean_reduction
@@ -366,7 +443,8 @@ class ContrastiveModule(nn.Module):
         self._log(f"loss/{stage}", loss)
         if self.gather_embeddings:
             loss = scale_for_mean_reduction(loss)
-        return loss
+        aux = self._run_auxiliary_heads(anchor_features, batch, stage)  # a mean over the local batch already: added unscaled
+        return loss if aux is None else loss + aux
 
     def training_step(self, batch: dict, batch_idx: int) -> Tensor:
         return self._step(batch, "train")
@@ -382,4 +460,12 @@ class ContrastiveModule(nn.Module):
         from .optim import FlatAdamW
 
         self.model.grad_mode = "flat"
-        return FlatAdamW(self.model.engine(), lr=self.lr, schedule=self.schedule, t_total=t_total or 0)
+        heads = self.heads_engine()
+        if heads is None:
+            return FlatAdamW(self.model.engine(), lr=self.lr, schedule=self.schedule, t_total=t_total or 0)
+        from .optim import MultiFlatAdamW
+
+        for head in self.auxiliary_heads.values():
+            head.grad_mode = "flat"
+        # AdamW(self.parameters(), lr) of the reference: one step count and one schedule over the encoder's and the heads' buffers
+        return MultiFlatAdamW(self.model.engine(), [heads], lr=self.lr, schedule=self.schedule, t_total=t_total or 0)

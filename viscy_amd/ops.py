@@ -1214,3 +1214,74 @@ def pair_cosine_dist(x: Tensor, inv: Tensor, pi: Tensor, pj: Tensor) -> Tensor:
     if p:
         check(lib().vsx_pair_cosine_dist(ptr(x), ptr(inv), ptr(pi), ptr(pj), p, d, ptr(out), stream()), "pair_cosine_dist")
     return out
+
+
+# ------------------------------------------------------------------ ClassificationHead: classifier + cross-entropy (csrc/aux_head.hip)
+def _cls_operands(h: Tensor, W: Tensor, inv_h, inv_w, log_scale, bias):
+    for t in (h, W):
+        ptr(t)
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise TypeError(f"cls: h and W must be float32 matrices, got {t.dtype} {tuple(t.shape)}")
+    if W.shape[1] != h.shape[1]:
+        raise ValueError(f"cls: h {tuple(h.shape)} and W {tuple(W.shape)} differ in width")
+    for t in (inv_h, inv_w, log_scale, bias):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("cls: inv_h / inv_w / log_scale / bias must be float32")
+    return h.shape[0], h.shape[1], W.shape[0]
+
+
+def cls_inv_norm(x: Tensor) -> Tensor:
+    """inv[i] = 1 / max(||x_i||_2, 1e-12): ``F.normalize``'s rule (a zero row gets 1e12 and a zero unit vector)"""
+    n, d = _rows_f32(x, "cls_inv_norm")
+    inv = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(lib().vsx_cls_inv_norm(ptr(x), ptr(inv), n, d, stream()), "cls_inv_norm")
+    return inv
+
+
+def cls_ce_fwd(h: Tensor, W: Tensor, labels: Tensor, k: int, *, inv_h: Tensor | None = None, inv_w: Tensor | None = None,
+               log_scale: Tensor | None = None, bias: Tensor | None = None, splits: int = 0):
+    """-> (rows [B, 4] = {lse, target logit, rank, valid}, acc [4] = {loss, top-1, top-k, n_valid}) of the cross-entropy over the
+    cosine (``inv_h``, ``inv_w``, ``log_scale``) or linear (``bias``) classifier's logits; no [B, C] buffer (include/vsx.h)"""
+    B, H, Cn = _cls_operands(h, W, inv_h, inv_w, log_scale, bias)
+    ptr(labels)
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise TypeError(f"cls_ce_fwd: labels must be {B} int64 values, got {labels.dtype} {tuple(labels.shape)}")
+    k = int(k)
+    if not 1 <= k <= Cn:  # the library refuses it too; here before anything is allocated
+        raise ValueError(f"cls_ce_fwd: k={k} must be in [1, C={Cn}]")
+    nbytes = int(lib().vsx_cls_ce_fwd_ws_bytes(B, H, Cn))
+    ws = torch.empty(max((nbytes + 3) // 4, 1), dtype=torch.float32, device=h.device)
+    rows = torch.empty((B, 4), dtype=torch.float32, device=h.device)
+    acc = torch.empty(4, dtype=torch.float32, device=h.device)
+    check(lib().vsx_cls_ce_fwd(ptr(h), ptr(W), ptr(labels), ptr(inv_h), ptr(inv_w), ptr(log_scale), ptr(bias), B, H, Cn, k,
+                               int(splits), ptr(rows), ptr(acc), ptr(ws), ws.numel() * 4, stream()), "cls_ce_fwd")
+    return rows, acc
+
+
+def cls_logits(h: Tensor, W: Tensor, *, inv_h: Tensor | None = None, inv_w: Tensor | None = None, log_scale: Tensor | None = None,
+               bias: Tensor | None = None) -> Tensor:
+    """the classifier's logits [B, C], materialised, with the rounding of ``cls_ce_fwd``"""
+    B, H, Cn = _cls_operands(h, W, inv_h, inv_w, log_scale, bias)
+    Z = torch.empty((B, Cn), dtype=torch.float32, device=h.device)
+    check(lib().vsx_cls_logits(ptr(h), ptr(W), ptr(inv_h), ptr(inv_w), ptr(log_scale), ptr(bias), B, H, Cn, ptr(Z), stream()),
+          "cls_logits")
+    return Z
+
+
+def cls_ce_bwd(h: Tensor, W: Tensor, labels: Tensor, rows: Tensor, acc: Tensor, gout: Tensor, dW: Tensor, *,
+               inv_h: Tensor | None = None, inv_w: Tensor | None = None, log_scale: Tensor | None = None, bias: Tensor | None = None,
+               dbias: Tensor | None = None, dlog_scale: Tensor | None = None) -> Tensor:
+    """-> dh [B, H]; ``dW`` [C, H] and ``dbias`` [C] (linear) or ``dlog_scale`` [1] (cosine) are accumulated into"""
+    B, H, Cn = _cls_operands(h, W, inv_h, inv_w, log_scale, bias)
+    for t in (dW, dbias, dlog_scale, rows, acc, gout):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("cls_ce_bwd: gradient and statistics buffers must be float32")
+    if dW.shape != W.shape:
+        raise ValueError(f"cls_ce_bwd: dW {tuple(dW.shape)} must have W's shape {tuple(W.shape)}")
+    nbytes = int(lib().vsx_cls_ce_bwd_ws_bytes(B, H, Cn))
+    ws = torch.empty(max((nbytes + 3) // 4, 4), dtype=torch.float32, device=h.device)
+    dh = torch.empty_like(h)
+    check(lib().vsx_cls_ce_bwd(ptr(h), ptr(W), ptr(labels), ptr(inv_h), ptr(inv_w), ptr(log_scale), ptr(bias), ptr(rows), ptr(acc),
+                               ptr(gout), B, H, Cn, ptr(dh), ptr(dW), ptr(dbias), ptr(dlog_scale), ptr(ws), ws.numel() * 4,
+                               stream()), "cls_ce_bwd")
+    return dh

@@ -102,3 +102,37 @@ class FlatAdamW:
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.set_step(int(sd["t"]))
+
+
+class MultiFlatAdamW(FlatAdamW):
+    """``FlatAdamW`` over the flat buffers of several engines (a module's encoder, then ``extra``: its auxiliary heads), with
+    the semantics of ONE torch ``AdamW`` over all their parameters: one device step counter, one schedule, one block of
+    hyper-parameters; one fused launch per buffer.  ``engine`` stays the first engine, for what reads it off the optimiser."""
+
+    def __init__(self, engine, extra, **kw):
+        super().__init__(engine, **kw)
+        self.extra = []
+        for eng in extra:
+            n = eng.trainable_numel()
+            self.extra.append((eng, n, torch.zeros(n, dtype=torch.float32, device=eng.flat.device),
+                               torch.zeros(n, dtype=torch.float32, device=eng.flat.device)))
+
+    def zero_grad(self) -> None:
+        super().zero_grad()
+        for eng, *_ in self.extra:
+            self.ops.fill_(eng.flat_grad, 0.0)
+            eng.reset_pending()
+
+    def device_step(self) -> None:
+        super().device_step()  # advances the counter and refreshes the hyper block once
+        for eng, n, m, v in self.extra:
+            self.ops.adamw(eng.flat[:n], eng.flat_grad[:n], m, v, self.hyper)
+
+    def state_dict(self):
+        return dict(super().state_dict(), extra=[{"m": m, "v": v} for _, _, m, v in self.extra])
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        for (_, _, m, v), e in zip(self.extra, sd.get("extra", [])):
+            m.copy_(e["m"])
+            v.copy_(e["v"])

@@ -137,6 +137,10 @@ class Trainer:
         if dist.is_initialized() and not native:
             raise NotImplementedError("data-parallel training is built for the flat-engine models (UNeXt2 / fcmae) only")
         ddp = FlatDataParallel(module.model.engine(), opt) if dist.is_initialized() else None
+        # auxiliary heads (ContrastiveModule): their flat buffer is broadcast and its gradients reduced like the encoder's; the
+        # 1 / world of the mean sits in the one optimiser's grad_scale, which covers both buffers
+        heads_engine = module.heads_engine() if hasattr(module, "heads_engine") else None
+        aux_ddp = FlatDataParallel(heads_engine) if dist.is_initialized() and heads_engine is not None else None
         self._train_steps = {}  # captured steps are bound to THIS fit's optimiser / process group
         use_bf16 = self.precision.startswith("bf16") and self.device.type == "cuda"
         from .data.combined import CombinedLoader
@@ -178,6 +182,8 @@ class Trainer:
                     loss.backward()
                     if ddp is not None:
                         ddp.finish()
+                    if aux_ddp is not None:
+                        aux_ddp.finish()
                     opt.step()
                 self.global_step += 1
             if hasattr(module, "on_train_epoch_end"):  # ContrastiveModule has none
