@@ -752,7 +752,7 @@ int32_t vsx_bn3d_bwd(const void* dy, int32_t ldy, int32_t ycoff, const void* z, 
 int32_t vsx_conv3d_to_cl(const float* x, void* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream);
 int32_t vsx_conv3d_from_cl(const void* y, float* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream);
 
-/* OnlineEvalCallback (csrc/online_eval.hip): cosine k-NN probe, neighbour vote, pair distances; fp32 throughout (exact f32 MFMA).
+/* OnlineEvalCallback (csrc/online_eval.hip + f32_tile.h): cosine k-NN probe, neighbour vote, pair distances; fp32 throughout (exact f32 MFMA).
  * row_inv_norm: inv[i] = 1 / (||x_i||_2 + eps), 0 where that denominator is 0 (an all-zero row with eps = 0).
  * knn_topk: row j is a candidate of query i iff group[j] >= 0 && group[j] != group[i]; s_ij = fl32(fl32(dot_ij * inv[i]) * inv[j]),
  * dot accumulated in fp32.  Per query: its min(k, #candidates) best candidates in the total order (s descending, j ascending) in
@@ -769,7 +769,7 @@ int32_t vsx_knn_vote(const int32_t* idx, const int32_t* cnt, const int32_t* labe
 int32_t vsx_pair_cosine_dist(const float* x, const float* inv, const int32_t* pi, const int32_t* pj, int64_t P, int32_t d, float* out,
     vsx_stream_t stream);
 
-/* ClassificationHead's classifier + cross-entropy (csrc/aux_head.hip; heads.py:159-272, 420-453); fp32 throughout, dot products
+/* ClassificationHead's classifier + cross-entropy (csrc/aux_head.hip + f32_tile.h; heads.py:159-272, 420-453); fp32 throughout, dot products
  * on the exact f32 MFMA.  h [B, H], W [C, H], labels [B] int64.  Cosine classifier: inv_h [B], inv_w [C] from vsx_cls_inv_norm
  * (inv = 1 / max(||x||, 1e-12), F.normalize's rule: a zero row gives zero logits and finite gradients) and the device scalar
  * log_scale; bias must be null.  Linear: inv_h = inv_w = log_scale = null, bias [C] or null.

@@ -137,6 +137,25 @@ def test_ops_knn_topk_matches_the_raw_call():
     assert np.array_equal(idx.cpu().numpy(), idx_r) and np.array_equal(sim.cpu().numpy(), sim_r) and np.array_equal(cnt.cpu().numpy(), cnt_r)
 
 
+def test_knn_similarities_are_the_classifier_heads_logits_bit_for_bit():
+    """csrc/f32_tile.h promises ONE summation order of a dot product for every kernel built on it.  On float rows (integer rows
+    cannot see a reordered sum) a similarity of vsx_knn_topk and a cosine logit of vsx_cls_logits over the same two rows are
+    both fl32(fl32(dot * inv_i) * inv_j) — times expf(0) = 1 on the head's side — so only the dot's order could tell them apart.
+    N = 130, d = 36: two tiles in each direction, the 64-column half boundary, one chunk plus one float4."""
+    from viscy_amd import ops
+
+    N, d, k = 130, 36, 64
+    x = torch.randn(N, d, generator=torch.Generator().manual_seed(13036)).to(DEV)
+    inv = ops.row_inv_norm(x, 0.0)
+    group = (torch.arange(N, dtype=torch.int32) % 3).to(DEV)
+    idx, sim, cnt = ops.knn_topk(x, inv, group, k)
+    Z = ops.cls_logits(x, x, inv_h=inv, inv_w=inv, log_scale=torch.zeros(1, device=DEV))
+    assert (cnt == k).all()                                                       # every row has at least 86 candidates
+    used = torch.arange(k, device=DEV)[None, :] < cnt[:, None]
+    logit = Z.gather(1, idx.clamp_min(0).long())
+    assert torch.equal(sim.view(torch.int32)[used], logit.view(torch.int32)[used])
+
+
 def test_knn_vote_against_the_restatement():
     from viscy_amd import ops
 

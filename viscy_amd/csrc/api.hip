@@ -67,6 +67,14 @@ extern "C" int32_t vsx_det_scope(int32_t on) {
   g_vsx_det_scope = on != 0;
   return prev;
 }
+int vsx_cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    const bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
+    return ok && n > 0 ? n : 256;
+  }();
+  return cus;
+}
 extern "C" int32_t vsx_det_active(void) { return vsx_det_on(); }
 extern "C" int32_t vsx_version(void) { return 1; }
 extern "C" const char* vsx_last_error(void) { return g_err; }

@@ -6,8 +6,8 @@
 //   inv(x)  = 1 / max(||x||, 1e-12)                         F.normalize's rule: a zero row has inv = 1e12 and a zero unit vector
 //   cosine:   z_bc = fl32(fl32(fl32(dot_bc * inv_h[b]) * inv_w[c]) * scale),   scale = expf(log_scale[0])
 //   linear:   z_bc = fl32(dot_bc + bias[c])                 (bias == nullptr: z_bc = dot_bc)
-//   dot_bc accumulates h[b, :] . W[c, :] in fp32, 32 features per chunk in ascending chunk order; the four lanes' order inside
-//   a chunk is the permutation of online_eval.hip, the same for every (b, c) and for every entry point of this file.
+//   dot_bc accumulates h[b, :] . W[c, :] in fp32 on the tile engine of f32_tile.h, whose one summation order holds for every
+//   (b, c) and for every entry point of this file.
 //
 // Forward (vsx_cls_ce_fwd), four launches, no atomics:
 //   (1) the target logit z_y of every row: one 128 x 128 MFMA tile per 128 rows whose class operand is the GATHERED rows
@@ -35,18 +35,11 @@
 // where a row at the 1e-12 clamp takes no projection term (the clamp's derivative, as torch).  Linear: dh = sum_c dZ W,
 // dW += dZ^T h, dbias += column sums of dZ.  Every sum has a fixed order: ALL gradients are bit-reproducible; nothing here
 // goes through the split-K GEMMs.
-#include "vsx_common.h"
+#include "f32_tile.h"
 #include "../../include/vsx.h"
 
 #include <math.h>
 
-#define CH_TQ 128
-#define CH_TC 128        // the class tile
-#define CH_KC 32
-#define CH_LD 36         // floats per staged row: 32 + 4, keeps 16-byte alignment and spreads rows over the banks
-#define CH_SLD 65        // floats per row of the logit half-tile
-#define CH_THREADS 256
-#define CH_STAGE (2 * CH_TQ * CH_LD)
 #define CH_IGNORE (-100)
 #define CH_NORM_EPS 1e-12f
 
@@ -54,10 +47,6 @@
 #define CH_DZ 1
 #define CH_LOGITS 2
 #define CH_TARGET 3
-
-typedef float ch_f32x16 __attribute__((ext_vector_type(16)));
-
-static_assert(CH_TQ * CH_SLD <= CH_STAGE, "the logit half-tile must fit the staging area");
 
 struct ChArgs {
   const float* h;          // [B, H]
@@ -70,43 +59,8 @@ struct ChArgs {
   int B, H, C;
 };
 
-// ------------------------------------------------------------------ inverse row norms, F.normalize's rule: one wave per row
-__global__ __launch_bounds__(256) void ch_inv_norm_kernel(const float* __restrict__ x, float* __restrict__ inv, int N, int d) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= N) return;
-  const float* xr = x + (size_t)row * d;
-  float ss = 0.f;
-  for (int c = lane; c < d; c += 64) ss = fmaf(xr[c], xr[c], ss);
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  if (lane == 0) inv[row] = __fdiv_rn(1.f, fmaxf(sqrtf(ss), CH_NORM_EPS));
-}
-
 __device__ __forceinline__ float ch_logit(bool cosine, float dot, float ih, float cw, float scale) {
   return cosine ? __fmul_rn(__fmul_rn(__fmul_rn(dot, ih), cw), scale) : __fadd_rn(dot, cw);
-}
-
-// one thread's share of a chunk: 8 x 4 features; f = t + 256 u -> operand f >> 10, row (f & 1023) >> 3, feature quad f & 7.
-// The class operand's row is c0 + r, or, for the target tile, the label of query row r (ylab: -1 = none, the row stays zero).
-template <bool GATHER>
-__device__ __forceinline__ void ch_fetch(float4* r, const ChArgs& a, const int* ylab, int q0, int c0, int kc0, int t) {
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int f = t + CH_THREADS * u;
-    const int g = f & 1023;
-    const int kk = kc0 + 4 * (g & 7);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* src = nullptr;
-    if (f >> 10) {
-      const int row = GATHER ? ylab[g >> 3] : c0 + (g >> 3);
-      if (row >= 0 && row < a.C) src = a.W + (size_t)row * a.H + kk;
-    } else {
-      const int row = q0 + (g >> 3);
-      if (row < a.B) src = a.h + (size_t)row * a.H + kk;
-    }
-    if (src && kk < a.H) v = *reinterpret_cast<const float4*>(src);  // H % 4 == 0 and both operands 16-byte aligned
-    r[u] = v;
-  }
 }
 
 // CH_SCAN:   in0 = zy [B];                                   out = partials [ctiles][B][3]
@@ -114,29 +68,27 @@ __device__ __forceinline__ void ch_fetch(float4* r, const ChArgs& a, const int* 
 // CH_LOGITS:                                                 out = Z [B, C]
 // CH_TARGET:                                                 out = zy [B]   (grid.y = 1, one gathered tile)
 template <int MODE>
-__global__ __launch_bounds__(CH_THREADS, 2) void ch_tile_kernel(ChArgs a, int tiles_per_split, const float* __restrict__ in0,
+__global__ __launch_bounds__(FT_THREADS, 2) void ch_tile_kernel(ChArgs a, int tiles_per_split, const float* __restrict__ in0,
                                                                 const float* __restrict__ in1, const float* __restrict__ in2,
                                                                 float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float stage[CH_STAGE];  // [2][CH_TQ][CH_LD]; later the logit half-tile [CH_TQ][CH_SLD]
-  __shared__ float invq[CH_TQ], colw[CH_TC], rowl[CH_TQ];
-  __shared__ int ylab[CH_TQ];
+  __shared__ __attribute__((aligned(16))) float stage[FT_STAGE];  // the engine's staging area; later the logit half-tile
+  __shared__ float invq[FT_T], colw[FT_T], rowl[FT_T];
+  __shared__ int ylab[FT_T];
 
-  const int t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  const int wq = wave & 1, wc = wave >> 1;      // this wave's 64 x 64 quadrant of the tile
-  const int r32 = lane & 31, hh = lane >> 5;
-  const int q0 = blockIdx.x * CH_TQ;
-  const int ntiles = (a.C + CH_TC - 1) / CH_TC;
+  const FtLane l = ft_lane();
+  const int t = l.t;
+  const int q0 = blockIdx.x * FT_T;
+  const int ntiles = (a.C + FT_T - 1) / FT_T;
   const int ct0 = MODE == CH_TARGET ? 0 : blockIdx.y * tiles_per_split;
   const int ct1 = MODE == CH_TARGET ? 1 : min(ct0 + tiles_per_split, ntiles);
-  const int nchunks = (a.H + CH_KC - 1) / CH_KC;
+  const int nchunks = (a.H + FT_KC - 1) / FT_KC;
   const bool cosine = a.inv_h != nullptr;
   const float scale = cosine ? expf(a.log_scale[0]) : 1.f;
 
   // the row's label, -1 where the row is invalid (ignored, out of range, past B)
   int yown = -1;
   float zyown = 0.f;
-  if (t < CH_TQ) {
+  if (t < FT_T) {
     const int i = q0 + t;
     if (MODE != CH_LOGITS && i < a.B) {
       const int64_t y = a.labels[i];
@@ -149,68 +101,44 @@ __global__ __launch_bounds__(CH_THREADS, 2) void ch_tile_kernel(ChArgs a, int ti
     if (MODE == CH_DZ) rowl[t] = i < a.B ? in0[(size_t)i * 4] : 0.f;
     if (MODE == CH_TARGET) colw[t] = yown >= 0 ? (cosine ? a.inv_w[yown] : (a.bias ? a.bias[yown] : 0.f)) : 0.f;
   }
-  const bool owner = t < CH_TQ && q0 + t < a.B;
+  const bool owner = t < FT_T && q0 + t < a.B;
   const float coef = MODE == CH_DZ ? __fdiv_rn(in2[0], in1[3]) : 0.f;
   __syncthreads();
 
   for (int ct = ct0; ct < ct1; ++ct) {
-    const int c0 = ct * CH_TC;
-    ch_f32x16 acc[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[x][b][e] = 0.f;
+    const int c0 = ct * FT_T;
+    ft_f32x16 acc[2][2];
+    ft_dots(
+        acc, stage, l, nchunks,
+        // the class operand's row is c0 + r, or, for the target tile, the label of query row r (-1 = none, the row stays zero);
+        // H % 4 == 0 and both operands 16-byte aligned
+        [&](int operand, int r, int kk) {
+          const float* src = nullptr;
+          if (operand) {
+            const int row = MODE == CH_TARGET ? ylab[r] : c0 + r;
+            if (row >= 0 && row < a.C) src = a.W + (size_t)row * a.H + kk;
+          } else {
+            const int row = q0 + r;
+            if (row < a.B) src = a.h + (size_t)row * a.H + kk;
+          }
+          return src && kk < a.H ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+        },
+        [&] {
+          if (MODE != CH_TARGET && t < FT_T) {
+            const int j = c0 + t;
+            colw[t] = j < a.C ? (cosine ? a.inv_w[j] : (a.bias ? a.bias[j] : 0.f)) : 0.f;
+          }
+        });
 
-    float4 pre[8];
-    ch_fetch<MODE == CH_TARGET>(pre, a, ylab, q0, c0, 0, t);
-    for (int ch = 0; ch < nchunks; ++ch) {
-      __syncthreads();  // the previous chunk's reads (or the previous tile's scan of the half-tile) are done
-      if (MODE != CH_TARGET && ch == 0 && t < CH_TC) {
-        const int j = c0 + t;
-        colw[t] = j < a.C ? (cosine ? a.inv_w[j] : (a.bias ? a.bias[j] : 0.f)) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int f = t + CH_THREADS * u;
-        *reinterpret_cast<float4*>(stage + (size_t)(f >> 3) * CH_LD + 4 * (f & 7)) = pre[u];  // row f >> 3 of [query | class]
-      }
-      __syncthreads();
-      if (ch + 1 < nchunks) ch_fetch<MODE == CH_TARGET>(pre, a, ylab, q0, c0, (ch + 1) * CH_KC, t);
-      const float* qa = stage + (size_t)(wq * 64 + r32) * CH_LD + 4 * hh;
-      const float* cb = stage + (size_t)(CH_TQ + wc * 64 + r32) * CH_LD + 4 * hh;
-#pragma unroll
-      for (int p = 0; p < CH_KC / 8; ++p) {
-        const float4 a0 = *reinterpret_cast<const float4*>(qa + 8 * p);
-        const float4 a1 = *reinterpret_cast<const float4*>(qa + 32 * CH_LD + 8 * p);
-        const float4 b0 = *reinterpret_cast<const float4*>(cb + 8 * p);
-        const float4 b1 = *reinterpret_cast<const float4*>(cb + 32 * CH_LD + 8 * p);
-        const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
-        const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], bv0[s], acc[0][0], 0, 0, 0);
-          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], bv1[s], acc[0][1], 0, 0, 0);
-          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], bv0[s], acc[1][0], 0, 0, 0);
-          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], bv1[s], acc[1][1], 0, 0, 0);
-        }
-      }
-    }
-
-    // C/D map of the 32 x 32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
     if (MODE == CH_TARGET) {
-      if (wq == wc) {  // the diagonal 64 x 64 quadrants; inside them the diagonal 32 x 32 blocks
+      if (l.wq == l.wc) {  // the diagonal 64 x 64 quadrants; inside them the diagonal 32 x 32 blocks
 #pragma unroll
         for (int x = 0; x < 2; ++x)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int rin = (e & 3) + 8 * (e >> 2) + 4 * hh;
-            if (rin == r32) {
-              const int row = wq * 64 + x * 32 + rin;
-              if (q0 + row < a.B)
-                out[q0 + row] = ylab[row] >= 0 ? ch_logit(cosine, acc[x][x][e], invq[row], colw[row], scale) : 0.f;
-            }
+            const int row = ft_row(l, x, e);
+            if ((row & 31) == l.r32 && q0 + row < a.B)
+              out[q0 + row] = ylab[row] >= 0 ? ch_logit(cosine, acc[x][x][e], invq[row], colw[row], scale) : 0.f;
           }
       }
     } else if (MODE == CH_DZ || MODE == CH_LOGITS) {
@@ -218,12 +146,12 @@ __global__ __launch_bounds__(CH_THREADS, 2) void ch_tile_kernel(ChArgs a, int ti
       for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-          const int lc = wc * 64 + b * 32 + r32;
+          const int lc = l.wc * 64 + b * 32 + l.r32;
           const int col = c0 + lc;
           const float cw = colw[lc];
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int row = wq * 64 + x * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+            const int row = ft_row(l, x, e);
             if (q0 + row < a.B && col < a.C) {
               const float z = ch_logit(cosine, acc[x][b][e], invq[row], cw, scale);
               float v = z;
@@ -240,24 +168,13 @@ __global__ __launch_bounds__(CH_THREADS, 2) void ch_tile_kernel(ChArgs a, int ti
       int ahead = 0;
       __syncthreads();  // every wave is done with the staged chunk: the half-tile takes its place
       for (int h = 0; h < 2; ++h) {
-        if (wc == h) {
-#pragma unroll
-          for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-              const int col = b * 32 + r32;        // within this half
-              const bool in = c0 + h * 64 + col < a.C;
-              const float cw = colw[h * 64 + col];
-#pragma unroll
-              for (int e = 0; e < 16; ++e) {
-                const int row = wq * 64 + x * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                stage[(size_t)row * CH_SLD + col] = in ? ch_logit(cosine, acc[x][b][e], invq[row], cw, scale) : -INFINITY;
-              }
-            }
-        }
+        ft_put_half(stage, acc, l, h, [&](float dot, int row, int col) {
+          const bool in = c0 + h * 64 + col < a.C;
+          return in ? ch_logit(cosine, dot, invq[row], colw[h * 64 + col], scale) : -INFINITY;
+        });
         __syncthreads();
         if (owner) {
-          const float* srow = stage + (size_t)t * CH_SLD;
+          const float* srow = ft_half_row(stage, t);
           const int jbase = c0 + h * 64;
           float hm = -INFINITY;
           for (int c = 0; c < 64; ++c) hm = fmaxf(hm, srow[c]);  // a NaN is skipped here and reaches the sum below
@@ -330,13 +247,7 @@ __global__ __launch_bounds__(256) void ch_fold_kernel(const float* __restrict__ 
     }
   }
   red[0][t] = loss; red[1][t] = top1; red[2][t] = topk; red[3][t] = n; red[4][t] = bad;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o)
-#pragma unroll
-      for (int q = 0; q < 5; ++q) red[q][t] = __fadd_rn(red[q][t], red[q][t + o]);
-    __syncthreads();
-  }
+  block_tree_sum<5>(red, t);
   if (t == 0) {
     acc[0] = red[4][0] > 0.f ? __builtin_nanf("") : __fdiv_rn(red[0][0], red[3][0]);
     acc[1] = __fdiv_rn(red[1][0], (float)B);
@@ -456,22 +367,16 @@ __global__ __launch_bounds__(256) void ch_contract_kernel(const float* __restric
 
 // dst[0] += sum_i v[i]: thread t sums i = t, t + 256, ... in order, then a fixed tree
 __global__ __launch_bounds__(256) void ch_sum_add_kernel(const float* __restrict__ v, int n, float* __restrict__ dst) {
-  __shared__ float red[256];
+  __shared__ float red[1][256];
   const int t = threadIdx.x;
   float s = 0.f;
   for (int i = t; i < n; i += 256) s = __fadd_rn(s, v[i]);
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] = __fadd_rn(red[t], red[t + o]);
-    __syncthreads();
-  }
-  if (t == 0) dst[0] = __fadd_rn(dst[0], red[0]);
+  red[0][t] = s;
+  block_tree_sum<1>(red, t);
+  if (t == 0) dst[0] = __fadd_rn(dst[0], red[0][0]);
 }
 
 // ------------------------------------------------------------------ host
-static bool ch_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static int ch_range(const char* who, int64_t B, int64_t H, int64_t C) {
   VSX_CHECK(B >= 1 && B <= (1 << 24), "%s: B=%ld must be in [1, 2^24]", who, (long)B);
   VSX_CHECK(H >= 4 && H <= (1 << 20) && H % 4 == 0, "%s: H=%ld must be a multiple of 4 in [4, 2^20]", who, (long)H);
@@ -481,34 +386,19 @@ static int ch_range(const char* who, int64_t B, int64_t H, int64_t C) {
 
 static int ch_operands(const char* who, const float* h, const float* W, const float* inv_h, const float* inv_w,
                        const float* log_scale, const float* bias) {
-  VSX_CHECK(h && W && ch_al16(h) && ch_al16(W), "%s: h and W must be non-null and 16-byte aligned", who);
+  VSX_CHECK(h && W && vsx_al16(h) && vsx_al16(W), "%s: h and W must be non-null and 16-byte aligned", who);
   if (inv_h || inv_w || log_scale)
     VSX_CHECK(inv_h && inv_w && log_scale && !bias, "%s: the cosine classifier takes inv_h, inv_w and log_scale, and no bias", who);
   return 0;
 }
 
-static int ch_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      cus = n;
-    else
-      cus = 256;
-  }
-  return cus;
-}
-
 extern "C" int32_t vsx_cls_inv_norm(const float* x, float* inv, int32_t N, int32_t d, vsx_stream_t stream) {
-  VSX_CHECK(x && inv && N >= 1 && d >= 1, "vsx_cls_inv_norm: bad arguments");
-  hipLaunchKernelGGL(ch_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, inv, N, d);
-  VSX_LAUNCH_CHECK();
-  return 0;
+  return ft_inv_norm<true>("vsx_cls_inv_norm", x, inv, N, d, CH_NORM_EPS, (hipStream_t)stream);
 }
 
 extern "C" int64_t vsx_cls_ce_fwd_ws_bytes(int32_t B, int32_t H, int32_t C) {
   if (B < 1 || H < 4 || H % 4 || C < 1) return 0;
-  const int64_t ntiles = (C + CH_TC - 1) / CH_TC;
+  const int64_t ntiles = (C + FT_T - 1) / FT_T;
   return (ntiles * B * 3 + B) * 4;  // the tiles' triples, then zy[B]
 }
 
@@ -522,10 +412,10 @@ extern "C" int32_t vsx_cls_ce_fwd(const float* h, const float* W, const int64_t*
   VSX_CHECK(ws_bytes >= vsx_cls_ce_fwd_ws_bytes(B, H, C) && ((uintptr_t)ws & 3) == 0,
             "vsx_cls_ce_fwd: the workspace must be 4-byte aligned and hold vsx_cls_ce_fwd_ws_bytes = %ld bytes (got %ld)",
             (long)vsx_cls_ce_fwd_ws_bytes(B, H, C), (long)ws_bytes);
-  const int qtiles = (B + CH_TQ - 1) / CH_TQ, ntiles = (C + CH_TC - 1) / CH_TC;
+  const int qtiles = (B + FT_T - 1) / FT_T, ntiles = (C + FT_T - 1) / FT_T;
   VSX_CHECK(splits >= 0, "vsx_cls_ce_fwd: splits=%d (0 = chosen here)", splits);
   if (splits == 0) {  // fill two workgroup slots per compute unit
-    const long want = (2L * ch_cus() + qtiles - 1) / qtiles;
+    const long want = (2L * vsx_cu_count() + qtiles - 1) / qtiles;
     splits = (int)(want < 1 ? 1 : want);
   }
   if (splits > ntiles) splits = ntiles;
@@ -535,9 +425,9 @@ extern "C" int32_t vsx_cls_ce_fwd(const float* h, const float* W, const int64_t*
   float* zy = part + (size_t)ntiles * B * 3;
   const ChArgs a = {h, W, labels, inv_h, inv_w, log_scale, bias, B, H, C};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((ch_tile_kernel<CH_TARGET>), dim3((unsigned)qtiles), dim3(CH_THREADS), 0, s, a, 1, (const float*)nullptr,
+  hipLaunchKernelGGL((ch_tile_kernel<CH_TARGET>), dim3((unsigned)qtiles), dim3(FT_THREADS), 0, s, a, 1, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, zy);
-  hipLaunchKernelGGL((ch_tile_kernel<CH_SCAN>), dim3((unsigned)qtiles, (unsigned)splits), dim3(CH_THREADS), 0, s, a, tps,
+  hipLaunchKernelGGL((ch_tile_kernel<CH_SCAN>), dim3((unsigned)qtiles, (unsigned)splits), dim3(FT_THREADS), 0, s, a, tps,
                      (const float*)zy, (const float*)nullptr, (const float*)nullptr, part);
   hipLaunchKernelGGL(ch_merge_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, (const float*)part, (const float*)zy, labels,
                      B, C, ntiles, rows);
@@ -551,9 +441,9 @@ extern "C" int32_t vsx_cls_logits(const float* h, const float* W, const float* i
   if (int rc = ch_range("vsx_cls_logits", B, H, C)) return rc;
   if (int rc = ch_operands("vsx_cls_logits", h, W, inv_h, inv_w, log_scale, bias)) return rc;
   VSX_CHECK(Z != nullptr, "vsx_cls_logits: null argument");
-  const int qtiles = (B + CH_TQ - 1) / CH_TQ, ntiles = (C + CH_TC - 1) / CH_TC;
+  const int qtiles = (B + FT_T - 1) / FT_T, ntiles = (C + FT_T - 1) / FT_T;
   const ChArgs a = {h, W, nullptr, inv_h, inv_w, log_scale, bias, B, H, C};
-  hipLaunchKernelGGL((ch_tile_kernel<CH_LOGITS>), dim3((unsigned)qtiles, (unsigned)ntiles), dim3(CH_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((ch_tile_kernel<CH_LOGITS>), dim3((unsigned)qtiles, (unsigned)ntiles), dim3(FT_THREADS), 0, (hipStream_t)stream,
                      a, 1, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, Z);
   VSX_LAUNCH_CHECK();
   return 0;
@@ -571,20 +461,20 @@ extern "C" int32_t vsx_cls_ce_bwd(const float* h, const float* W, const int64_t*
                                   int64_t ws_bytes, vsx_stream_t stream) {
   if (int rc = ch_range("vsx_cls_ce_bwd", B, H, C)) return rc;
   if (int rc = ch_operands("vsx_cls_ce_bwd", h, W, inv_h, inv_w, log_scale, bias)) return rc;
-  VSX_CHECK(labels && rows && acc && gout && dh && dW && ws && ch_al16(dh) && ch_al16(dW),
+  VSX_CHECK(labels && rows && acc && gout && dh && dW && ws && vsx_al16(dh) && vsx_al16(dW),
             "vsx_cls_ce_bwd: null argument, or dh / dW not 16-byte aligned");
   const bool cosine = inv_h != nullptr;
   VSX_CHECK(cosine ? (dlog_scale && !dbias) : !dlog_scale, "vsx_cls_ce_bwd: cosine takes dlog_scale (no dbias), linear dbias or none");
-  VSX_CHECK(ws_bytes >= vsx_cls_ce_bwd_ws_bytes(B, H, C) && ch_al16(ws),
+  VSX_CHECK(ws_bytes >= vsx_cls_ce_bwd_ws_bytes(B, H, C) && vsx_al16(ws),
             "vsx_cls_ce_bwd: the workspace must be 16-byte aligned and hold vsx_cls_ce_bwd_ws_bytes = %ld bytes (got %ld)",
             (long)vsx_cls_ce_bwd_ws_bytes(B, H, C), (long)ws_bytes);
-  const int qtiles = (B + CH_TQ - 1) / CH_TQ, ntiles = (C + CH_TC - 1) / CH_TC;
+  const int qtiles = (B + FT_T - 1) / FT_T, ntiles = (C + FT_T - 1) / FT_T;
   float* dZ = (float*)ws;
   float* rawW = dZ + ((size_t)B * C + 3) / 4 * 4;
   float* tdot = rawW + (size_t)C * H;
   const ChArgs a = {h, W, labels, inv_h, inv_w, log_scale, bias, B, H, C};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((ch_tile_kernel<CH_DZ>), dim3((unsigned)qtiles, (unsigned)ntiles), dim3(CH_THREADS), 0, s, a, 1, rows, acc, gout, dZ);
+  hipLaunchKernelGGL((ch_tile_kernel<CH_DZ>), dim3((unsigned)qtiles, (unsigned)ntiles), dim3(FT_THREADS), 0, s, a, 1, rows, acc, gout, dZ);
   const dim3 gh((unsigned)((B + CC_RB - 1) / CC_RB)), gw((unsigned)((C + CC_RB - 1) / CC_RB)), block(256);
   if (cosine) {
     hipLaunchKernelGGL((ch_contract_kernel<true>), gh, block, 0, s, (const float*)dZ, (long)C, 1L, B, C, H, W, inv_w, h, inv_h, log_scale,

@@ -361,8 +361,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
 }
 
 // acc = {loss, mean cos_ap, mean d_ap, mean cos_an, mean d_an, share of rows with hinge > 0};  loss = mean or sum of hinge.
-// ONE workgroup, a fixed order: thread t adds rows t, t + 256, ... in ascending order, then the 256 partial sums of each
-// quantity are combined by a binary tree in LDS (stride 128, 64, ... 1) — no atomics, the same bits in every run
+// ONE workgroup, a fixed order: thread t adds rows t, t + 256, ... in ascending order, then block_tree_sum: the same bits in every run
 __global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __restrict__ rows, float* __restrict__ acc, int B,
                                                                int sum_reduction) {
   __shared__ float red[6][256];
@@ -379,14 +378,7 @@ __global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __re
   }
 #pragma unroll
   for (int q = 0; q < 6; ++q) red[q][t] = v[q];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) red[q][t] += red[q][t + o];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<6>(red, t);
   if (t < 6) acc[t] = (t == 0 && sum_reduction) ? red[0][0] : red[t][0] / (float)B;
 }
 
@@ -419,7 +411,7 @@ extern "C" int32_t vsx_triplet_fwd(const float* A, const float* P, const float* 
   VSX_CHECK(A && P && N && rows && acc && B >= 1 && D >= 1, "vsx_triplet_fwd: bad arguments");
   VSX_CHECK(reduction == 0 || reduction == 1, "vsx_triplet_fwd: unknown reduction %d (0 = mean, 1 = sum)", reduction);
   hipStream_t s = (hipStream_t)stream;
-  const int vec = D % 4 == 0 && (((uintptr_t)A | (uintptr_t)P | (uintptr_t)N) & 15) == 0;
+  const int vec = D % 4 == 0 && vsx_al16(A) && vsx_al16(P) && vsx_al16(N);
   hipLaunchKernelGGL(triplet_rows_kernel, dim3(vsx_cdiv(B, 4)), dim3(256), 0, s, A, P, N, rows, B, D, margin, eps, vec);
   hipLaunchKernelGGL(triplet_finalize_kernel, dim3(1), dim3(256), 0, s, rows, acc, B, reduction);
   VSX_LAUNCH_CHECK();

@@ -718,7 +718,7 @@ int proj_wgs(long M) {
   const long g = (M + 15) / 16;
   return (int)(g < 1024 ? g : 1024);
 }
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool al16(const void* p) { return vsx_al16(p); }
 
 }  // namespace
 

@@ -7,53 +7,26 @@
 //   s_ij   = fl32(fl32(dot_ij * inv_i) * inv_j)        candidate iff group[j] >= 0 && group[j] != group[i]
 //   result = the min(k, #candidates) best candidates of every row in the total order (s descending, j ascending)
 //
-// vsx_knn_topk never stores an N x N matrix.  A workgroup owns KT_TQ = 128 query rows and one contiguous range of candidate tiles
-// (KT_TC = 128 rows each).  Per tile it stages both operands through LDS in chunks of KT_KC = 32 features, forms the 128 x 128
-// tile of dot products in registers (four waves, a 64 x 64 quadrant of four 32 x 32 accumulators each), writes the scaled and
-// masked similarities to LDS one 64-column half at a time, and thread r < 128 scans row r of that half against the row's k-th
-// best, which it keeps in registers; the few survivors are inserted into the row's sorted list in LDS.  The candidate range of
-// a query tile is split over up to KT_MAX_SPLITS workgroups to fill the machine; every split stores its sorted list to the
-// workspace (O(N k)), and a second kernel merges the splits' lists per row in the same total order.  Since the order is total,
-// the result does not depend on the split count or on the order in which survivors were inserted.
+// vsx_knn_topk never stores an N x N matrix.  A workgroup owns 128 query rows and one contiguous range of candidate tiles
+// (128 rows each).  Per tile it forms the 128 x 128 tile of dot products in registers with the tile engine of f32_tile.h (which
+// also fixes the dots' summation order), writes the scaled and masked similarities to LDS one 64-column half at a time, and
+// thread r < 128 scans row r of that half against the row's k-th best, which it keeps in registers; the few survivors are
+// inserted into the row's sorted list in LDS.  The candidate range of a query tile is split over up to KT_MAX_SPLITS workgroups
+// to fill the machine; every split stores its sorted list to the workspace (O(N k)), and a second kernel merges the splits'
+// lists per row in the same total order.  Since the order is total, the result does not depend on the split count or on the
+// order in which survivors were inserted.
 //
 // A masked entry travels through LDS as NaN: every comparison with it is false, so it is never inserted (a NaN similarity of
 // non-finite input rows is dropped in the same way).
-//
-// The feature index inside a chunk is permuted between the MFMA steps (lane half h, step s of group p reads feature 8p + 4h + s,
-// for both operands alike), so that each lane fetches four steps' operands with one 16-byte LDS read; a sum over k does not
-// care which k meets which step.
-#include "vsx_common.h"
+#include "f32_tile.h"
 #include "../../include/vsx.h"
 
 #include <math.h>
 
-#define KT_TQ 128
-#define KT_TC 128
-#define KT_KC 32
-#define KT_LD 36         // floats per staged row: 32 + 4, keeps 16-byte alignment and spreads rows over the banks
-#define KT_SLD 65        // floats per row of the similarity half-tile
-#define KT_THREADS 256
-#define KT_STAGE (2 * KT_TQ * KT_LD)   // floats of the staging area (query chunk | candidate chunk); the half-tile (128 x 65) reuses it
 #define KT_MAX_SPLITS 8
 #define KT_MAX_K 64
 
-typedef float kt_f32x16 __attribute__((ext_vector_type(16)));
-
-static_assert(KT_TQ * KT_SLD <= KT_STAGE, "the similarity half-tile must fit the staging area");
-
-// ------------------------------------------------------------------ (a) inverse row norms: one wave per row
-__global__ __launch_bounds__(256) void row_inv_norm_kernel(const float* __restrict__ x, float* __restrict__ inv, int N, int d, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= N) return;
-  const float* xr = x + (size_t)row * d;
-  float ss = 0.f;
-  for (int c = lane; c < d; c += 64) ss = fmaf(xr[c], xr[c], ss);
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  const float den = __fadd_rn(sqrtf(ss), eps);
-  if (lane == 0) inv[row] = den == 0.f ? 0.f : __fdiv_rn(1.f, den);
-}
-
+// (a) inverse row norms: ft_inv_norm_kernel of f32_tile.h
 // ------------------------------------------------------------------ (d) cosine distance of listed pairs: one wave per pair
 __global__ __launch_bounds__(256) void pair_cosine_dist_kernel(const float* __restrict__ x, const float* __restrict__ inv,
                                                                const int* __restrict__ pi, const int* __restrict__ pj, long P, int d,
@@ -73,135 +46,79 @@ __global__ __launch_bounds__(256) void pair_cosine_dist_kernel(const float* __re
 // ------------------------------------------------------------------ (b) streaming similarity + top-k
 __device__ __forceinline__ bool kt_better(float s, int j, float s0, int j0) { return s > s0 || (s == s0 && j < j0); }
 
-// one thread's share of a chunk: 8 x 4 features; f = t + 256 u -> operand f >> 10, row (f & 1023) >> 3, feature quad f & 7, so
-// that 8 consecutive lanes read 128 contiguous bytes of one row
-template <bool VEC>
-__device__ __forceinline__ void kt_fetch(float4* r, const float* __restrict__ x, int q0, int c0, int kc0, int N, int d, int t) {
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int f = t + KT_THREADS * u;
-    const int g = f & 1023;
-    const int row = ((f >> 10) ? c0 : q0) + (g >> 3);
-    const int kk = kc0 + 4 * (g & 7);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < N) {
-      const float* src = x + (size_t)row * d + kk;
-      if (VEC) {
-        if (kk < d) v = *reinterpret_cast<const float4*>(src);  // d % 4 == 0 and x 16-byte aligned
-      } else {
-        if (kk < d) v.x = src[0];
-        if (kk + 1 < d) v.y = src[1];
-        if (kk + 2 < d) v.z = src[2];
-        if (kk + 3 < d) v.w = src[3];
-      }
-    }
-    r[u] = v;
-  }
-}
-
-// KB: the list capacity the LDS is sized for (k <= KB); the lists themselves are laid out for the k of the call
+// KB: the list capacity the LDS is sized for (k <= KB); the lists themselves are laid out for the k of the call.
+// VEC: d % 4 == 0 and x 16-byte aligned, rows are read as float4; else feature by feature
 template <bool VEC, int KB>
-__global__ __launch_bounds__(KT_THREADS, KB <= 24 ? 2 : 1) void knn_topk_kernel(const float* __restrict__ x, const float* __restrict__ inv,
+__global__ __launch_bounds__(FT_THREADS, KB <= 24 ? 2 : 1) void knn_topk_kernel(const float* __restrict__ x, const float* __restrict__ inv,
                                                                 const int* __restrict__ group, int N, int d, int k,
                                                                 int tiles_per_split, int* __restrict__ pidx,
                                                                 float* __restrict__ psim, int* __restrict__ pcnt) {
-  __shared__ __attribute__((aligned(16))) float kt_smem[KT_STAGE + 2 * KB * KT_TQ];
-  float* stage = kt_smem;                       // [2][KT_TQ][KT_LD]; later the similarity half-tile [KT_TQ][KT_SLD]
-  float* ls = kt_smem + KT_STAGE;               // [k][KT_TQ] sorted similarities of every query row
-  int* li = reinterpret_cast<int*>(ls + (size_t)k * KT_TQ);  // [k][KT_TQ] their row indices
-  __shared__ float invq[KT_TQ], invc[KT_TC];
-  __shared__ int gq[KT_TQ], gc[KT_TC];
+  __shared__ __attribute__((aligned(16))) float kt_smem[FT_STAGE + 2 * KB * FT_T];
+  float* stage = kt_smem;                       // the engine's staging area; later the similarity half-tile
+  float* ls = kt_smem + FT_STAGE;               // [k][FT_T] sorted similarities of every query row
+  int* li = reinterpret_cast<int*>(ls + (size_t)k * FT_T);  // [k][FT_T] their row indices
+  __shared__ float invq[FT_T], invc[FT_T];
+  __shared__ int gq[FT_T], gc[FT_T];
 
-  const int t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  const int wq = wave & 1, wc = wave >> 1;      // this wave's 64 x 64 quadrant of the tile
-  const int r32 = lane & 31, hh = lane >> 5;
-  const int q0 = blockIdx.x * KT_TQ;
-  const int ntiles = (N + KT_TC - 1) / KT_TC;
+  const FtLane l = ft_lane();
+  const int t = l.t;
+  const int q0 = blockIdx.x * FT_T;
+  const int ntiles = (N + FT_T - 1) / FT_T;
   const int ct0 = blockIdx.y * tiles_per_split;
   const int ct1 = min(ct0 + tiles_per_split, ntiles);
-  const int nchunks = (d + KT_KC - 1) / KT_KC;
+  const int nchunks = (d + FT_KC - 1) / FT_KC;
 
-  if (t < KT_TQ) {
+  if (t < FT_T) {
     const int i = q0 + t;
     gq[t] = i < N ? group[i] : -1;
     invq[t] = i < N ? inv[i] : 0.f;
   }
   // the owner of query row t keeps the row's count and its k-th best in registers
-  const bool owner = t < KT_TQ && q0 + t < N;
+  const bool owner = t < FT_T && q0 + t < N;
   int cnt = 0;
   float thr_s = 0.f;
   int thr_j = 0;
 
   for (int ct = ct0; ct < ct1; ++ct) {
-    const int c0 = ct * KT_TC;
-    kt_f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-    float4 pre[8];
-    kt_fetch<VEC>(pre, x, q0, c0, 0, N, d, t);
-    for (int ch = 0; ch < nchunks; ++ch) {
-      __syncthreads();  // the previous chunk's reads (or the previous tile's scan of the half-tile) are done
-      if (ch == 0 && t < KT_TC) {
-        const int j = c0 + t;
-        gc[t] = j < N ? group[j] : -1;
-        invc[t] = j < N ? inv[j] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int f = t + KT_THREADS * u;
-        *reinterpret_cast<float4*>(stage + (size_t)(f >> 3) * KT_LD + 4 * (f & 7)) = pre[u];  // row f >> 3 of [query | candidate]
-      }
-      __syncthreads();
-      if (ch + 1 < nchunks) kt_fetch<VEC>(pre, x, q0, c0, (ch + 1) * KT_KC, N, d, t);
-      const float* qa = stage + (size_t)(wq * 64 + r32) * KT_LD + 4 * hh;
-      const float* cb = stage + (size_t)(KT_TQ + wc * 64 + r32) * KT_LD + 4 * hh;
-#pragma unroll
-      for (int p = 0; p < KT_KC / 8; ++p) {
-        const float4 a0 = *reinterpret_cast<const float4*>(qa + 8 * p);
-        const float4 a1 = *reinterpret_cast<const float4*>(qa + 32 * KT_LD + 8 * p);
-        const float4 b0 = *reinterpret_cast<const float4*>(cb + 8 * p);
-        const float4 b1 = *reinterpret_cast<const float4*>(cb + 32 * KT_LD + 8 * p);
-        const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
-        const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], bv0[s], acc[0][0], 0, 0, 0);
-          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], bv1[s], acc[0][1], 0, 0, 0);
-          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], bv0[s], acc[1][0], 0, 0, 0);
-          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], bv1[s], acc[1][1], 0, 0, 0);
-        }
-      }
-    }
+    const int c0 = ct * FT_T;
+    ft_f32x16 acc[2][2];
+    ft_dots(
+        acc, stage, l, nchunks,
+        [&](int operand, int r, int kk) {
+          const int row = (operand ? c0 : q0) + r;
+          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (row < N) {
+            const float* src = x + (size_t)row * d + kk;
+            if (VEC) {
+              if (kk < d) v = *reinterpret_cast<const float4*>(src);
+            } else {
+              if (kk < d) v.x = src[0];
+              if (kk + 1 < d) v.y = src[1];
+              if (kk + 2 < d) v.z = src[2];
+              if (kk + 3 < d) v.w = src[3];
+            }
+          }
+          return v;
+        },
+        [&] {
+          if (t < FT_T) {
+            const int j = c0 + t;
+            gc[t] = j < N ? group[j] : -1;
+            invc[t] = j < N ? inv[j] : 0.f;
+          }
+        });
     __syncthreads();  // every wave is done with the staged chunk: the half-tile takes its place
 
     for (int h = 0; h < 2; ++h) {
-      if (wc == h) {
-        // C/D map of the 32 x 32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            const int col = b * 32 + r32;        // within this half
-            const int gj = gc[h * 64 + col];
-            const float ij = invc[h * 64 + col];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int row = wq * 64 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-              const bool ok = gj >= 0 && gj != gq[row];
-              const float s = __fmul_rn(__fmul_rn(acc[a][b][e], invq[row]), ij);
-              stage[(size_t)row * KT_SLD + col] = ok ? s : __builtin_nanf("");
-            }
-          }
-      }
+      ft_put_half(stage, acc, l, h, [&](float dot, int row, int col) {
+        const int gj = gc[h * 64 + col];
+        const bool ok = gj >= 0 && gj != gq[row];
+        const float s = __fmul_rn(__fmul_rn(dot, invq[row]), invc[h * 64 + col]);
+        return ok ? s : __builtin_nanf("");
+      });
       __syncthreads();
       if (owner) {
-        const float* srow = stage + (size_t)t * KT_SLD;
+        const float* srow = ft_half_row(stage, t);
         const int jbase = c0 + h * 64;
         for (int c = 0; c < 64; ++c) {
           const float s = srow[c];
@@ -210,18 +127,18 @@ __global__ __launch_bounds__(KT_THREADS, KB <= 24 ? 2 : 1) void knn_topk_kernel(
           if (cnt == k && !kt_better(s, j, thr_s, thr_j)) continue;
           int p = cnt < k ? cnt++ : k - 1;        // a full list drops its last entry
           while (p > 0) {
-            const float sp = ls[(size_t)(p - 1) * KT_TQ + t];
-            const int jp = li[(size_t)(p - 1) * KT_TQ + t];
+            const float sp = ls[(size_t)(p - 1) * FT_T + t];
+            const int jp = li[(size_t)(p - 1) * FT_T + t];
             if (!kt_better(s, j, sp, jp)) break;
-            ls[(size_t)p * KT_TQ + t] = sp;
-            li[(size_t)p * KT_TQ + t] = jp;
+            ls[(size_t)p * FT_T + t] = sp;
+            li[(size_t)p * FT_T + t] = jp;
             --p;
           }
-          ls[(size_t)p * KT_TQ + t] = s;
-          li[(size_t)p * KT_TQ + t] = j;
+          ls[(size_t)p * FT_T + t] = s;
+          li[(size_t)p * FT_T + t] = j;
           if (cnt == k) {
-            thr_s = ls[(size_t)(k - 1) * KT_TQ + t];
-            thr_j = li[(size_t)(k - 1) * KT_TQ + t];
+            thr_s = ls[(size_t)(k - 1) * FT_T + t];
+            thr_j = li[(size_t)(k - 1) * FT_T + t];
           }
         }
       }
@@ -232,8 +149,8 @@ __global__ __launch_bounds__(KT_THREADS, KB <= 24 ? 2 : 1) void knn_topk_kernel(
   if (owner) {
     const size_t base = ((size_t)blockIdx.y * N + (size_t)(q0 + t)) * k;
     for (int p = 0; p < cnt; ++p) {
-      psim[base + p] = ls[(size_t)p * KT_TQ + t];
-      pidx[base + p] = li[(size_t)p * KT_TQ + t];
+      psim[base + p] = ls[(size_t)p * FT_T + t];
+      pidx[base + p] = li[(size_t)p * FT_T + t];
     }
     pcnt[(size_t)blockIdx.y * N + q0 + t] = cnt;
   }
@@ -311,10 +228,7 @@ static int kt_range(const char* who, int64_t N, int64_t d, int64_t k) {
 }
 
 extern "C" int32_t vsx_row_inv_norm(const float* x, float* inv, int32_t N, int32_t d, float eps, vsx_stream_t stream) {
-  VSX_CHECK(x && inv && N >= 1 && d >= 1, "vsx_row_inv_norm: bad arguments");
-  hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, inv, N, d, eps);
-  VSX_LAUNCH_CHECK();
-  return 0;
+  return ft_inv_norm<false>("vsx_row_inv_norm", x, inv, N, d, eps, (hipStream_t)stream);
 }
 
 extern "C" int64_t vsx_knn_topk_ws_bytes(int32_t N, int32_t d, int32_t k) {
@@ -348,23 +262,15 @@ extern "C" int32_t vsx_knn_topk(const float* x, const float* inv, const int32_t*
   VSX_CHECK(ws_bytes >= vsx_knn_topk_ws_bytes(N, d, k) && ((uintptr_t)ws & 3) == 0,
             "vsx_knn_topk: the workspace must be 4-byte aligned and hold vsx_knn_topk_ws_bytes = %ld bytes (got %ld)",
             (long)vsx_knn_topk_ws_bytes(N, d, k), (long)ws_bytes);
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      cus = n;
-    else
-      cus = 256;
-  }
-  const int qtiles = (N + KT_TQ - 1) / KT_TQ, ctiles = (N + KT_TC - 1) / KT_TC;
-  const int splits = kt_splits(qtiles, ctiles, cus);
+  const int qtiles = (N + FT_T - 1) / FT_T, ctiles = qtiles;
+  const int splits = kt_splits(qtiles, ctiles, vsx_cu_count());
   const int tps = (ctiles + splits - 1) / splits;
   int* pidx = (int*)ws;
   float* psim = (float*)(pidx + (size_t)splits * N * k);
   int* pcnt = (int*)(psim + (size_t)splits * N * k);
-  const bool vec = d % 4 == 0 && ((uintptr_t)x & 15) == 0;
+  const bool vec = d % 4 == 0 && vsx_al16(x);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)qtiles, (unsigned)splits), block(KT_THREADS);
+  const dim3 grid((unsigned)qtiles, (unsigned)splits), block(FT_THREADS);
 #define KT_GO(VEC, KB) hipLaunchKernelGGL((knn_topk_kernel<VEC, KB>), grid, block, 0, s, x, inv, group, N, d, k, tps, pidx, psim, pcnt)
   if (k <= 8) {
     if (vec) KT_GO(true, 8); else KT_GO(false, 8);

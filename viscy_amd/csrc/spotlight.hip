@@ -281,7 +281,6 @@ __global__ __launch_bounds__(SL_THREADS) void spotlight_bwd_kernel(const TP* __r
 }
 
 // ------------------------------------------------------------------ host side of the loss
-static inline bool sl_aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
 static inline long sl_cpr(long n) { return (n + SL_CHUNK - 1) / SL_CHUNK; }
 
 extern "C" int64_t vsx_spotlight_workspace(int32_t op, int64_t rows, int64_t n) {
@@ -323,7 +322,7 @@ extern "C" int32_t vsx_spotlight_fwd(const void* pred, int32_t dtype, const floa
   if (int rc = sl_check("vsx_spotlight_fwd", pred, dtype, target, mask, mask_mode, thr, rows, n, sigmoid_k)) return rc;
   VSX_CHECK(ws && loss && coef && ((uintptr_t)ws & 7) == 0, "vsx_spotlight_fwd: workspace (8-byte aligned), loss and coef are required");
   const int cpr = (int)sl_cpr(n);
-  const int vec = sl_aligned16(pred) && sl_aligned16(target) && sl_aligned16(mask);
+  const int vec = (!pred || vsx_al16(pred)) && (!target || vsx_al16(target)) && (!mask || vsx_al16(mask));
   const SlConst k = sl_const(sigmoid_k);
   double* part = (double*)ws;
   double* rowstat = part + rows * cpr * 5;
@@ -347,7 +346,7 @@ extern "C" int32_t vsx_spotlight_bwd(const void* pred, int32_t dtype, const floa
   if (int rc = sl_check("vsx_spotlight_bwd", pred, dtype, target, mask, mask_mode, thr, rows, n, sigmoid_k)) return rc;
   VSX_CHECK(coef && gout && dpred, "vsx_spotlight_bwd: coef, gout and dpred are required");
   const int cpr = (int)sl_cpr(n);
-  const int vec = sl_aligned16(pred) && sl_aligned16(target) && sl_aligned16(mask) && sl_aligned16(dpred);
+  const int vec = (!pred || vsx_al16(pred)) && (!target || vsx_al16(target)) && (!mask || vsx_al16(mask)) && (!dpred || vsx_al16(dpred));
   const SlConst k = sl_const(sigmoid_k);
   const dim3 grid((unsigned)(rows * cpr)), block(SL_THREADS);
   hipStream_t s = (hipStream_t)stream;
@@ -486,7 +485,7 @@ extern "C" int32_t vsx_otsu_threshold(const float* target, float* thr, void* ws,
   VSX_CHECK(((uintptr_t)ws & 3) == 0, "vsx_otsu_threshold: the workspace must be 4-byte aligned");
   VSX_CHECK(rows * sl_cpr(n) < (1L << 24), "vsx_otsu_threshold: %ld rows of %ld values need more than 2^24 workgroups", (long)rows, (long)n);
   const int cpr = (int)sl_cpr(n);
-  const int vec = sl_aligned16(target);
+  const int vec = (!target || vsx_al16(target));
   float* mm = (float*)ws;
   float* lohi = mm + rows * cpr * 2;
   uint32_t* hist = (uint32_t*)(lohi + rows * 2);

@@ -44,6 +44,8 @@ extern thread_local const char* g_vsx_last_kernel;  // api.hip: set by the GEMM 
   } while (0)
 
 static inline int vsx_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool vsx_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }  // fit for 16-byte vector accesses
+int vsx_cu_count();  // compute units of the current device, asked once (256 where the query fails): api.hip
 
 // ------------------------------------------------------------------ element traits
 template <typename T>
@@ -262,4 +264,19 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ------------------------------------------------------------------ block helpers (256 threads)
+// Fixed-order sum of Q quantities: every thread has stored its red[q][t]; on return red[q][0] is the total of each q.  A binary
+// tree in LDS (stride 128, 64, ... 1), plain round-to-nearest adds, a barrier per level: no atomics, the same bits in every run
+template <int Q>
+__device__ __forceinline__ void block_tree_sum(float (*red)[256], int t) {
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) red[q][t] = __fadd_rn(red[q][t], red[q][t + o]);
+    }
+    __syncthreads();
+  }
 }
