@@ -797,6 +797,31 @@ int32_t vsx_cls_ce_bwd(const float* h, const float* W, const int64_t* labels, co
     const float* log_scale, const float* bias, const float* rows, const float* acc, const float* gout, int32_t B, int32_t H,
     int32_t C, float* dh, float* dW, float* dbias, float* dlog_scale, void* ws, int64_t ws_bytes, vsx_stream_t stream);
 
+/* MMD two-sample permutation test (csrc/mmd.hip + f32_tile.h; viscy_utils/evaluation/mmd.py): Gaussian RBF kernel sums of N pooled rows
+ * [X; Y] under P label vectors, without an N x N buffer.  fp32 kernel values from dots on the exact f32 MFMA, sums in float64.
+ * mmd_prepare: mean[d] = the column mean of x [N, d] (float64 sums in a fixed order, rounded to fp32), xc = fl32(x - mean) (xc may be
+ * x), norms[i] = sum_c xc_ic^2.
+ * Kernel value, one device function for every entry point:  d2_ij = max(fl32(fl32(n_i + n_j) - 2 dot_ij), 0),
+ * k_ij = expf(-fl32(d2_ij / fl32(2 bandwidth))) (IEEE division, library expf), k_ij == k_ji bit for bit; in the pooled kernel k_ii = 0.
+ * mmd_sums: labels uint8 [P][N] of 0 / 1 (1 = the row belongs to X); sums [P][3] doubles = {sum_XX, sum_YY, sum_XY} =
+ * {z'Kz, T - 2 z'r + z'Kz, z'r - z'Kz} with r = K 1, T = 1'K1.  The kernel tile of a (row tile, column tile) pair is formed once,
+ * whatever P.  No floating-point atomics; per-workgroup partials in ws are folded in ascending order in float64, and how the column
+ * tiles are shared among workgroups depends on N alone: sums is a pure function of the inputs, bit-identical from run to run.
+ * 2 <= N <= 2^24, 1 <= d <= 2^20, 1 <= P <= 2^24, bandwidth > 0.  ws (8-byte aligned): vsx_mmd_sums_ws_bytes(N, P) bytes (0 for shapes
+ * that are not served), O(P N / 128), any contents.
+ * rbf_block: out [(r1 - r0)][(c1 - c0)] = k_ij for i in [r0, r1), j in [c0, c1) (0 <= r0 < r1 <= N, likewise c; at most 65535 * 128 rows);
+ * zero_diag != 0 stores 0 for i == j, else the diagonal holds its computed value.
+ * sqdist_upper: out[i (2M - i - 1) / 2 + (j - i - 1)] = d2_ij for 0 <= i < j < M, 2 <= M <= 65536: one contiguous row of M (M - 1) / 2 values
+ * (the median heuristic takes its middle ranks with vsx_row_select).
+ * Every check runs before any launch; anything not served is refused with a non-zero status. */
+int32_t vsx_mmd_prepare(const float* x, float* xc, float* norms, float* mean, int32_t N, int32_t d, vsx_stream_t stream);
+int64_t vsx_mmd_sums_ws_bytes(int32_t N, int32_t P);
+int32_t vsx_mmd_sums(const float* xc, const float* norms, const uint8_t* labels, int32_t N, int32_t d, int32_t P, double bandwidth,
+    double* sums, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int32_t vsx_rbf_block(const float* xc, const float* norms, int32_t N, int32_t d, int32_t r0, int32_t r1, int32_t c0, int32_t c1,
+    double bandwidth, int32_t zero_diag, float* out, vsx_stream_t stream);
+int32_t vsx_sqdist_upper(const float* xc, const float* norms, int32_t M, int32_t d, float* out, vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,11 @@ _SIGS = {
     "vsx_cls_logits": (_I32, [_P] * 6 + [_I32] * 3 + [_P, _P]),
     "vsx_cls_ce_bwd_ws_bytes": (_I64, [_I32, _I32, _I32]),
     "vsx_cls_ce_bwd": (_I32, [_P] * 10 + [_I32] * 3 + [_P] * 5 + [_I64, _P]),
+    "vsx_mmd_prepare": (_I32, [_P, _P, _P, _P, _I32, _I32, _P]),
+    "vsx_mmd_sums_ws_bytes": (_I64, [_I32, _I32]),
+    "vsx_mmd_sums": (_I32, [_P, _P, _P, _I32, _I32, _I32, C.c_double, _P, _P, _I64, _P]),
+    "vsx_rbf_block": (_I32, [_P, _P] + [_I32] * 6 + [C.c_double, _I32, _P, _P]),
+    "vsx_sqdist_upper": (_I32, [_P, _P, _I32, _I32, _P, _P]),
 }
 
 _lib = None

@@ -1285,3 +1285,59 @@ def cls_ce_bwd(h: Tensor, W: Tensor, labels: Tensor, rows: Tensor, acc: Tensor, 
                                ptr(gout), B, H, Cn, ptr(dh), ptr(dW), ptr(dbias), ptr(dlog_scale), ptr(ws), ws.numel() * 4,
                                stream()), "cls_ce_bwd")
     return dh
+
+
+# ------------------------------------------------------------------ MMD permutation test (csrc/mmd.hip)
+def mmd_prepare(x: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """-> (xc (N, d), norms (N,), mean (d,)): the rows minus their column mean (float64 sums in a fixed order, rounded to
+    float32) and the squared norms of the centred rows"""
+    n, d = _rows_f32(x, "mmd_prepare")
+    xc = torch.empty_like(x)
+    norms = torch.empty(n, dtype=torch.float32, device=x.device)
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    check(lib().vsx_mmd_prepare(ptr(x), ptr(xc), ptr(norms), ptr(mean), n, d, stream()), "mmd_prepare")
+    return xc, norms, mean
+
+
+def _mmd_pool(xc: Tensor, norms: Tensor, what: str) -> tuple[int, int]:
+    n, d = _rows_f32(xc, what)
+    ptr(norms)
+    if norms.dtype != torch.float32 or norms.numel() != n:
+        raise TypeError(f"{what}: norms must be {n} float32 values")
+    return n, d
+
+
+def mmd_sums(xc: Tensor, norms: Tensor, labels: Tensor, bandwidth: float) -> Tensor:
+    """-> (P, 3) float64 {sum_XX, sum_YY, sum_XY} of the pooled Gaussian kernel (zero diagonal) of the centred rows ``xc`` under
+    every 0 / 1 label vector of ``labels`` uint8 (P, N).  No N x N buffer: the workspace is O(P N / 128).  Bit-identical from run
+    to run."""
+    n, d = _mmd_pool(xc, norms, "mmd_sums")
+    ptr(labels)
+    if labels.dtype != torch.uint8 or labels.dim() != 2 or labels.shape[1] != n or labels.shape[0] < 1:
+        raise TypeError(f"mmd_sums: labels must be a uint8 (P, {n}) tensor, got {labels.dtype} {tuple(labels.shape)}")
+    P = labels.shape[0]
+    nbytes = int(lib().vsx_mmd_sums_ws_bytes(n, P))
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=xc.device)
+    sums = torch.empty((P, 3), dtype=torch.float64, device=xc.device)
+    check(lib().vsx_mmd_sums(ptr(xc), ptr(norms), ptr(labels), n, d, P, float(bandwidth), ptr(sums), ptr(ws), ws.numel() * 8, stream()),
+          "mmd_sums")
+    return sums
+
+
+def rbf_block(xc: Tensor, norms: Tensor, rows: tuple[int, int], cols: tuple[int, int], bandwidth: float, zero_diag: bool) -> Tensor:
+    """-> float32 (r1 - r0, c1 - c0): the kernel values k_ij of rows [r0, r1) x columns [c0, c1) of the centred pool, the very
+    values ``mmd_sums`` sums; ``zero_diag`` stores 0 where i == j"""
+    n, d = _mmd_pool(xc, norms, "rbf_block")
+    (r0, r1), (c0, c1) = (int(v) for v in rows), (int(v) for v in cols)
+    out = torch.empty((max(r1 - r0, 0), max(c1 - c0, 0)), dtype=torch.float32, device=xc.device)
+    check(lib().vsx_rbf_block(ptr(xc), ptr(norms), n, d, r0, r1, c0, c1, float(bandwidth), int(bool(zero_diag)), ptr(out), stream()),
+          "rbf_block")
+    return out
+
+
+def sqdist_upper(xc: Tensor, norms: Tensor) -> Tensor:
+    """-> float32 (1, M (M - 1) / 2): max(n_i + n_j - 2 dot_ij, 0) for i < j, row-major over the strict upper triangle"""
+    m, d = _mmd_pool(xc, norms, "sqdist_upper")
+    out = torch.empty((1, max(m * (m - 1) // 2, 1)), dtype=torch.float32, device=xc.device)
+    check(lib().vsx_sqdist_upper(ptr(xc), ptr(norms), m, d, ptr(out), stream()), "sqdist_upper")
+    return out
