@@ -231,6 +231,23 @@ def test_sqdist_upper_is_the_upper_triangle_of_the_tile():
     assert np.abs(up - ref).max() <= 4 * np.abs(RM.gram_sqdist_f32(x64.astype(np.float32)).astype(np.float64)[i, j] - ref).max()
 
 
+def test_squared_distances_hold_the_classifier_heads_dots_bit_for_bit():
+    """f32_tile.h's one summation order for the third user: with zero norms sqdist_upper stores max(-2 dot, 0) (the doubling is
+    exact), and the linear head without a bias stores the plain dot of the same two rows.  154 rows: two row tiles, the second
+    partial; d = 36: one full chunk and one of 4 features.  pool = [x; -x] makes half of the dots negative (50.3 % in float64,
+    the smallest |dot| 1.8e-3, far above fp32 error), so the clamp leaves half of the comparison non-trivial"""
+    from viscy_amd import ops
+
+    x = torch.randn(77, 36, generator=torch.Generator().manual_seed(0))
+    pool = torch.cat([x, -x]).to(DEV)
+    Z = ops.cls_logits(pool, pool)
+    D = ops.sqdist_upper(pool, torch.zeros(154, device=DEV))[0]
+    i, j = torch.triu_indices(154, 154, 1, device=DEV)
+    assert D.shape == (11781,)
+    assert torch.equal(D, torch.clamp_min(-2.0 * Z[i, j], 0.0))
+    assert int((D != 0).sum()) >= 0.45 * 11781
+
+
 def test_ops_refuse_what_they_do_not_serve():
     from viscy_amd import ops
 

@@ -77,11 +77,9 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ch_tile_kernel(ChArgs a, int ti
 
   const FtLane l = ft_lane();
   const int t = l.t;
-  const int q0 = blockIdx.x * FT_T;
-  const int ntiles = (a.C + FT_T - 1) / FT_T;
-  const int ct0 = MODE == CH_TARGET ? 0 : blockIdx.y * tiles_per_split;
-  const int ct1 = MODE == CH_TARGET ? 1 : min(ct0 + tiles_per_split, ntiles);
-  const int nchunks = (a.H + FT_KC - 1) / FT_KC;
+  FtRange g = ft_range(a.C, a.H, tiles_per_split);
+  if (MODE == CH_TARGET) g.ct0 = 0, g.ct1 = 1;  // the one gathered tile
+  const int q0 = g.q0;
   const bool cosine = a.inv_h != nullptr;
   const float scale = cosine ? expf(a.log_scale[0]) : 1.f;
 
@@ -105,23 +103,16 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ch_tile_kernel(ChArgs a, int ti
   const float coef = MODE == CH_DZ ? __fdiv_rn(in2[0], in1[3]) : 0.f;
   __syncthreads();
 
-  for (int ct = ct0; ct < ct1; ++ct) {
+  for (int ct = g.ct0; ct < g.ct1; ++ct) {
     const int c0 = ct * FT_T;
     ft_f32x16 acc[2][2];
     ft_dots(
-        acc, stage, l, nchunks,
+        acc, stage, l, g.nchunks,
         // the class operand's row is c0 + r, or, for the target tile, the label of query row r (-1 = none, the row stays zero);
         // H % 4 == 0 and both operands 16-byte aligned
         [&](int operand, int r, int kk) {
-          const float* src = nullptr;
-          if (operand) {
-            const int row = MODE == CH_TARGET ? ylab[r] : c0 + r;
-            if (row >= 0 && row < a.C) src = a.W + (size_t)row * a.H + kk;
-          } else {
-            const int row = q0 + r;
-            if (row < a.B) src = a.h + (size_t)row * a.H + kk;
-          }
-          return src && kk < a.H ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+          if (!operand) return ft_row4<true>(a.h, q0 + r, a.B, a.H, kk);
+          return ft_row4<true>(a.W, MODE == CH_TARGET ? ylab[r] : c0 + r, a.C, a.H, kk);
         },
         [&] {
           if (MODE != CH_TARGET && t < FT_T) {
@@ -131,46 +122,30 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ch_tile_kernel(ChArgs a, int ti
         });
 
     if (MODE == CH_TARGET) {
-      if (l.wq == l.wc) {  // the diagonal 64 x 64 quadrants; inside them the diagonal 32 x 32 blocks
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int row = ft_row(l, x, e);
-            if ((row & 31) == l.r32 && q0 + row < a.B)
-              out[q0 + row] = ylab[row] >= 0 ? ch_logit(cosine, acc[x][x][e], invq[row], colw[row], scale) : 0.f;
-          }
-      }
+      ft_each(acc, l, [&](float dot, int row, int col) {  // the tile's diagonal
+        if (row == col && q0 + row < a.B) out[q0 + row] = ylab[row] >= 0 ? ch_logit(cosine, dot, invq[row], colw[row], scale) : 0.f;
+      });
     } else if (MODE == CH_DZ || MODE == CH_LOGITS) {
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const int lc = l.wc * 64 + b * 32 + l.r32;
-          const int col = c0 + lc;
-          const float cw = colw[lc];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int row = ft_row(l, x, e);
-            if (q0 + row < a.B && col < a.C) {
-              const float z = ch_logit(cosine, acc[x][b][e], invq[row], cw, scale);
-              float v = z;
-              if (MODE == CH_DZ) {
-                const int y = ylab[row];
-                v = y >= 0 ? __fmul_rn(__fsub_rn(expf(__fsub_rn(z, rowl[row])), col == y ? 1.f : 0.f), coef) : 0.f;
-              }
-              out[(size_t)(q0 + row) * a.C + col] = v;
-            }
+      ft_each(acc, l, [&](float dot, int row, int lc) {
+        const int col = c0 + lc;
+        const float cw = colw[lc];  // ahead of the bounds test: one LDS read per column, not one per dot
+        if (q0 + row < a.B && col < a.C) {
+          const float z = ch_logit(cosine, dot, invq[row], cw, scale);
+          float v = z;
+          if (MODE == CH_DZ) {
+            const int y = ylab[row];
+            v = y >= 0 ? __fmul_rn(__fsub_rn(expf(__fsub_rn(z, rowl[row])), col == y ? 1.f : 0.f), coef) : 0.f;
           }
+          out[(size_t)(q0 + row) * a.C + col] = v;
         }
+      });
     } else {
       float m = -INFINITY, ssum = 0.f;
       int ahead = 0;
       __syncthreads();  // every wave is done with the staged chunk: the half-tile takes its place
       for (int h = 0; h < 2; ++h) {
         ft_put_half(stage, acc, l, h, [&](float dot, int row, int col) {
-          const bool in = c0 + h * 64 + col < a.C;
-          return in ? ch_logit(cosine, dot, invq[row], colw[h * 64 + col], scale) : -INFINITY;
+          return c0 + col < a.C ? ch_logit(cosine, dot, invq[row], colw[col], scale) : -INFINITY;
         });
         __syncthreads();
         if (owner) {
@@ -339,8 +314,7 @@ __global__ __launch_bounds__(256) void ch_contract_kernel(const float* __restric
     if (row >= R) continue;  // wave-uniform
     float d = 0.f, ix = 1.f;
     if (COS) {
-      d = dot[u];
-      for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+      d = ft_wave_sum(dot[u]);
       ix = inv_x[row];
       if (tdot && lane == 0) tdot[row] = d;
       if (ix >= __fdiv_rn(1.f, CH_NORM_EPS)) d = 0.f;  // at the clamp x^ = x / eps: no projection term
@@ -414,13 +388,8 @@ extern "C" int32_t vsx_cls_ce_fwd(const float* h, const float* W, const int64_t*
             (long)vsx_cls_ce_fwd_ws_bytes(B, H, C), (long)ws_bytes);
   const int qtiles = (B + FT_T - 1) / FT_T, ntiles = (C + FT_T - 1) / FT_T;
   VSX_CHECK(splits >= 0, "vsx_cls_ce_fwd: splits=%d (0 = chosen here)", splits);
-  if (splits == 0) {  // fill two workgroup slots per compute unit
-    const long want = (2L * vsx_cu_count() + qtiles - 1) / qtiles;
-    splits = (int)(want < 1 ? 1 : want);
-  }
-  if (splits > ntiles) splits = ntiles;
-  const int tps = (ntiles + splits - 1) / splits;
-  splits = (ntiles + tps - 1) / tps;  // no empty split
+  int tps;  // splits = 0: fill two workgroup slots per compute unit
+  ft_even_split(ntiles, splits ? splits : (2L * vsx_cu_count() + qtiles - 1) / qtiles, &splits, &tps);
   float* part = (float*)ws;
   float* zy = part + (size_t)ntiles * B * 3;
   const ChArgs a = {h, W, labels, inv_h, inv_w, log_scale, bias, B, H, C};

@@ -31,24 +31,6 @@ __device__ __forceinline__ float mmd_d2(float ni, float nj, float dot) {
 }
 __device__ __forceinline__ float mmd_kval(float ni, float nj, float dot, float two_bw) { return expf(-__fdiv_rn(mmd_d2(ni, nj, dot), two_bw)); }
 
-// four features of row `row` from feature kk on; zeros past the row's end or for row >= nrows
-template <bool VEC>
-__device__ __forceinline__ float4 mmd_row4(const float* __restrict__ x, int row, int nrows, int d, int kk) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (row < nrows) {
-    const float* src = x + (size_t)row * d + kk;
-    if (VEC) {
-      if (kk < d) v = *reinterpret_cast<const float4*>(src);
-    } else {
-      if (kk < d) v.x = src[0];
-      if (kk + 1 < d) v.y = src[1];
-      if (kk + 2 < d) v.z = src[2];
-      if (kk + 3 < d) v.w = src[3];
-    }
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------ (a) centring: pooled column mean, centred rows, squared norms
 // 16 columns x 16 row lanes per workgroup; a row lane sums its rows in ascending order in float64, the lanes are folded 0 .. 15
 __global__ __launch_bounds__(256) void mmd_colmean_kernel(const float* __restrict__ x, float* __restrict__ mean, int N, int d) {
@@ -80,7 +62,7 @@ __global__ __launch_bounds__(256) void mmd_centre_kernel(const float* __restrict
     cr[c] = v;
     ss = fmaf(v, v, ss);
   }
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  ss = ft_wave_sum(ss);
   if (lane == 0) nrm[row] = ss;
 }
 
@@ -130,40 +112,27 @@ __global__ __launch_bounds__(FT_THREADS, 1) void mmd_sums_kernel(const float* __
 
   const FtLane l = ft_lane();
   const int t = l.t;
-  const int q0 = blockIdx.x * FT_T;
-  const int ntiles = (N + FT_T - 1) / FT_T;
-  const int ct0 = blockIdx.y * tiles_per_split;
-  const int ct1 = min(ct0 + tiles_per_split, ntiles);
-  const int nchunks = (d + FT_KC - 1) / FT_KC;
+  const FtRange g = ft_range(N, d, tiles_per_split);
+  const int q0 = g.q0;
   const int Pp = P + 1;
   const int npc = (Pp + MM_PC - 1) / MM_PC;
   double* wsq = ws + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * (size_t)Pp;
   const int zrow = t >> 1, zoff = (t & 1) * 64;  // this thread's share of a label tile: row, first column
 
-  if (t < FT_T) nq[t] = q0 + t < N ? nrm[q0 + t] : 0.f;
+  ft_side(nq, nrm, q0, N, 0.f);
 
-  for (int ct = ct0; ct < ct1; ++ct) {
+  for (int ct = g.ct0; ct < g.ct1; ++ct) {
     const int c0 = ct * FT_T;
     ft_f32x16 acc[2][2];
     ft_dots(
-        acc, ktile, l, nchunks, [&](int operand, int r, int kk) { return mmd_row4<VEC>(xc, (operand ? c0 : q0) + r, N, d, kk); },
-        [&] {
-          if (t < FT_T) nc[t] = c0 + t < N ? nrm[c0 + t] : 0.f;
-        });
+        acc, ktile, l, g.nchunks, [&](int operand, int r, int kk) { return ft_row4<VEC>(xc, (operand ? c0 : q0) + r, N, d, kk); },
+        [&] { ft_side(nc, nrm, c0, N, 0.f); });
     __syncthreads();  // every wave is done with the staged chunk: the kernel tile takes its place
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int col = l.wc * 64 + b * 32 + l.r32;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = ft_row(l, a, e);
-          const int gi = q0 + row, gj = c0 + col;
-          const bool ok = gi < N && gj < N && gi != gj;
-          ktile[row * MM_KLD + col] = ok ? mmd_kval(nq[row], nc[col], acc[a][b][e], two_bw) : 0.f;
-        }
-      }
+    ft_each(acc, l, [&](float dot, int row, int col) {
+      const int gi = q0 + row, gj = c0 + col;
+      const bool ok = gi < N && gj < N && gi != gj;
+      ktile[row * MM_KLD + col] = ok ? mmd_kval(nq[row], nc[col], dot, two_bw) : 0.f;
+    });
 
     uint32_t lc[16], lq[16];
     mmd_fetch_labels<VECZ>(lc, z, zrow, P, c0 + zoff, N);
@@ -180,14 +149,9 @@ __global__ __launch_bounds__(FT_THREADS, 1) void mmd_sums_kernel(const float* __
         mmd_fetch_labels<VECZ>(lq, z, (long)(pc + 1) * MM_PC + zrow, P, q0 + zoff, N);
       }
 
-      // S = K tile (128 rows x 128 columns) x labels' (128 columns x 128 label vectors); the operand map is ft_dots'
+      // S = K tile (128 rows x 128 columns) x labels' (128 columns x 128 label vectors)
       ft_f32x16 s2[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) s2[a][b][e] = 0.f;
+      ft_zero(s2);
       const float* ka = ktile + (l.wq * 64 + l.r32) * MM_KLD + 4 * l.hh;
       const uint8_t* zb = zc + (l.wc * 64 + l.r32) * MM_ZLD + 4 * l.hh;
 #pragma unroll 4
@@ -196,15 +160,10 @@ __global__ __launch_bounds__(FT_THREADS, 1) void mmd_sums_kernel(const float* __
         const float4 a1 = *reinterpret_cast<const float4*>(ka + 32 * MM_KLD + 8 * p8);
         const uint32_t w0 = *reinterpret_cast<const uint32_t*>(zb + 8 * p8);
         const uint32_t w1 = *reinterpret_cast<const uint32_t*>(zb + 32 * MM_ZLD + 8 * p8);
-        const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
+        float b0[4], b1[4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const float b0 = (float)((w0 >> (8 * s)) & 0xffu), b1 = (float)((w1 >> (8 * s)) & 0xffu);
-          s2[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], b0, s2[0][0], 0, 0, 0);
-          s2[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s], b1, s2[0][1], 0, 0, 0);
-          s2[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], b0, s2[1][0], 0, 0, 0);
-          s2[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s], b1, s2[1][1], 0, 0, 0);
-        }
+        for (int s = 0; s < 4; ++s) b0[s] = (float)((w0 >> (8 * s)) & 0xffu), b1[s] = (float)((w1 >> (8 * s)) & 0xffu);
+        ft_mma_step(s2, a0, a1, b0, b1);
       }
 
       // the lane's 32 rows of label vector pcol, in float64: all of them (zr) and those the vector labels 1 (quad)
@@ -234,7 +193,7 @@ __global__ __launch_bounds__(FT_THREADS, 1) void mmd_sums_kernel(const float* __
         const int tp = t & (MM_PC - 1);
         const double v = ((red[which][0][0][tp] + red[which][0][1][tp]) + red[which][1][0][tp]) + red[which][1][1][tp];
         double* dst = wsq + (size_t)which * Pp + p;
-        *dst = ct == ct0 ? v : *dst + v;  // only this workgroup touches its row of the workspace
+        *dst = ct == g.ct0 ? v : *dst + v;  // only this workgroup touches its row of the workspace
       }
     }
   }
@@ -265,31 +224,19 @@ __global__ __launch_bounds__(FT_THREADS, 2) void mmd_rbf_block_kernel(const floa
   __shared__ __attribute__((aligned(16))) float stage[FT_STAGE];
   __shared__ float nq[FT_T], nc[FT_T];
   const FtLane l = ft_lane();
-  const int t = l.t;
   const int q0 = r0 + blockIdx.y * FT_T, cb = c0 + blockIdx.x * FT_T;
-  if (t < FT_T) {
-    nq[t] = q0 + t < r1 ? nrm[q0 + t] : 0.f;
-    nc[t] = cb + t < c1 ? nrm[cb + t] : 0.f;
-  }
+  ft_side(nq, nrm, q0, r1, 0.f);
+  ft_side(nc, nrm, cb, c1, 0.f);
   ft_f32x16 acc[2][2];
   ft_dots(
       acc, stage, l, (d + FT_KC - 1) / FT_KC,
-      [&](int operand, int r, int kk) { return operand ? mmd_row4<VEC>(xc, cb + r, c1, d, kk) : mmd_row4<VEC>(xc, q0 + r, r1, d, kk); }, [] {});
+      [&](int operand, int r, int kk) { return operand ? ft_row4<VEC>(xc, cb + r, c1, d, kk) : ft_row4<VEC>(xc, q0 + r, r1, d, kk); }, [] {});
   const size_t ld = (size_t)(c1 - c0);
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int col = l.wc * 64 + b * 32 + l.r32;
-      const int gj = cb + col;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = ft_row(l, a, e);
-        const int gi = q0 + row;
-        if (gi < r1 && gj < c1)
-          out[(size_t)(gi - r0) * ld + (size_t)(gj - c0)] = (zero_diag && gi == gj) ? 0.f : mmd_kval(nq[row], nc[col], acc[a][b][e], two_bw);
-      }
-    }
+  ft_each(acc, l, [&](float dot, int row, int col) {
+    const int gi = q0 + row, gj = cb + col;
+    if (gi < r1 && gj < c1)
+      out[(size_t)(gi - r0) * ld + (size_t)(gj - c0)] = (zero_diag && gi == gj) ? 0.f : mmd_kval(nq[row], nc[col], dot, two_bw);
+  });
 }
 
 // ------------------------------------------------------------------ (d) strict upper triangle of squared distances, one row
@@ -300,29 +247,17 @@ __global__ __launch_bounds__(FT_THREADS, 2) void mmd_sqdist_upper_kernel(const f
   __shared__ float nq[FT_T], nc[FT_T];
   if (blockIdx.x < blockIdx.y) return;  // the tile lies below the diagonal (uniform over the workgroup)
   const FtLane l = ft_lane();
-  const int t = l.t;
   const int q0 = blockIdx.y * FT_T, cb = blockIdx.x * FT_T;
-  if (t < FT_T) {
-    nq[t] = q0 + t < M ? nrm[q0 + t] : 0.f;
-    nc[t] = cb + t < M ? nrm[cb + t] : 0.f;
-  }
+  ft_side(nq, nrm, q0, M, 0.f);
+  ft_side(nc, nrm, cb, M, 0.f);
   ft_f32x16 acc[2][2];
   ft_dots(
-      acc, stage, l, (d + FT_KC - 1) / FT_KC, [&](int operand, int r, int kk) { return mmd_row4<VEC>(xc, (operand ? cb : q0) + r, M, d, kk); },
+      acc, stage, l, (d + FT_KC - 1) / FT_KC, [&](int operand, int r, int kk) { return ft_row4<VEC>(xc, (operand ? cb : q0) + r, M, d, kk); },
       [] {});
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int col = l.wc * 64 + b * 32 + l.r32;
-      const long gj = cb + col;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = ft_row(l, a, e);
-        const long gi = q0 + row;
-        if (gi < gj && gj < M) out[gi * (2L * M - gi - 1) / 2 + (gj - gi - 1)] = mmd_d2(nq[row], nc[col], acc[a][b][e]);
-      }
-    }
+  ft_each(acc, l, [&](float dot, int row, int col) {
+    const long gi = q0 + row, gj = cb + col;
+    if (gi < gj && gj < M) out[gi * (2L * M - gi - 1) / 2 + (gj - gi - 1)] = mmd_d2(nq[row], nc[col], dot);
+  });
 }
 
 // ------------------------------------------------------------------ host
@@ -352,11 +287,8 @@ extern "C" int32_t vsx_mmd_prepare(const float* x, float* xc, float* norms, floa
 // how many workgroups share the column tiles of one row tile: a function of N alone
 static void mm_split(int N, int* tiles, int* splits, int* tps) {
   *tiles = (N + FT_T - 1) / FT_T;
-  int s = (MM_WANT_WGS + *tiles - 1) / *tiles;
-  s = s < 1 ? 1 : (s > MM_MAX_SPLITS ? MM_MAX_SPLITS : s);
-  if (s > *tiles) s = *tiles;
-  *tps = (*tiles + s - 1) / s;
-  *splits = (*tiles + *tps - 1) / *tps;  // no empty split
+  const int want = (MM_WANT_WGS + *tiles - 1) / *tiles;
+  ft_even_split(*tiles, want > MM_MAX_SPLITS ? MM_MAX_SPLITS : want, splits, tps);
 }
 
 extern "C" int64_t vsx_mmd_sums_ws_bytes(int32_t N, int32_t P) {
@@ -380,7 +312,7 @@ extern "C" int32_t vsx_mmd_sums(const float* xc, const float* norms, const uint8
             (long)vsx_mmd_sums_ws_bytes(N, P), (long)ws_bytes);
   int tiles, splits, tps;
   mm_split(N, &tiles, &splits, &tps);
-  const bool vec = d % 4 == 0 && vsx_al16(xc);
+  const bool vec = ft_vec_ok(xc, d);
   const bool vecz = N % 16 == 0 && vsx_al16(labels);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)tiles, (unsigned)splits), block(FT_THREADS);
@@ -408,7 +340,7 @@ extern "C" int32_t vsx_rbf_block(const float* xc, const float* norms, int32_t N,
   const dim3 grid((unsigned)((c1 - c0 + FT_T - 1) / FT_T), (unsigned)((r1 - r0 + FT_T - 1) / FT_T)), block(FT_THREADS);
   VSX_CHECK(grid.y <= 65535u, "vsx_rbf_block: at most %d rows per call (got %ld)", 65535 * FT_T, (long)(r1 - r0));
   hipStream_t s = (hipStream_t)stream;
-  if (d % 4 == 0 && vsx_al16(xc))
+  if (ft_vec_ok(xc, d))
     hipLaunchKernelGGL(mmd_rbf_block_kernel<true>, grid, block, 0, s, xc, norms, d, r0, r1, c0, c1, two_bw, zero_diag, out);
   else
     hipLaunchKernelGGL(mmd_rbf_block_kernel<false>, grid, block, 0, s, xc, norms, d, r0, r1, c0, c1, two_bw, zero_diag, out);
@@ -424,7 +356,7 @@ extern "C" int32_t vsx_sqdist_upper(const float* xc, const float* norms, int32_t
   const unsigned nt = (unsigned)((M + FT_T - 1) / FT_T);
   const dim3 grid(nt, nt), block(FT_THREADS);
   hipStream_t s = (hipStream_t)stream;
-  if (d % 4 == 0 && vsx_al16(xc))
+  if (ft_vec_ok(xc, d))
     hipLaunchKernelGGL(mmd_sqdist_upper_kernel<true>, grid, block, 0, s, xc, norms, M, d, out);
   else
     hipLaunchKernelGGL(mmd_sqdist_upper_kernel<false>, grid, block, 0, s, xc, norms, M, d, out);

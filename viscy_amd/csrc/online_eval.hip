@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void pair_cosine_dist_kernel(const float* __re
   const float* xj = x + (size_t)j * d;
   float dot = 0.f;
   for (int c = lane; c < d; c += 64) dot = fmaf(xi[c], xj[c], dot);
-  for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+  dot = ft_wave_sum(dot);
   if (lane == 0) out[p] = __fsub_rn(1.f, __fmul_rn(__fmul_rn(dot, inv[i]), inv[j]));
 }
 
@@ -62,58 +62,33 @@ __global__ __launch_bounds__(FT_THREADS, KB <= 24 ? 2 : 1) void knn_topk_kernel(
 
   const FtLane l = ft_lane();
   const int t = l.t;
-  const int q0 = blockIdx.x * FT_T;
-  const int ntiles = (N + FT_T - 1) / FT_T;
-  const int ct0 = blockIdx.y * tiles_per_split;
-  const int ct1 = min(ct0 + tiles_per_split, ntiles);
-  const int nchunks = (d + FT_KC - 1) / FT_KC;
+  const FtRange g = ft_range(N, d, tiles_per_split);
+  const int q0 = g.q0;
 
-  if (t < FT_T) {
-    const int i = q0 + t;
-    gq[t] = i < N ? group[i] : -1;
-    invq[t] = i < N ? inv[i] : 0.f;
-  }
+  ft_side(gq, group, q0, N, -1);
+  ft_side(invq, inv, q0, N, 0.f);
   // the owner of query row t keeps the row's count and its k-th best in registers
   const bool owner = t < FT_T && q0 + t < N;
   int cnt = 0;
   float thr_s = 0.f;
   int thr_j = 0;
 
-  for (int ct = ct0; ct < ct1; ++ct) {
+  for (int ct = g.ct0; ct < g.ct1; ++ct) {
     const int c0 = ct * FT_T;
     ft_f32x16 acc[2][2];
     ft_dots(
-        acc, stage, l, nchunks,
-        [&](int operand, int r, int kk) {
-          const int row = (operand ? c0 : q0) + r;
-          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (row < N) {
-            const float* src = x + (size_t)row * d + kk;
-            if (VEC) {
-              if (kk < d) v = *reinterpret_cast<const float4*>(src);
-            } else {
-              if (kk < d) v.x = src[0];
-              if (kk + 1 < d) v.y = src[1];
-              if (kk + 2 < d) v.z = src[2];
-              if (kk + 3 < d) v.w = src[3];
-            }
-          }
-          return v;
-        },
+        acc, stage, l, g.nchunks, [&](int operand, int r, int kk) { return ft_row4<VEC>(x, (operand ? c0 : q0) + r, N, d, kk); },
         [&] {
-          if (t < FT_T) {
-            const int j = c0 + t;
-            gc[t] = j < N ? group[j] : -1;
-            invc[t] = j < N ? inv[j] : 0.f;
-          }
+          ft_side(gc, group, c0, N, -1);
+          ft_side(invc, inv, c0, N, 0.f);
         });
     __syncthreads();  // every wave is done with the staged chunk: the half-tile takes its place
 
     for (int h = 0; h < 2; ++h) {
       ft_put_half(stage, acc, l, h, [&](float dot, int row, int col) {
-        const int gj = gc[h * 64 + col];
+        const int gj = gc[col];
         const bool ok = gj >= 0 && gj != gq[row];
-        const float s = __fmul_rn(__fmul_rn(dot, invq[row]), invc[h * 64 + col]);
+        const float s = __fmul_rn(__fmul_rn(dot, invq[row]), invc[col]);
         return ok ? s : __builtin_nanf("");
       });
       __syncthreads();
@@ -243,8 +218,9 @@ static int kt_splits(int qtiles, int ctiles, int cus) {
   int best = 1;
   double best_eff = 0.0;
   for (int s = 1; s <= KT_MAX_SPLITS && s <= ctiles; ++s) {
-    const int tps = (ctiles + s - 1) / s;
-    if ((long)(s - 1) * tps >= ctiles) continue;  // the last split would be empty
+    int n, tps;
+    ft_even_split(ctiles, s, &n, &tps);
+    if (n != s) continue;  // the last split would be empty
     const long wgs = (long)qtiles * s;
     const double eff = (double)wgs / (double)(((wgs + slots - 1) / slots) * slots);
     if (eff > best_eff * 1.02) {
@@ -263,12 +239,12 @@ extern "C" int32_t vsx_knn_topk(const float* x, const float* inv, const int32_t*
             "vsx_knn_topk: the workspace must be 4-byte aligned and hold vsx_knn_topk_ws_bytes = %ld bytes (got %ld)",
             (long)vsx_knn_topk_ws_bytes(N, d, k), (long)ws_bytes);
   const int qtiles = (N + FT_T - 1) / FT_T, ctiles = qtiles;
-  const int splits = kt_splits(qtiles, ctiles, vsx_cu_count());
-  const int tps = (ctiles + splits - 1) / splits;
+  int splits, tps;
+  ft_even_split(ctiles, kt_splits(qtiles, ctiles, vsx_cu_count()), &splits, &tps);
   int* pidx = (int*)ws;
   float* psim = (float*)(pidx + (size_t)splits * N * k);
   int* pcnt = (int*)(psim + (size_t)splits * N * k);
-  const bool vec = d % 4 == 0 && vsx_al16(x);
+  const bool vec = ft_vec_ok(x, d);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)qtiles, (unsigned)splits), block(FT_THREADS);
 #define KT_GO(VEC, KB) hipLaunchKernelGGL((knn_topk_kernel<VEC, KB>), grid, block, 0, s, x, inv, group, N, d, k, tps, pidx, psim, pcnt)

@@ -1160,6 +1160,17 @@ def _i32(t: Tensor, n: int, what: str) -> Tensor:
     return t
 
 
+def _f32_vec(t: Tensor, n: int, what: str) -> None:
+    ptr(t)
+    if t.dtype != torch.float32 or t.numel() != n:
+        raise TypeError(f"{what} must be {n} float32 values")
+
+
+def _ws(dev, nbytes: int, dtype: torch.dtype, min_elems: int = 1) -> Tensor:
+    """a workspace of ``dtype`` that holds ``nbytes`` bytes and at least ``min_elems`` elements; ``ws.nbytes`` is its size"""
+    return torch.empty(max(-(-int(nbytes) // dtype.itemsize), min_elems), dtype=dtype, device=dev)
+
+
 def row_inv_norm(x: Tensor, eps: float = 0.0) -> Tensor:
     """inv[i] = 1 / (||x_i||_2 + eps); 0 where that denominator is 0 (an all-zero row with eps = 0, as sklearn's ``normalize``)"""
     n, d = _rows_f32(x, "row_inv_norm")
@@ -1173,19 +1184,16 @@ def knn_topk(x: Tensor, inv: Tensor, group: Tensor, k: int):
     OTHER groups (``group[j] >= 0 and group[j] != group[i]``), s = fl32(fl32(dot * inv_i) * inv_j), in the total order
     (s descending, j ascending); unused slots idx = -1, sim = -inf.  No N x N buffer: the workspace is O(N k)."""
     n, d = _rows_f32(x, "knn_topk")
-    if inv.dtype != torch.float32 or inv.numel() != n:
-        raise TypeError(f"knn_topk: inv must be {n} float32 values")
+    _f32_vec(inv, n, "knn_topk: inv")
     _i32(group, n, "knn_topk: group")
     k = int(k)
     if not 1 <= k <= KNN_MAX_K:  # the library refuses it too; here before anything is allocated
         raise ValueError(f"knn_topk: k={k} must be in [1, {KNN_MAX_K}]")
-    nbytes = int(lib().vsx_knn_topk_ws_bytes(n, d, k))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=x.device)
+    ws = _ws(x.device, lib().vsx_knn_topk_ws_bytes(n, d, k), torch.int32, 0)
     idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
     sim = torch.empty((n, k), dtype=torch.float32, device=x.device)
     cnt = torch.empty(n, dtype=torch.int32, device=x.device)
-    check(lib().vsx_knn_topk(ptr(x), ptr(inv), ptr(group), n, d, k, ptr(idx), ptr(sim), ptr(cnt), ptr(ws), ws.numel() * 4, stream()),
-          "knn_topk")
+    check(lib().vsx_knn_topk(ptr(x), ptr(inv), ptr(group), n, d, k, ptr(idx), ptr(sim), ptr(cnt), ptr(ws), ws.nbytes, stream()), "knn_topk")
     return idx, sim, cnt
 
 
@@ -1205,8 +1213,7 @@ def knn_vote(idx: Tensor, cnt: Tensor, labels: Tensor) -> Tensor:
 def pair_cosine_dist(x: Tensor, inv: Tensor, pi: Tensor, pj: Tensor) -> Tensor:
     """out[p] = 1 - fl32(fl32(dot(x[pi[p]], x[pj[p]]) * inv[pi[p]]) * inv[pj[p]])"""
     n, d = _rows_f32(x, "pair_cosine_dist")
-    if inv.dtype != torch.float32 or inv.numel() != n:
-        raise TypeError(f"pair_cosine_dist: inv must be {n} float32 values")
+    _f32_vec(inv, n, "pair_cosine_dist: inv")
     p = pi.numel()
     _i32(pi, p, "pair_cosine_dist: pi")
     _i32(pj, p, "pair_cosine_dist: pj")
@@ -1249,12 +1256,11 @@ def cls_ce_fwd(h: Tensor, W: Tensor, labels: Tensor, k: int, *, inv_h: Tensor | 
     k = int(k)
     if not 1 <= k <= Cn:  # the library refuses it too; here before anything is allocated
         raise ValueError(f"cls_ce_fwd: k={k} must be in [1, C={Cn}]")
-    nbytes = int(lib().vsx_cls_ce_fwd_ws_bytes(B, H, Cn))
-    ws = torch.empty(max((nbytes + 3) // 4, 1), dtype=torch.float32, device=h.device)
+    ws = _ws(h.device, lib().vsx_cls_ce_fwd_ws_bytes(B, H, Cn), torch.float32)
     rows = torch.empty((B, 4), dtype=torch.float32, device=h.device)
     acc = torch.empty(4, dtype=torch.float32, device=h.device)
     check(lib().vsx_cls_ce_fwd(ptr(h), ptr(W), ptr(labels), ptr(inv_h), ptr(inv_w), ptr(log_scale), ptr(bias), B, H, Cn, k,
-                               int(splits), ptr(rows), ptr(acc), ptr(ws), ws.numel() * 4, stream()), "cls_ce_fwd")
+                               int(splits), ptr(rows), ptr(acc), ptr(ws), ws.nbytes, stream()), "cls_ce_fwd")
     return rows, acc
 
 
@@ -1278,12 +1284,11 @@ def cls_ce_bwd(h: Tensor, W: Tensor, labels: Tensor, rows: Tensor, acc: Tensor, 
             raise TypeError("cls_ce_bwd: gradient and statistics buffers must be float32")
     if dW.shape != W.shape:
         raise ValueError(f"cls_ce_bwd: dW {tuple(dW.shape)} must have W's shape {tuple(W.shape)}")
-    nbytes = int(lib().vsx_cls_ce_bwd_ws_bytes(B, H, Cn))
-    ws = torch.empty(max((nbytes + 3) // 4, 4), dtype=torch.float32, device=h.device)
+    ws = _ws(h.device, lib().vsx_cls_ce_bwd_ws_bytes(B, H, Cn), torch.float32, 4)
     dh = torch.empty_like(h)
     check(lib().vsx_cls_ce_bwd(ptr(h), ptr(W), ptr(labels), ptr(inv_h), ptr(inv_w), ptr(log_scale), ptr(bias), ptr(rows), ptr(acc),
-                               ptr(gout), B, H, Cn, ptr(dh), ptr(dW), ptr(dbias), ptr(dlog_scale), ptr(ws), ws.numel() * 4,
-                               stream()), "cls_ce_bwd")
+                               ptr(gout), B, H, Cn, ptr(dh), ptr(dW), ptr(dbias), ptr(dlog_scale), ptr(ws), ws.nbytes, stream()),
+          "cls_ce_bwd")
     return dh
 
 
@@ -1301,9 +1306,7 @@ def mmd_prepare(x: Tensor) -> tuple[Tensor, Tensor, Tensor]:
 
 def _mmd_pool(xc: Tensor, norms: Tensor, what: str) -> tuple[int, int]:
     n, d = _rows_f32(xc, what)
-    ptr(norms)
-    if norms.dtype != torch.float32 or norms.numel() != n:
-        raise TypeError(f"{what}: norms must be {n} float32 values")
+    _f32_vec(norms, n, f"{what}: norms")
     return n, d
 
 
@@ -1316,11 +1319,9 @@ def mmd_sums(xc: Tensor, norms: Tensor, labels: Tensor, bandwidth: float) -> Ten
     if labels.dtype != torch.uint8 or labels.dim() != 2 or labels.shape[1] != n or labels.shape[0] < 1:
         raise TypeError(f"mmd_sums: labels must be a uint8 (P, {n}) tensor, got {labels.dtype} {tuple(labels.shape)}")
     P = labels.shape[0]
-    nbytes = int(lib().vsx_mmd_sums_ws_bytes(n, P))
-    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=xc.device)
+    ws = _ws(xc.device, lib().vsx_mmd_sums_ws_bytes(n, P), torch.float64)
     sums = torch.empty((P, 3), dtype=torch.float64, device=xc.device)
-    check(lib().vsx_mmd_sums(ptr(xc), ptr(norms), ptr(labels), n, d, P, float(bandwidth), ptr(sums), ptr(ws), ws.numel() * 8, stream()),
-          "mmd_sums")
+    check(lib().vsx_mmd_sums(ptr(xc), ptr(norms), ptr(labels), n, d, P, float(bandwidth), ptr(sums), ptr(ws), ws.nbytes, stream()), "mmd_sums")
     return sums
 
 
