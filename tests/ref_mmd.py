@@ -15,7 +15,7 @@ CASES = {
     "n200_m157_d768_p257": dict(n=200, m=157, d=768, P=257, shift=0.15, offset=0.0, seed=104, pseed=42),  # three tiles, P crosses 256
     "n150_m150_d16_p200_null": dict(n=150, m=150, d=16, P=200, shift=0.0, offset=0.0, seed=5326, pseed=42),  # mid-range p-value; seed searched for gap >= 100 err_ref
     "n90_m100_d64_p100_offset10": dict(n=90, m=100, d=64, P=100, shift=0.2, offset=10.0, seed=106, pseed=42),  # fails without centring
-    "n600_m500_d16_p40": dict(n=600, m=500, d=16, P=40, shift=0.1, offset=0.0, seed=107, pseed=42),    # nine tiles: column splits; subsampled median
+    "n600_m500_d16_p40": dict(n=600, m=500, d=16, P=40, shift=0.1, offset=0.0, seed=107, pseed=42),    # 9 tiles = 9 splits x 1 tile (two per split from N = 2945: ref_exact_tile.py); subsampled median
     "n2_m2_d1_p1": dict(n=2, m=2, d=1, P=1, shift=1.0, offset=0.0, seed=108, pseed=43),                # tiny; pseed 43 draws a mixed split
 }
 LABEL_CASES = ("n20_m23_d5_p50", "n2_m2_d1_p1")          # the golden stores the reference's label matrix

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import ref_exact_tile as XT
 from tests import ref_mmd as RM
 from tests.conftest import load_golden
 
@@ -107,7 +108,10 @@ def test_gaussian_rbf_kernel_against_the_reference(name):
 
 
 # ------------------------------------------------------------------------------------------------ exact properties of the tile
-POOLS = ("case357", "n272_d20")  # N % 16 != 0, d % 4 == 0: byte label loads;  N % 16 == 0: 16-byte label loads
+# N % 16 != 0, d % 4 == 0: byte label loads;  N % 16 == 0: 16-byte label loads;  25 column tiles in 13 splits of 2, the last of 1
+# (tests/ref_exact_tile.mmd_plan): real kernel values on the accumulation over tiles, which the 0 / 1 values of
+# tests/test_gpu_tile_exact.py cannot tell from values with a wrong exponent of the same class
+POOLS = ("case357", "n272_d20", "n3075_d12")
 
 
 @functools.lru_cache(maxsize=None)
@@ -117,8 +121,10 @@ def _pool(kind):
 
     if kind == "case357":
         x, bw = np.concatenate(RM.build("n200_m157_d768_p257")), golden()["n200_m157_d768_p257"]["bandwidth"]
-    else:
+    elif kind == "n272_d20":
         x, bw = np.random.RandomState(7).randn(272, 20).astype(np.float32), 18.0
+    else:   # squared distances of unit normal rows: mean 2 d = 24, the median a little below
+        x, bw = np.random.RandomState(11).randn(3075, 12).astype(np.float32), 23.0
     xc, norms, mean = ops.mmd_prepare(torch.from_numpy(x).to(DEV))
     N = len(x)
     assert np.abs(mean.cpu().numpy() - x.astype(np.float64).mean(0)).max() <= 2.0 ** -23 * np.abs(x).max()
@@ -127,7 +133,19 @@ def _pool(kind):
 
 
 def _pairs(N):
-    return [(0, 127), (127, 128), (0, N - 1), (N - 2, N - 1), (5, 5 + 128)]
+    """(i, j) for the two-hot label vectors: tile corners and, where mmd_plan(N) gives a workgroup two or more column tiles, pairs
+    in the second tile of a split, in two different splits, in the short last split and in the tail tile (row i meets column j
+    and row j column i)"""
+    pairs = [(0, 127), (127, 128), (0, N - 1), (N - 2, N - 1), (5, 5 + 128)]
+    tiles, splits, tps, last = XT.mmd_plan(N)
+    if tps >= 2:
+        T, mid = XT.T, (splits // 2) * tps
+        pairs += [(7, (mid + 1) * T + 9),                      # the second tile of a split; the rows' own split is the first
+                  (mid * T + 3, (mid + 1) * T + 64),           # the first and the second tile of one split
+                  ((tps + 1) * T + 1, (mid + tps + 1) * T + 5),  # second tiles of two different splits
+                  (200, (splits - 1) * tps * T + (N - 1 - (splits - 1) * tps * T) // 2),   # the last split
+                  ((mid + 1) * T + 2, N - 1 - (N - 1) % T)]    # the first row of the tail tile
+    return pairs
 
 
 @pytest.mark.parametrize("kind", POOLS)

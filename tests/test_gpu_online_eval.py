@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import ref_exact_tile as XT
 from tests import ref_online_eval as RO
 from tests.conftest import load_golden
 
@@ -57,13 +58,19 @@ def _exact_case(N, d, k, gkind, ikind):
     return x, inv, group, idx, sim, cnt
 
 
-def _raw_topk(x, inv, group, k):
-    """vsx_knn_topk on buffers pre-filled with sentinels (and a workspace full of junk): every slot must be written"""
+def _raw_topk(x, inv, group, k, x_offset=0):
+    """vsx_knn_topk on buffers pre-filled with sentinels (and a workspace full of junk): every slot must be written.
+    x_offset: the rows start that many floats past a 16-byte boundary"""
     from viscy_amd import _lib
 
     L = _lib.lib()
     N, d = x.shape
     xd, invd, gd = (torch.from_numpy(a).to(DEV) for a in (x, inv, group))
+    if x_offset:
+        buf = torch.empty(N * d + x_offset, dtype=torch.float32, device=DEV)
+        buf[x_offset:].copy_(xd.view(-1))
+        xd = buf[x_offset:].view(N, d)
+        assert buf.data_ptr() % 16 == 0 and xd.data_ptr() % 16 == 4 * x_offset % 16 != 0 and xd.is_contiguous()
     idx = torch.full((N, k), -7, dtype=torch.int32, device=DEV)
     sim = torch.full((N, k), 123.0, dtype=torch.float32, device=DEV)
     cnt = torch.full((N,), -7, dtype=torch.int32, device=DEV)
@@ -87,12 +94,24 @@ EXACT = [
     # fewer than k candidates; none
     (65, 4, 7, "few", "pow2"), (257, 33, 20, "few", "ones"), (130, 4, 64, "few", "pow2"),
     (5, 4, 7, "one", "ones"), (129, 3, 20, "one", "pow2"),
+    # two and three candidate tiles per workgroup (tests/ref_exact_tile.KNN_CASES states each leg), one case per KB instance:
+    # KB 8 on scalar loads; KB 24 with a shorter last split; KB 64 with three tiles per split; cnt < k carried across tiles
+    (1153, 3, 7, "folds", "ones"), (1030, 4, 20, "folds", "pow2"), (2171, 33, 64, "folds", "pow2"), (1030, 4, 20, "few", "pow2"),
 ]
+MULTI_TILE = [c["case"] for c in XT.KNN_CASES]
+
+
+def _assert_two_tiles_per_workgroup(N):
+    """the leg with the device's own compute-unit count; a device that gives these sizes one tile per workgroup fails here"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert XT.knn_plan(N, cus)[2] >= 2, (N, cus, XT.knn_leg(N, cus))
 
 
 @pytest.mark.parametrize("N,d,k,gkind,ikind", EXACT, ids=[f"N{c[0]}_d{c[1]}_k{c[2]}_{c[3]}_{c[4]}" for c in EXACT])
 def test_knn_topk_is_bit_equal_to_the_restatement(N, d, k, gkind, ikind):
     x, inv, group, idx_r, sim_r, cnt_r = _exact_case(N, d, k, gkind, ikind)
+    if (N, d, k, gkind, ikind) in MULTI_TILE:
+        _assert_two_tiles_per_workgroup(N)
     idx, sim, cnt = _raw_topk(x, inv, group, k)
     assert np.array_equal(cnt, cnt_r)
     assert np.array_equal(idx, idx_r)
@@ -105,6 +124,17 @@ def test_knn_topk_is_bit_equal_to_the_restatement(N, d, k, gkind, ikind):
         assert (cnt_r[group == 0] == min(4, N - 1)).all() and (idx_r[group == 0, min(4, N - 1):] == -1).all()
     if gkind == "one":
         assert (cnt == 0).all() and (idx == -1).all() and np.isneginf(sim).all()
+
+
+def test_knn_topk_on_rows_off_the_16_byte_grid():
+    """d % 4 == 0 but x only 4-byte aligned: ft_vec_ok is false and the rows come feature by feature; same bits, two tiles per
+    workgroup"""
+    N, d, k, gkind, ikind = XT.KNN_VIEW_CASE
+    assert XT.KNN_VIEW_CASE in EXACT
+    x, inv, group, idx_r, sim_r, cnt_r = _exact_case(N, d, k, gkind, ikind)
+    _assert_two_tiles_per_workgroup(N)
+    idx, sim, cnt = _raw_topk(x, inv, group, k, x_offset=1)
+    assert np.array_equal(cnt, cnt_r) and np.array_equal(idx, idx_r) and np.array_equal(sim.view(np.int32), sim_r.view(np.int32))
 
 
 def test_knn_topk_refuses_what_it_does_not_serve():
@@ -137,20 +167,23 @@ def test_ops_knn_topk_matches_the_raw_call():
     assert np.array_equal(idx.cpu().numpy(), idx_r) and np.array_equal(sim.cpu().numpy(), sim_r) and np.array_equal(cnt.cpu().numpy(), cnt_r)
 
 
-def test_knn_similarities_are_the_classifier_heads_logits_bit_for_bit():
+@pytest.mark.parametrize("N,d,k", [(130, 36, 64), XT.KNN_ORDER_CASE])
+def test_knn_similarities_are_the_classifier_heads_logits_bit_for_bit(N, d, k):
     """csrc/f32_tile.h promises ONE summation order of a dot product for every kernel built on it.  On float rows (integer rows
     cannot see a reordered sum) a similarity of vsx_knn_topk and a cosine logit of vsx_cls_logits over the same two rows are
     both fl32(fl32(dot * inv_i) * inv_j) — times expf(0) = 1 on the head's side — so only the dot's order could tell them apart.
-    N = 130, d = 36: two tiles in each direction, the 64-column half boundary, one chunk plus one float4."""
+    N = 130, d = 36: two tiles in each direction, the 64-column half boundary, one chunk plus one float4.  N = 1030: nine tiles,
+    two per workgroup of the probe, so the order also holds for the second tile a workgroup forms."""
     from viscy_amd import ops
 
-    N, d, k = 130, 36, 64
-    x = torch.randn(N, d, generator=torch.Generator().manual_seed(13036)).to(DEV)
+    if N > 130:
+        _assert_two_tiles_per_workgroup(N)
+    x = torch.randn(N, d, generator=torch.Generator().manual_seed(100 * N + d)).to(DEV)
     inv = ops.row_inv_norm(x, 0.0)
     group = (torch.arange(N, dtype=torch.int32) % 3).to(DEV)
     idx, sim, cnt = ops.knn_topk(x, inv, group, k)
     Z = ops.cls_logits(x, x, inv_h=inv, inv_w=inv, log_scale=torch.zeros(1, device=DEV))
-    assert (cnt == k).all()                                                       # every row has at least 86 candidates
+    assert (cnt == k).all()                                                       # every row has at least 86 candidates (N = 130)
     used = torch.arange(k, device=DEV)[None, :] < cnt[:, None]
     logit = Z.gather(1, idx.clamp_min(0).long())
     assert torch.equal(sim.view(torch.int32)[used], logit.view(torch.int32)[used])
