@@ -822,6 +822,27 @@ int32_t vsx_rbf_block(const float* xc, const float* norms, int32_t N, int32_t d,
     double bandwidth, int32_t zero_diag, float* out, vsx_stream_t stream);
 int32_t vsx_sqdist_upper(const float* xc, const float* norms, int32_t M, int32_t d, float* out, vsx_stream_t stream);
 
+/* The data passes of PCA (csrc/pca.hip; viscy_utils/evaluation/dimensionality_reduction.py compute_pca = StandardScaler -> sklearn PCA):
+ * x [n, d] fp32 row-major, any 4-byte alignment, 2 <= n < 2^31, 1 <= d <= 4096.  No atomics: per-workgroup partials in ws, folded in
+ * ascending order, so every output is bit-identical from run to run for fixed (n, d).  ws: 8-byte aligned, any contents.
+ * col_moments: mean[d] = sum_i x_ij / n, m2[d] = sum_i (x_ij - mean_j)^2, float64 throughout (two passes over x).
+ * gram_centered: gram [d, d] float64 = sum_i c_ij c_il with c_ij = fl32(x_ij - mean_j) (float64 difference, rounded once), both triangles
+ * written and equal bit for bit.  128 x 128 tiles of feature pairs on v_mfma_f32_32x32x2_f32, upper-triangular tile pairs only; fp32
+ * accumulation over blocks of 128 rows, each block sum added to float64 accumulators in ascending block order; the rows are split over
+ * workgroups in runs of vsx_gram_rows_per_split(n, d) rows (a multiple of 128, a function of n and d alone) whose float64 tiles are folded
+ * in split order.  Standard scaling is the caller's: gram_jl / (s_j s_l) in float64.  ws: vsx_gram_ws_bytes(n, d) = splits * pairs * 128 KiB.
+ * center_project: z [n, k] fp32 = (x - mean) w' for w [k, d] fp32, k >= 1: the dots of csrc/f32_tile.h (one summation order) over the
+ * centred rows; fold 1 / scale into w for standardised data.
+ * The size queries answer 0 for shapes that are not served.  Every check runs before any launch. */
+int64_t vsx_col_moments_ws_bytes(int64_t n, int32_t d);
+int32_t vsx_col_moments(const float* x, int64_t n, int32_t d, double* mean, double* m2, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int64_t vsx_gram_ws_bytes(int64_t n, int32_t d);
+int64_t vsx_gram_rows_per_split(int64_t n, int32_t d);
+int32_t vsx_gram_centered(const float* x, int64_t n, int32_t d, const double* mean, double* gram, void* ws, int64_t ws_bytes,
+    vsx_stream_t stream);
+int32_t vsx_center_project(const float* x, int64_t n, int32_t d, const double* mean, const float* w, int32_t k, float* z,
+    vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

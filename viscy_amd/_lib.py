@@ -217,6 +217,12 @@ _SIGS = {
     "vsx_mmd_sums": (_I32, [_P, _P, _P, _I32, _I32, _I32, C.c_double, _P, _P, _I64, _P]),
     "vsx_rbf_block": (_I32, [_P, _P] + [_I32] * 6 + [C.c_double, _I32, _P, _P]),
     "vsx_sqdist_upper": (_I32, [_P, _P, _I32, _I32, _P, _P]),
+    "vsx_col_moments_ws_bytes": (_I64, [_I64, _I32]),
+    "vsx_col_moments": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _P]),
+    "vsx_gram_ws_bytes": (_I64, [_I64, _I32]),
+    "vsx_gram_rows_per_split": (_I64, [_I64, _I32]),
+    "vsx_gram_centered": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _P]),
+    "vsx_center_project": (_I32, [_P, _I64, _I32, _P, _P, _I32, _P, _P]),
 }
 
 _lib = None

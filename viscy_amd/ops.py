@@ -1342,3 +1342,50 @@ def sqdist_upper(xc: Tensor, norms: Tensor) -> Tensor:
     out = torch.empty((1, max(m * (m - 1) // 2, 1)), dtype=torch.float32, device=xc.device)
     check(lib().vsx_sqdist_upper(ptr(xc), ptr(norms), m, d, ptr(out), stream()), "sqdist_upper")
     return out
+
+
+# ------------------------------------------------------------------ PCA data passes (csrc/pca.hip)
+def _f64_vec(t: Tensor, n: int, what: str) -> None:
+    ptr(t)
+    if t.dtype != torch.float64 or t.numel() != n:
+        raise TypeError(f"{what} must be {n} float64 values, got {t.dtype} {tuple(t.shape)}")
+
+
+def col_moments(x: Tensor) -> tuple[Tensor, Tensor]:
+    """-> (mean (d,), m2 (d,)) float64: the column mean and the centred sum of squares of x float32 (n, d), two fixed-order
+    float64 passes; bit-identical from run to run"""
+    n, d = _rows_f32(x, "col_moments")
+    ws = _ws(x.device, lib().vsx_col_moments_ws_bytes(n, d), torch.float64)
+    mean = torch.empty(d, dtype=torch.float64, device=x.device)
+    m2 = torch.empty(d, dtype=torch.float64, device=x.device)
+    check(lib().vsx_col_moments(ptr(x), n, d, ptr(mean), ptr(m2), ptr(ws), ws.nbytes, stream()), "col_moments")
+    return mean, m2
+
+
+def gram_rows_per_split(n: int, d: int) -> int:
+    """rows one workgroup of ``gram_centered`` folds into its float64 tile: a multiple of 128, a function of (n, d) alone"""
+    return int(lib().vsx_gram_rows_per_split(int(n), int(d)))
+
+
+def gram_centered(x: Tensor, mean: Tensor) -> Tensor:
+    """-> float64 (d, d): (x - mean)' (x - mean), symmetric bit for bit; fp32 products on the MFMA summed over blocks of 128 rows,
+    float64 past the block.  The workspace is O(splits d^2)."""
+    n, d = _rows_f32(x, "gram_centered")
+    _f64_vec(mean, d, "gram_centered: mean")
+    ws = _ws(x.device, lib().vsx_gram_ws_bytes(n, d), torch.float64)
+    gram = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    check(lib().vsx_gram_centered(ptr(x), n, d, ptr(mean), ptr(gram), ptr(ws), ws.nbytes, stream()), "gram_centered")
+    return gram
+
+
+def center_project(x: Tensor, mean: Tensor, w: Tensor) -> Tensor:
+    """-> float32 (n, k): (x - mean) w' for w float32 (k, d), the dots of the f32 tile engine over the centred rows"""
+    n, d = _rows_f32(x, "center_project")
+    _f64_vec(mean, d, "center_project: mean")
+    ptr(w)
+    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != d or w.shape[0] < 1:
+        raise TypeError(f"center_project: w must be a float32 (k, {d}) tensor, got {w.dtype} {tuple(w.shape)}")
+    k = w.shape[0]
+    z = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    check(lib().vsx_center_project(ptr(x), n, d, ptr(mean), ptr(w), k, ptr(z), stream()), "center_project")
+    return z
