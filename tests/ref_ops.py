@@ -567,6 +567,17 @@ def bn1d_bwd(dy, x, y, w, sm, sr, dw, db, training, relu):
     return g * (d - sb / B - xh * sg / B) if training else g * d
 
 
+def grn_q_reduce(Q, cs, W2, s, beta, P, S, dW2, db2):
+    """vsx_grn_q_reduce, all four outputs accumulated: from Q[b] = dout_b^T g_b [C, 4C] and cs[b] = column sums of dout_b [C]
+    P[b, j] += sum_c W2[c, j] Q[b, c, j],  S[b, j] += sum_c W2[c, j] cs[b, c],
+    dW2[c, j] += sum_b (s[b, j] Q[b, c, j] + beta[j] cs[b, c]),  db2[c] += sum_b cs[b, c]"""
+    w = W2.float()
+    P += torch.einsum("cj,bcj->bj", w, Q)
+    S += cs @ w
+    dW2 += torch.einsum("bj,bcj->cj", s, Q) + cs.sum(0)[:, None] * beta[None, :]
+    db2 += cs.sum(0)
+
+
 def scale_rows_samples(x, scale, M, C, hw):
     idx = torch.arange(M, device=x.device) // hw
     return (x.float() * scale[idx][:, None]).to(x.dtype)

@@ -864,6 +864,17 @@ def test_voxel_shuffle_head(dt, pool):
 def test_head_tail_fwd_bwd(dt, geom):
     """`row-tiles*`: W2 is a multiple of 64, so the bf16 forward and backward pass 2 run the row-tiled MFMA kernels
     (csrc/head.hip, `head_rows` bits 0 / 1); fp32 stays on the thread-per-voxel kernels at every geometry."""
+    _check_head_tail(dt, geom)
+
+
+@pytest.mark.parametrize("geom", [(1, 3, 5, 2, 16, 1), (2, 2, 3, 3, 48, 3)], ids=["mid16", "mid48"])
+def test_head_tail_fwd_bwd_narrow_and_odd_widths(geom):
+    """The (Cmid, 4 * out_channels) = (16, 4) and (48, 12) instances of the thread-per-voxel kernels.  fp32 only: a bf16 row of
+    4 * out_channels values must be a whole number of 8-element vectors, which out_channels = 1 and 3 are not."""
+    _check_head_tail(torch.float32, geom)
+
+
+def _check_head_tail(dt, geom):
     H = _hip()
     B, H2, W2, Z, Cmid, Cout = geom
     Mh = B * H2 * W2
@@ -1003,9 +1014,10 @@ def test_prep_unprep_adamw():
 
 # ---------------------------------------------------------------- FCMAE masked pre-training pieces (csrc/mae.hip)
 @pytest.mark.parametrize("dt", DTYPES, ids=["f32", "bf16"])
-@pytest.mark.parametrize("C", [96, 40, 6, 3])
+@pytest.mark.parametrize("C", [96, 40, 12, 6, 3])
 def test_rows_select_gather_scatter_mask(dt, C):
-    """masked_patchify / masked_unpatchify / `x *= unmasked` as one row permutation; every vector width (16/8/4/2-byte rows)."""
+    """masked_patchify / masked_unpatchify / `x *= unmasked` as one row permutation; every vector width (16/8/4/2-byte rows;
+    C = 12 is the 8-byte width in bf16, C = 6 in fp32)."""
     H = _hip()
     n, k = 1000, 380
     g = torch.Generator().manual_seed(C)
@@ -1022,6 +1034,34 @@ def test_rows_select_gather_scatter_mask(dt, C):
     if (C * src.element_size()) % 4 == 0:
         add = rnd(k, C, dt=dt, seed=2)
         close(H.rows_select(src.to(DEV), kept.to(DEV), k, C, add=add.to(DEV)), R.rows_select(src, kept, k, C, add=add), dt, "gather+add")
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["f32", "bf16"])
+def test_grn_q_reduce_vs_statement(dt):
+    """GRN statistics and the fc2 weight / bias gradient from the per-sample products, with W2 in either dtype (the engine only
+    takes this path in bf16); 10 samples = one whole group of 8 and a partial one, all four outputs accumulate"""
+    H = _hip()
+    nb, C = 10, 8
+    N = 4 * C
+    Q, cs, W2 = rnd(nb, C, N, seed=1), rnd(nb, C, seed=2), rnd(C, N, dt=dt, seed=3, scale=0.3)
+    s, beta = 1.0 + 0.1 * rnd(nb, N, seed=4), 0.1 * rnd(N, seed=5)
+
+    def run(ops, dev):
+        outs = [torch.ones(nb, N, device=dev), torch.ones(nb, N, device=dev), torch.ones(C, N, device=dev), torch.ones(C, device=dev)]
+        ops.grn_q_reduce(*(t.to(dev) for t in (Q, cs, W2, s, beta)), *outs)
+        return outs
+
+    for name, a, b in zip(["P", "S", "dW2", "db2"], run(H, DEV), run(R, "cpu")):
+        close(a, b, dt, name)
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["f32", "bf16"])
+def test_scale_rows_samples(dt):
+    """per-sample scale of a [B * hw, C] activation (the drop-path mask of the fused block backward), several vectors per row"""
+    H = _hip()
+    B, hw, C = 3, 5, 24
+    x, scale = rnd(B * hw, C, dt=dt, seed=1), torch.tensor([0.0, 1.25, 2.0])
+    close(H.scale_rows_samples(x.to(DEV), scale.to(DEV), B * hw, C, hw), R.scale_rows_samples(x, scale, B * hw, C, hw), dt, "scale_rows_samples")
 
 
 @pytest.mark.parametrize("shape", [(2, 1, 5, 64, 96), (3, 2, 3, 32, 36), (1, 2, 1, 256, 256)])

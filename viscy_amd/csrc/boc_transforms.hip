@@ -180,10 +180,10 @@ extern "C" int32_t vsx_row_select(const float* x, float* out, void* ws, int64_t 
   hipLaunchKernelGGL(rs_init_kernel, dim3(gi), dim3(256), 0, s, w, slots, (long)rows, (int)nranks, rk);
   for (int p = 0; p < RS_PASSES; ++p) {
     const int shift = 32 - RS_BITS * (p + 1);
-    if (p == 0)
-      hipLaunchKernelGGL(rs_hist_kernel<true>, dim3((unsigned)(rows * gx)), dim3(256), 0, s, x, w, slots, (long)n, (int)nranks, (int)gx, shift);
-    else
-      hipLaunchKernelGGL(rs_hist_kernel<false>, dim3((unsigned)(rows * gx)), dim3(256), 0, s, x, w, slots, (long)n, (int)nranks, (int)gx, shift);
+    vsx_by_bool(p == 0, [&](auto first) {
+      hipLaunchKernelGGL(rs_hist_kernel<decltype(first)::value>, dim3((unsigned)(rows * gx)), dim3(256), 0, s, x, w, slots, (long)n, (int)nranks,
+                         (int)gx, shift);
+    });
     hipLaunchKernelGGL(rs_scan_kernel, dim3((unsigned)slots), dim3(256), 0, s, w, out, slots, (int)nranks, (int)(p == RS_PASSES - 1));
   }
   VSX_LAUNCH_CHECK();
@@ -268,10 +268,10 @@ extern "C" int32_t vsx_percentile_scale(const float* x, float* y, const float* a
   const bool vec = (((uintptr_t)x | (uintptr_t)y) & 15u) == 0;
   int g = vsx_cdiv(vec ? (total + 3) / 4 : total, 256L * 4);
   g = g > 8192 ? 8192 : (g < 1 ? 1 : g);
-  if (vec)
-    hipLaunchKernelGGL(percentile_scale_kernel<true>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, y, a_min, a_max, degenerate, (long)n, total, a);
-  else
-    hipLaunchKernelGGL(percentile_scale_kernel<false>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, y, a_min, a_max, degenerate, (long)n, total, a);
+  vsx_by_bool(vec, [&](auto vec_) {
+    hipLaunchKernelGGL(percentile_scale_kernel<decltype(vec_)::value>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, y, a_min, a_max, degenerate,
+                       (long)n, total, a);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

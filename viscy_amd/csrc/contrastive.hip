@@ -30,10 +30,10 @@ extern "C" int32_t vsx_avgpool_rows_fwd(const void* x, float* out, int32_t B, in
                                         vsx_stream_t stream) {
   VSX_CHECK(x && out && B > 0 && hw > 0 && C > 0 && B <= 65535, "vsx_avgpool_rows_fwd: bad arguments");
   dim3 g(vsx_cdiv(C, 256), B);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(avgpool_rows_fwd_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, out, hw, C);
-  else
-    hipLaunchKernelGGL(avgpool_rows_fwd_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)x, out, hw, C);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(avgpool_rows_fwd_kernel<T>, g, dim3(256), 0, (hipStream_t)stream, (const T*)x, out, hw, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -41,10 +41,10 @@ extern "C" int32_t vsx_avgpool_rows_bwd(const float* dout, void* dx, int32_t B, 
                                         vsx_stream_t stream) {
   VSX_CHECK(dout && dx && B > 0 && hw > 0 && C > 0 && B <= 65535, "vsx_avgpool_rows_bwd: bad arguments");
   dim3 g(vsx_cdiv(C, 256), B);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(avgpool_rows_bwd_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, dout, (bf16_t*)dx, hw, C);
-  else
-    hipLaunchKernelGGL(avgpool_rows_bwd_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, dout, (float*)dx, hw, C);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(avgpool_rows_bwd_kernel<T>, g, dim3(256), 0, (hipStream_t)stream, dout, (T*)dx, hw, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

@@ -593,12 +593,10 @@ extern "C" int32_t vsx_conv3d_prep_weight(const float* w, void* out, int32_t N, 
                                           int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(w && out && N > 0 && Kc > 0, "vsx_conv3d_prep_weight: bad arguments");
   const long n = (long)N * 27 * Kc;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(conv3d_prep_weight_kernel<bf16_t>, dim3(c3_grid(n)), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)out, N,
-                       Kc, sn, sc, flip);
-  else
-    hipLaunchKernelGGL(conv3d_prep_weight_kernel<float>, dim3(c3_grid(n)), dim3(256), 0, (hipStream_t)stream, w, (float*)out, N,
-                       Kc, sn, sc, flip);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(conv3d_prep_weight_kernel<T>, dim3(c3_grid(n)), dim3(256), 0, (hipStream_t)stream, w, (T*)out, N, Kc, sn, sc, flip);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -634,20 +632,17 @@ extern "C" int32_t vsx_conv3d_fwd(const void* a, int32_t lda, int32_t acoff, con
   p.tiles_m = (int)((Mq + C3_BM - 1) / C3_BM);
   dim3 grid(p.tiles_m, (Cout + C3_BN - 1) / C3_BN, transposed ? 8 : 1);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSX_BF16) {
-    const bool vec = Cin % 8 == 0 && lda % 8 == 0 && acoff % 8 == 0 && c3_al(a, 8, 2) && c3_al(wp, 8, 2);
-    if (out_f32) {
-      if (vec) hipLaunchKernelGGL((conv3d_igemm_kernel<bf16_t, float, true>), grid, dim3(C3_THREADS), 0, s, p);
-      else hipLaunchKernelGGL((conv3d_igemm_kernel<bf16_t, float, false>), grid, dim3(C3_THREADS), 0, s, p);
-    } else {
-      if (vec) hipLaunchKernelGGL((conv3d_igemm_kernel<bf16_t, bf16_t, true>), grid, dim3(C3_THREADS), 0, s, p);
-      else hipLaunchKernelGGL((conv3d_igemm_kernel<bf16_t, bf16_t, false>), grid, dim3(C3_THREADS), 0, s, p);
-    }
-  } else {
-    const bool vec = Cin % 4 == 0 && lda % 4 == 0 && acoff % 4 == 0 && c3_al(a, 4, 4) && c3_al(wp, 4, 4);
-    if (vec) hipLaunchKernelGGL((conv3d_igemm_kernel<float, float, true>), grid, dim3(C3_THREADS), 0, s, p);
-    else hipLaunchKernelGGL((conv3d_igemm_kernel<float, float, false>), grid, dim3(C3_THREADS), 0, s, p);
-  }
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int VN = VT<T>::N, ES = sizeof(T);
+    const bool vec = Cin % VN == 0 && lda % VN == 0 && acoff % VN == 0 && c3_al(a, VN, ES) && c3_al(wp, VN, ES);
+    vsx_by_bool(out_f32, [&](auto f32_out) {
+      using TO = std::conditional_t<decltype(f32_out)::value, float, T>;  // fp32 input writes fp32 either way
+      vsx_by_bool(vec, [&](auto vec_) {
+        hipLaunchKernelGGL((conv3d_igemm_kernel<T, TO, decltype(vec_)::value>), grid, dim3(C3_THREADS), 0, s, p);
+      });
+    });
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -677,10 +672,10 @@ extern "C" int32_t vsx_conv3d_wgrad(const void* P, int32_t ldp, int32_t pcoff, c
   const int gs = (int)((V + p.vox_per_split - 1) / p.vox_per_split);  // splits that own voxels (<= splits)
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((27 * C + C3_BN - 1) / C3_BN, (R + C3_BM - 1) / C3_BM, gs);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(conv3d_wgrad_kernel<bf16_t>, grid, dim3(C3_THREADS), 0, s, p);
-  else
-    hipLaunchKernelGGL(conv3d_wgrad_kernel<float>, grid, dim3(C3_THREADS), 0, s, p);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(conv3d_wgrad_kernel<T>, grid, dim3(C3_THREADS), 0, s, p);
+  });
   VSX_LAUNCH_CHECK();
   const long n = (long)R * C * 27;
   hipLaunchKernelGGL(conv3d_wgrad_fold_kernel, dim3(c3_grid(n)), dim3(256), 0, s, ws, out, R, C, gs);
@@ -703,12 +698,11 @@ extern "C" int32_t vsx_conv3d_colsum(const void* x, int32_t ldx, int32_t xcoff, 
   const int ct = c3_ct(C);
   VSX_CHECK((long)(C3_RED_THREADS / ct) * C <= 2048, "vsx_conv3d_colsum: C=%d not served", C);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL((conv3d_colsum_kernel<bf16_t, 0>), dim3(G), dim3(C3_RED_THREADS), 0, s, (const bf16_t*)x, ldx, xcoff,
-                       (const bf16_t*)nullptr, (const float*)nullptr, ws, M, C, rpg, ct);
-  else
-    hipLaunchKernelGGL((conv3d_colsum_kernel<float, 0>), dim3(G), dim3(C3_RED_THREADS), 0, s, (const float*)x, ldx, xcoff,
-                       (const float*)nullptr, (const float*)nullptr, ws, M, C, rpg, ct);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((conv3d_colsum_kernel<T, 0>), dim3(G), dim3(C3_RED_THREADS), 0, s, (const T*)x, ldx, xcoff, (const T*)nullptr,
+                       (const float*)nullptr, ws, M, C, rpg, ct);
+  });
   VSX_LAUNCH_CHECK();
   hipLaunchKernelGGL(conv3d_colsum_fold_kernel, dim3(C), dim3(C3_RED_THREADS), 0, s, ws, out, (int)G, C);
   VSX_LAUNCH_CHECK();
@@ -729,12 +723,10 @@ extern "C" int32_t vsx_bn3d_apply_relu(const void* z, const float* ss, void* dst
                                        int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(z && ss && dst && M > 0 && C > 0 && ldd >= dcoff + C, "vsx_bn3d_apply_relu: bad arguments");
   const int g = c3_grid(M * C);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(bn3d_apply_relu_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)z, ss, (bf16_t*)dst,
-                       ldd, dcoff, M, C);
-  else
-    hipLaunchKernelGGL(bn3d_apply_relu_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)z, ss, (float*)dst,
-                       ldd, dcoff, M, C);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(bn3d_apply_relu_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)z, ss, (T*)dst, ldd, dcoff, M, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -752,21 +744,19 @@ extern "C" int32_t vsx_bn3d_bwd(const void* dy, int32_t ldy, int32_t ycoff, cons
   float* coef = ws + G * 2 * C;
   hipStream_t s = (hipStream_t)stream;
   const int g = c3_grid(M * C);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL((conv3d_colsum_kernel<bf16_t, 1>), dim3(G), dim3(C3_RED_THREADS), 0, s, (const bf16_t*)dy, ldy, ycoff,
-                       (const bf16_t*)z, ss, ws, M, C, rpg, ct);
-  else
-    hipLaunchKernelGGL((conv3d_colsum_kernel<float, 1>), dim3(G), dim3(C3_RED_THREADS), 0, s, (const float*)dy, ldy, ycoff,
-                       (const float*)z, ss, ws, M, C, rpg, ct);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((conv3d_colsum_kernel<T, 1>), dim3(G), dim3(C3_RED_THREADS), 0, s, (const T*)dy, ldy, ycoff, (const T*)z, ss, ws,
+                       M, C, rpg, ct);
+  });
   VSX_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn3d_bwd_finalize_kernel, dim3(C), dim3(C3_RED_THREADS), 0, s, ws, (int)G, M, C, dgamma, dbeta, coef, training);
   VSX_LAUNCH_CHECK();
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(bn3d_bwd_apply_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)dy, ldy, ycoff, (const bf16_t*)z, ss,
-                       gamma, coef, (bf16_t*)dz, M, C);
-  else
-    hipLaunchKernelGGL(bn3d_bwd_apply_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)dy, ldy, ycoff, (const float*)z, ss,
-                       gamma, coef, (float*)dz, M, C);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(bn3d_bwd_apply_kernel<T>, dim3(g), dim3(256), 0, s, (const T*)dy, ldy, ycoff, (const T*)z, ss, gamma, coef,
+                       (T*)dz, M, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -774,10 +764,10 @@ extern "C" int32_t vsx_bn3d_bwd(const void* dy, int32_t ldy, int32_t ycoff, cons
 extern "C" int32_t vsx_conv3d_to_cl(const float* x, void* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(x && out && B > 0 && C > 0 && S > 0, "vsx_conv3d_to_cl: bad arguments");
   const int g = c3_grid((long)B * C * S);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(conv3d_to_cl_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)out, B, C, S);
-  else
-    hipLaunchKernelGGL(conv3d_to_cl_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, (float*)out, B, C, S);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(conv3d_to_cl_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, (T*)out, B, C, S);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -785,10 +775,10 @@ extern "C" int32_t vsx_conv3d_to_cl(const float* x, void* out, int32_t B, int32_
 extern "C" int32_t vsx_conv3d_from_cl(const void* y, float* out, int32_t B, int32_t C, int64_t S, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(y && out && B > 0 && C > 0 && S > 0, "vsx_conv3d_from_cl: bad arguments");
   const int g = c3_grid((long)B * C * S);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(conv3d_from_cl_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, out, B, C, S);
-  else
-    hipLaunchKernelGGL(conv3d_from_cl_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)y, out, B, C, S);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(conv3d_from_cl_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)y, out, B, C, S);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

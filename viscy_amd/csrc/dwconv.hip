@@ -288,12 +288,10 @@ static int dw_launch_cfg(const void* x, const float* w, const float* bias, const
   constexpr int CB = NCV * VT<T>::N;
   long blocks = (long)B * vsx_cdiv(H, TH) * vsx_cdiv(W, TW) * vsx_cdiv(C, CB);
   dim3 grid((unsigned)blocks);
-  if (flip)
-    hipLaunchKernelGGL((dwconv7_kernel<T, NCV, TH, TW, K, true>), grid, dim3(256), 0, s, (const T*)x, w, bias,
+  vsx_by_bool(flip, [&](auto flip_) {
+    hipLaunchKernelGGL((dwconv7_kernel<T, NCV, TH, TW, K, decltype(flip_)::value>), grid, dim3(256), 0, s, (const T*)x, w, bias,
                        (const T*)add, (T*)y, B, H, W, C);
-  else
-    hipLaunchKernelGGL((dwconv7_kernel<T, NCV, TH, TW, K, false>), grid, dim3(256), 0, s, (const T*)x, w, bias,
-                       (const T*)add, (T*)y, B, H, W, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -328,18 +326,22 @@ int dw_launch<float>(const void* x, const float* w, const float* bias, const voi
  * tap-major fp32 copy [49][C] of conv_dw.weight[C,1,7,7]; y = conv(x) + bias [+ add]. */
 extern "C" int32_t vsx_dwconv7_fwd(const void* x, const float* w, const float* bias, const void* add, void* y, int32_t B,
                                    int32_t H, int32_t W, int32_t C, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(x && w && y && B > 0 && H > 0 && W > 0 && C > 0 && C % vn == 0, "vsx_dwconv7_fwd: bad arguments (C=%d)", C);
-  return dtype == VSX_BF16 ? dw_launch<bf16_t>(x, w, bias, add, y, B, H, W, C, false, (hipStream_t)stream)
-                           : dw_launch<float>(x, w, bias, add, y, B, H, W, C, false, (hipStream_t)stream);
+  return vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return dw_launch<T>(x, w, bias, add, y, B, H, W, C, false, (hipStream_t)stream);
+  });
 }
 /* data gradient: dx = conv(dy, flipped w) [+ add]  (add = the residual-branch gradient) */
 extern "C" int32_t vsx_dwconv7_bwd_data(const void* dy, const float* w, const void* add, void* dx, int32_t B, int32_t H,
                                         int32_t W, int32_t C, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dy && w && dx && B > 0 && H > 0 && W > 0 && C > 0 && C % vn == 0, "vsx_dwconv7_bwd_data: bad arguments");
-  return dtype == VSX_BF16 ? dw_launch<bf16_t>(dy, w, nullptr, add, dx, B, H, W, C, true, (hipStream_t)stream)
-                           : dw_launch<float>(dy, w, nullptr, add, dx, B, H, W, C, true, (hipStream_t)stream);
+  return vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return dw_launch<T>(dy, w, nullptr, add, dx, B, H, W, C, true, (hipStream_t)stream);
+  });
 }
 template <typename T, int NCV, int TH, int TW>
 static int dw_wgrad_cfg(const void* dy, const void* x, float* dw, float* db, float* ws, int ws_rows, int B, int H, int W,
@@ -364,7 +366,7 @@ static int dw_wgrad_cfg(const void* dy, const void* x, float* dw, float* db, flo
 extern "C" int32_t vsx_dwconv7_bwd_weight(const void* dy, const void* x, float* dw, float* db, float* ws, int32_t ws_rows,
                                           int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                                           vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dy && x && dw && ws && ws_rows > 0 && B > 0 && H > 0 && W > 0 && C > 0 && C % vn == 0,
             "vsx_dwconv7_bwd_weight: bad arguments");
   hipStream_t st = (hipStream_t)stream;

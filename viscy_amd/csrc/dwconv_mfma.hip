@@ -744,20 +744,19 @@ int vsx_dwconv7_mfma_try(const void* x, const float* w, const float* bias, const
   int grid = chunks * nslab;
   // keep the XCD remap valid: pad the grid to a multiple of 8 (surplus workgroups exit at once)
   grid = (grid + 7) & ~7;
-#define DWM_LAUNCH(NXT, FLIP)                                                                                          \
-  hipLaunchKernelGGL((dwconv7_mfma_kernel<NXT, FLIP>), dim3(grid), dim3(DWM_THREADS), 0, s, (const bf16_t*)x, w, bias,  \
-                     (const bf16_t*)add, (bf16_t*)y, B, H, W, C, nslab, tiles, per)
-#define DWD_LAUNCH(FLIP, CBV)                                                                                         \
-  hipLaunchKernelGGL((dwconv7_mfma_dma_kernel<FLIP, CBV>), dim3(grid), dim3(CBV * 32), 0, s, (const bf16_t*)x, w, bias,  \
-                     (const bf16_t*)add, (bf16_t*)y, B, H, W, C, nslab, tiles, per)
-  if (dma) {
-    if (flip) DWD_LAUNCH(true, 32); else DWD_LAUNCH(false, 32);
-  } else if (nxt == 2) {
-    if (flip) DWM_LAUNCH(2, true); else DWM_LAUNCH(2, false);
-  } else {
-    if (flip) DWM_LAUNCH(1, true); else DWM_LAUNCH(1, false);
-  }
-#undef DWM_LAUNCH
+  constexpr int CBV = 32;  // channels per workgroup of the DMA kernel
+  if (dma)
+    vsx_by_bool(flip, [&](auto flip_) {
+      hipLaunchKernelGGL((dwconv7_mfma_dma_kernel<decltype(flip_)::value, CBV>), dim3(grid), dim3(CBV * 32), 0, s, (const bf16_t*)x, w, bias,
+                         (const bf16_t*)add, (bf16_t*)y, B, H, W, C, nslab, tiles, per);
+    });
+  else
+    vsx_by_int<2, 1>(nxt, [&](auto nxt_) {
+      vsx_by_bool(flip, [&](auto flip_) {
+        hipLaunchKernelGGL((dwconv7_mfma_kernel<decltype(nxt_)::value, decltype(flip_)::value>), dim3(grid), dim3(DWM_THREADS), 0, s,
+                           (const bf16_t*)x, w, bias, (const bf16_t*)add, (bf16_t*)y, B, H, W, C, nslab, tiles, per);
+      });
+    });
   VSX_LAUNCH_CHECK();
   *taken = 1;
   return 0;

@@ -847,7 +847,7 @@ static bool nt_fast_ok(const VsxGemm* p, int es) {
 }
 
 static int check_common(const VsxGemm* p, int dtype, const char* who) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(p != nullptr, "%s: null params", who);
   VSX_CHECK(dtype == VSX_F32 || dtype == VSX_BF16, "%s: bad dtype %d", who, dtype);
   VSX_CHECK(p->M > 0 && p->N > 0 && p->K > 0, "%s: empty GEMM %dx%dx%d", who, p->M, p->N, p->K);
@@ -869,7 +869,7 @@ static int check_common(const VsxGemm* p, int dtype, const char* who) {
 
 static int plan_nt(const VsxGemm* p, int dtype, VsxGemmPlan& pl) {
   if (int e = check_common(p, dtype, "vsx_gemm_nt")) return e;
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(p->ldc % vn == 0, "vsx_gemm_nt: ldc=%d must be a multiple of %d", p->ldc, vn);
   if (p->c_mode == VSX_A_PATCH2)
     VSX_CHECK(p->c_cs > 0 && p->c_cs % vn == 0 && p->N % p->c_cs == 0 && p->gh > 0 && p->gw > 0,

@@ -829,16 +829,15 @@ static bool head_rows_ok(const HeadDims& d, int dtype, int bit) {
          4 * d.Cmid * 4 + 64 * d.Z * (d.Cmid * 2 + 16 + 16 * d.Cout) + 16 <= 65536;  // static LDS limit of a plain launch
 }
 
-#define HEAD_DISPATCH(KERNEL, TT, ...)                                                                         \
-  do {                                                                                                          \
-    if (Cmid == 16 && Cout == 1) hipLaunchKernelGGL((KERNEL<TT, 16, 4>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-    else if (Cmid == 32 && Cout == 2) hipLaunchKernelGGL((KERNEL<TT, 32, 8>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-    else if (Cmid == 48 && Cout == 3) hipLaunchKernelGGL((KERNEL<TT, 48, 12>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<TT, 64, 16>), grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);         \
-  } while (0)
+// dtype x (Cmid, 4 * Cout) in (16,4) (32,8) (48,12) (64,16), the last for every other width: f(vsx_type<T>, integral_constant<int, Cmid>).
+// head_check has run, so Cout == Cmid / 16 and Cmid alone picks the pair
+template <class F>
+static __forceinline__ void head_dispatch(int dtype, int Cmid, F&& f) {
+  vsx_by_dtype(dtype, [&](auto tag) { vsx_by_int<16, 32, 48, 64>(Cmid, [&](auto cm) { f(tag, cm); }); });
+}
 
 static int head_check(const char* who, HeadDims d, int dtype) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(d.B > 0 && d.H2 > 0 && d.W2 > 0 && d.Z > 0, "%s: bad dims", who);
   VSX_CHECK(d.Cmid > 0 && d.Cmid <= HEAD_MAX_CMID && d.Cmid % vn == 0, "%s: Cmid=%d must be <=%d and a multiple of %d", who,
             d.Cmid, HEAD_MAX_CMID, vn);
@@ -872,12 +871,12 @@ extern "C" int32_t vsx_head_out_fwd(const void* U, const float* ssum, const floa
     return 0;
   }
   dim3 grid(vsx_cdiv((long)H2 * W2 * Z, 256), B);
-  if (dtype == VSX_BF16)
-    HEAD_DISPATCH(head_out_fwd_kernel, bf16_t, (const bf16_t*)U, ssum, ssq,
-                       w2, b2, alpha, out, d, eps);
-  else
-    HEAD_DISPATCH(head_out_fwd_kernel, float, (const float*)U, ssum, ssq,
-                       w2, b2, alpha, out, d, eps);
+  head_dispatch(dtype, Cmid, [&](auto tag, auto cm) {
+    using T = typename decltype(tag)::type;
+    constexpr int CM = decltype(cm)::value;
+    hipLaunchKernelGGL((head_out_fwd_kernel<T, CM, CM / 4>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)U, ssum, ssq, w2, b2,
+                       alpha, out, d, eps);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -893,12 +892,12 @@ extern "C" int32_t vsx_head_out_bwd1(const void* U, const float* ssum, const flo
   int vpt = vsx_cdiv(nvox, 256L * 512);
   if (vpt < 1) vpt = 1;
   dim3 grid(vsx_cdiv(nvox, 256L * vpt), B);
-  if (dtype == VSX_BF16)
-    HEAD_DISPATCH(head_out_bwd1_kernel, bf16_t, (const bf16_t*)U, ssum, ssq,
-                       w2, alpha, dout, (bf16_t*)act, (bf16_t*)dv, S1, S2, dalpha, d, eps, vpt);
-  else
-    HEAD_DISPATCH(head_out_bwd1_kernel, float, (const float*)U, ssum, ssq,
-                       w2, alpha, dout, (float*)act, (float*)dv, S1, S2, dalpha, d, eps, vpt);
+  head_dispatch(dtype, Cmid, [&](auto tag, auto cm) {
+    using T = typename decltype(tag)::type;
+    constexpr int CM = decltype(cm)::value;
+    hipLaunchKernelGGL((head_out_bwd1_kernel<T, CM, CM / 4>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)U, ssum, ssq, w2, alpha,
+                       dout, (T*)act, (T*)dv, S1, S2, dalpha, d, eps, vpt);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -975,12 +974,12 @@ extern "C" int32_t vsx_head_out_bwd2(const void* U, const float* ssum, const flo
     return 0;
   }
   dim3 grid(vsx_cdiv((long)H2 * W2 * Z, 256), B);
-  if (dtype == VSX_BF16)
-    HEAD_DISPATCH(head_out_bwd2_kernel, bf16_t, (const bf16_t*)U, ssum, ssq,
-                       w2, alpha, (const bf16_t*)dv, S1, S2, (bf16_t*)dU, d, eps);
-  else
-    HEAD_DISPATCH(head_out_bwd2_kernel, float, (const float*)U, ssum, ssq,
-                       w2, alpha, (const float*)dv, S1, S2, (float*)dU, d, eps);
+  head_dispatch(dtype, Cmid, [&](auto tag, auto cm) {
+    using T = typename decltype(tag)::type;
+    constexpr int CM = decltype(cm)::value;
+    hipLaunchKernelGGL((head_out_bwd2_kernel<T, CM, CM / 4>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)U, ssum, ssq, w2, alpha,
+                       (const T*)dv, S1, S2, (T*)dU, d, eps);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

@@ -792,11 +792,10 @@ extern "C" int32_t vsx_ssim_scale_fwd_fused(const float* P, const float* T, cons
   VSX_CHECK((long)42 * W < (1l << 31), "vsx_ssim_scale_fwd_fused: row length");
   dim3 grid(vsx_cdiv(W - 10, ST), vsx_cdiv(H - 10, ST), B * C);
   const bool vec = (W & 1) == 0 && ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(T)) & 7) == 0;
-#define VSX_FUSED_LAUNCH(VEC_)                                                                                           \
-  hipLaunchKernelGGL((ssim_tile_fused_kernel<VEC_>), grid, dim3(FT), 0, (hipStream_t)stream, P, T, tmax, C, D, H, W,   \
-                     sum_ssim, sum_cs, dmu, last ? 1 : 0, Po, To, tmax_next, l1sum, l2sum)
-  if (vec) VSX_FUSED_LAUNCH(true); else VSX_FUSED_LAUNCH(false);
-#undef VSX_FUSED_LAUNCH
+  vsx_by_bool(vec, [&](auto vec_) {
+    hipLaunchKernelGGL((ssim_tile_fused_kernel<decltype(vec_)::value>), grid, dim3(FT), 0, (hipStream_t)stream, P, T, tmax, C, D, H, W,
+                       sum_ssim, sum_cs, dmu, last ? 1 : 0, Po, To, tmax_next, l1sum, l2sum);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

@@ -72,21 +72,14 @@ static int32_t rows_select_launch(const void* src, const int* map, const void* a
                                   hipStream_t stream) {
   const int rb = C * (int)sizeof(T);
   const long cap = 256L * 64 * 8;  // grid-stride beyond 8 waves' worth of blocks per CU
-#define VSX_RS(VB)                                                                                                  \
-  {                                                                                                                 \
-    const int vpr = rb / VB;                                                                                        \
-    long nb = (n_out * vpr + 255) / 256;                                                                            \
-    if (nb > cap) nb = cap;                                                                                         \
-    hipLaunchKernelGGL((rows_select_kernel<T, VB>), dim3((unsigned)nb), dim3(256), 0, stream, src, map, add, dst, n_out, vpr); \
-  }
-  if (rb % 16 == 0) VSX_RS(16)
-  else if (rb % 8 == 0) VSX_RS(8)
-  else if (rb % 4 == 0) VSX_RS(4)
-  else {
-    VSX_CHECK(add == nullptr, "vsx_rows_select: the fused add needs rows that are a multiple of 4 bytes (C=%d)", C);
-    VSX_RS(2)
-  }
-#undef VSX_RS
+  const int vb = rb % 16 == 0 ? 16 : rb % 8 == 0 ? 8 : rb % 4 == 0 ? 4 : 2;  // bytes per access: the widest that divides a row
+  VSX_CHECK(vb >= 4 || add == nullptr, "vsx_rows_select: the fused add needs rows that are a multiple of 4 bytes (C=%d)", C);
+  const int vpr = rb / vb;
+  long nb = (n_out * vpr + 255) / 256;
+  if (nb > cap) nb = cap;
+  vsx_by_int<16, 8, 4, 2>(vb, [&](auto vb_) {
+    hipLaunchKernelGGL((rows_select_kernel<T, decltype(vb_)::value>), dim3((unsigned)nb), dim3(256), 0, stream, src, map, add, dst, n_out, vpr);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -95,8 +88,10 @@ extern "C" int32_t vsx_rows_select(const void* src, const int32_t* map, const vo
                                    int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(src && map && dst && n_out > 0 && C > 0, "vsx_rows_select: bad arguments");
   VSX_CHECK(src != dst, "vsx_rows_select: in-place permutation is not supported");
-  if (dtype == VSX_BF16) return rows_select_launch<bf16_t>(src, map, add, dst, n_out, C, (hipStream_t)stream);
-  return rows_select_launch<float>(src, map, add, dst, n_out, C, (hipStream_t)stream);
+  return vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return rows_select_launch<T>(src, map, add, dst, n_out, C, (hipStream_t)stream);
+  });
 }
 
 // ------------------------------------------------------------------ MaskedMSELoss (engine.py:104-125)
@@ -213,17 +208,16 @@ __global__ __launch_bounds__(256) void scale_rows_samples_kernel(const T* __rest
 
 extern "C" int32_t vsx_scale_rows_samples(const void* x, const float* scale, void* out, int64_t M, int32_t C, int32_t hw,
                                           int32_t dtype, vsx_stream_t stream) {
-  const int vn = dtype == VSX_BF16 ? 8 : 4;
+  const int vn = vsx_vec_elems(dtype);
   VSX_CHECK(x && scale && out && M > 0 && C > 0 && hw > 0 && C % vn == 0, "vsx_scale_rows_samples: bad arguments (C=%d)", C);
   const long total = (long)M * (C / vn);
   long nb = (total + 255) / 256;
   if (nb > 256L * 64) nb = 256L * 64;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(scale_rows_samples_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, scale,
-                       (bf16_t*)out, (long)M, C / vn, hw);
-  else
-    hipLaunchKernelGGL(scale_rows_samples_kernel<float>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const float*)x, scale,
-                       (float*)out, (long)M, C / vn, hw);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(scale_rows_samples_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const T*)x, scale, (T*)out,
+                       (long)M, C / vn, hw);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

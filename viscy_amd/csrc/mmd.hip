@@ -316,13 +316,12 @@ extern "C" int32_t vsx_mmd_sums(const float* xc, const float* norms, const uint8
   const bool vecz = N % 16 == 0 && vsx_al16(labels);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)tiles, (unsigned)splits), block(FT_THREADS);
-#define MM_GO(VEC, VECZ) hipLaunchKernelGGL((mmd_sums_kernel<VEC, VECZ>), grid, block, 0, s, xc, norms, labels, N, d, P, two_bw, tps, (double*)ws)
-  if (vec) {
-    if (vecz) MM_GO(true, true); else MM_GO(true, false);
-  } else {
-    if (vecz) MM_GO(false, true); else MM_GO(false, false);
-  }
-#undef MM_GO
+  vsx_by_bool(vec, [&](auto vec_) {
+    vsx_by_bool(vecz, [&](auto vecz_) {
+      hipLaunchKernelGGL((mmd_sums_kernel<decltype(vec_)::value, decltype(vecz_)::value>), grid, block, 0, s, xc, norms, labels, N, d, P, two_bw,
+                         tps, (double*)ws);
+    });
+  });
   hipLaunchKernelGGL(mmd_fold_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const double*)ws, tiles * splits, P, sums);
   VSX_LAUNCH_CHECK();
   return 0;
@@ -340,10 +339,9 @@ extern "C" int32_t vsx_rbf_block(const float* xc, const float* norms, int32_t N,
   const dim3 grid((unsigned)((c1 - c0 + FT_T - 1) / FT_T), (unsigned)((r1 - r0 + FT_T - 1) / FT_T)), block(FT_THREADS);
   VSX_CHECK(grid.y <= 65535u, "vsx_rbf_block: at most %d rows per call (got %ld)", 65535 * FT_T, (long)(r1 - r0));
   hipStream_t s = (hipStream_t)stream;
-  if (ft_vec_ok(xc, d))
-    hipLaunchKernelGGL(mmd_rbf_block_kernel<true>, grid, block, 0, s, xc, norms, d, r0, r1, c0, c1, two_bw, zero_diag, out);
-  else
-    hipLaunchKernelGGL(mmd_rbf_block_kernel<false>, grid, block, 0, s, xc, norms, d, r0, r1, c0, c1, two_bw, zero_diag, out);
+  vsx_by_bool(ft_vec_ok(xc, d), [&](auto vec) {
+    hipLaunchKernelGGL(mmd_rbf_block_kernel<decltype(vec)::value>, grid, block, 0, s, xc, norms, d, r0, r1, c0, c1, two_bw, zero_diag, out);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -356,10 +354,9 @@ extern "C" int32_t vsx_sqdist_upper(const float* xc, const float* norms, int32_t
   const unsigned nt = (unsigned)((M + FT_T - 1) / FT_T);
   const dim3 grid(nt, nt), block(FT_THREADS);
   hipStream_t s = (hipStream_t)stream;
-  if (ft_vec_ok(xc, d))
-    hipLaunchKernelGGL(mmd_sqdist_upper_kernel<true>, grid, block, 0, s, xc, norms, M, d, out);
-  else
-    hipLaunchKernelGGL(mmd_sqdist_upper_kernel<false>, grid, block, 0, s, xc, norms, M, d, out);
+  vsx_by_bool(ft_vec_ok(xc, d), [&](auto vec) {
+    hipLaunchKernelGGL(mmd_sqdist_upper_kernel<decltype(vec)::value>, grid, block, 0, s, xc, norms, M, d, out);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

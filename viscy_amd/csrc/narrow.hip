@@ -745,7 +745,7 @@ extern "C" int64_t vsx_narrow_ws_floats(int32_t op, int32_t B, int64_t n, int32_
 extern "C" int32_t vsx_narrow_stem_fwd(const float* x, const float* W, const float* bias, void* out, int32_t B, int32_t Cin, int32_t Z,
                                        int32_t H, int32_t Wd, int32_t kz, int32_t ky, int32_t kx, int32_t C0, int32_t dtype,
                                        vsx_stream_t stream) {
-  const int K = Cin * kz * ky * kx, vn = dtype == VSX_BF16 ? 8 : 4;
+  const int K = Cin * kz * ky * kx, vn = vsx_vec_elems(dtype);
   VSX_CHECK(x && W && bias && out && B > 0 && Cin > 0 && kz > 0 && ky > 0 && kx > 0 && Z == kz && H % ky == 0 && Wd % kx == 0,
             "vsx_narrow_stem_fwd: bad arguments (Z=%d must equal kz=%d, H=%d / W=%d multiples of the kernel)", Z, kz, H, Wd);
   VSX_CHECK(C0 > 0 && C0 % vn == 0 && K * C0 + C0 <= 16384 && al16(out), "vsx_narrow_stem_fwd: C0=%d K=%d not served", C0, K);
@@ -753,12 +753,10 @@ extern "C" int32_t vsx_narrow_stem_fwd(const float* x, const float* W, const flo
   int g = vsx_cdiv(total, NB);
   if (g > 65536) g = 65536;
   const size_t lds = (size_t)(K * C0 + C0) * sizeof(float);
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(narrow_stem_fwd_kernel<bf16_t>, dim3(g), dim3(NB), lds, (hipStream_t)stream, x, W, bias, (bf16_t*)out, B, Cin, kz,
-                       H, Wd, ky, kx, C0);
-  else
-    hipLaunchKernelGGL(narrow_stem_fwd_kernel<float>, dim3(g), dim3(NB), lds, (hipStream_t)stream, x, W, bias, (float*)out, B, Cin, kz, H,
-                       Wd, ky, kx, C0);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(narrow_stem_fwd_kernel<T>, dim3(g), dim3(NB), lds, (hipStream_t)stream, x, W, bias, (T*)out, B, Cin, kz, H, Wd, ky, kx, C0);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -776,29 +774,20 @@ extern "C" int32_t vsx_narrow_stem_wgrad(const float* x, const void* df, float* 
   const int NE = C0 * K + C0;
   VSX_CHECK(ws_floats >= (int64_t)G * NE, "vsx_narrow_stem_wgrad: workspace needs %ld floats", (long)G * NE);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(narrow_stem_wgrad_kernel<bf16_t>, dim3(G), dim3(NB), 0, st, x, (const bf16_t*)df, ws, B, Cin, kz, H, Wd, ky, kx, C0,
-                       rpw);
-  else
-    hipLaunchKernelGGL(narrow_stem_wgrad_kernel<float>, dim3(G), dim3(NB), 0, st, x, (const float*)df, ws, B, Cin, kz, H, Wd, ky, kx, C0,
-                       rpw);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(narrow_stem_wgrad_kernel<T>, dim3(G), dim3(NB), 0, st, x, (const T*)df, ws, B, Cin, kz, H, Wd, ky, kx, C0, rpw);
+  });
   VSX_LAUNCH_CHECK();
   if (vsx_det_group_sum(ws, NE, 0, dW, 1, G, C0 * K, st)) return 2;
   return vsx_det_group_sum(ws, NE, C0 * K, db, 1, G, C0, st) ? 2 : 0;
 }
 
-#define NARROW_DISPATCH(KERNEL, GRID, ...)                                                                        \
-  do {                                                                                                            \
-    if (dtype == VSX_BF16) {                                                                                      \
-      typedef bf16_t T_;                                                                                          \
-      if (C == 4) hipLaunchKernelGGL((KERNEL<T_, 4>), GRID, dim3(NB), 0, st, __VA_ARGS__);                      \
-      else hipLaunchKernelGGL((KERNEL<T_, 8>), GRID, dim3(NB), 0, st, __VA_ARGS__);                             \
-    } else {                                                                                                      \
-      typedef float T_;                                                                                           \
-      if (C == 4) hipLaunchKernelGGL((KERNEL<T_, 4>), GRID, dim3(NB), 0, st, __VA_ARGS__);                      \
-      else hipLaunchKernelGGL((KERNEL<T_, 8>), GRID, dim3(NB), 0, st, __VA_ARGS__);                             \
-    }                                                                                                             \
-  } while (0)
+// dtype x C in {4, 8} (the entries check C first): f(vsx_type<T>, integral_constant<int, C>)
+template <class F>
+static __forceinline__ void narrow_dispatch(int dtype, int C, F&& f) {
+  vsx_by_dtype(dtype, [&](auto tag) { vsx_by_int<4, 8>(C, [&](auto c) { f(tag, c); }); });
+}
 
 extern "C" int32_t vsx_narrow_proj_fwd(const void* cat, const float* gamma, const float* beta, const float* Wp, const float* bp, void* out,
                                        float* mean, float* rstd, int64_t M, int32_t Ccat, int32_t C, float eps, int32_t dtype,
@@ -808,7 +797,11 @@ extern "C" int32_t vsx_narrow_proj_fwd(const void* cat, const float* gamma, cons
   hipStream_t st = (hipStream_t)stream;
   const long rows16 = (M + 15) / 16;
   const dim3 grid((int)(rows16 < 65536 ? rows16 : 65536));
-  NARROW_DISPATCH(narrow_proj_fwd_kernel, grid, (const T_*)cat, gamma, beta, Wp, bp, (T_*)out, mean, rstd, (long)M, Ccat, eps);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_proj_fwd_kernel<T, decltype(c)::value>), grid, dim3(NB), 0, st, (const T*)cat, gamma, beta, Wp, bp, (T*)out,
+                       mean, rstd, (long)M, Ccat, eps);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -821,8 +814,11 @@ extern "C" int32_t vsx_narrow_proj_bwd(const void* dout, const void* cat, const 
   const int G = proj_wgs(M), NE = C * Ccat + C;
   VSX_CHECK(ws_floats >= (int64_t)G * NE, "vsx_narrow_proj_bwd: workspace needs %ld floats", (long)G * NE);
   hipStream_t st = (hipStream_t)stream;
-  NARROW_DISPATCH(narrow_proj_bwd_kernel, dim3(G), (const T_*)dout, (const T_*)cat, mean, rstd, gamma, beta, Wp, (T_*)dxn, ws, (long)M,
-                  Ccat);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_proj_bwd_kernel<T, decltype(c)::value>), dim3(G), dim3(NB), 0, st, (const T*)dout, (const T*)cat, mean,
+                       rstd, gamma, beta, Wp, (T*)dxn, ws, (long)M, Ccat);
+  });
   VSX_LAUNCH_CHECK();
   if (vsx_det_group_sum(ws, NE, 0, dW, 1, G, C * Ccat, st)) return 2;
   return vsx_det_group_sum(ws, NE, C * Ccat, db, 1, G, C, st) ? 2 : 0;
@@ -841,7 +837,11 @@ extern "C" int32_t vsx_narrow_block_fwd1(const void* x, const float* dw_w, const
   blk_grid(B, (long)H * Wd, gps, tpw);
   VSX_CHECK(ws_floats >= (int64_t)B * gps * 4 * C, "vsx_narrow_block_fwd1: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  NARROW_DISPATCH(narrow_block_fwd1_kernel, dim3(gps, B), (const T_*)x, dw_w, dw_b, (const T_*)W1f, b1f, (T_*)y, ws, H, Wd, tpw);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_block_fwd1_kernel<T, decltype(c)::value>), dim3(gps, B), dim3(NB), 0, st, (const T*)x, dw_w, dw_b,
+                       (const T*)W1f, b1f, (T*)y, ws, H, Wd, tpw);
+  });
   VSX_LAUNCH_CHECK();
   return vsx_det_group_sum(ws, 4 * C, 0, colsq, B, gps, 4 * C, st) ? 2 : 0;
 }
@@ -854,8 +854,11 @@ extern "C" int32_t vsx_narrow_block_fwd2(const void* y, const void* x, const voi
   int gps, tpw;
   blk_grid(B, (long)H * Wd, gps, tpw);
   hipStream_t st = (hipStream_t)stream;
-  NARROW_DISPATCH(narrow_block_fwd2_kernel, dim3(gps, B), (const T_*)y, (const T_*)x, (const T_*)W1f, b1f, s, grn_b, (const T_*)W2, b2,
-                  (T_*)out, H, Wd, tpw);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_block_fwd2_kernel<T, decltype(c)::value>), dim3(gps, B), dim3(NB), 0, st, (const T*)y, (const T*)x,
+                       (const T*)W1f, b1f, s, grn_b, (const T*)W2, b2, (T*)out, H, Wd, tpw);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -872,8 +875,11 @@ extern "C" int32_t vsx_narrow_block_bwd_a(const void* dout, const void* y, const
   const int HD = 4 * C, NE = C * HD + C + 2 * HD;
   VSX_CHECK(ws_floats >= (int64_t)B * gps * NE, "vsx_narrow_block_bwd_a: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  NARROW_DISPATCH(narrow_block_bwd_a_kernel, dim3(gps, B), (const T_*)dout, (const T_*)y, (const T_*)W1f, b1f, s, grn_b, (const T_*)W2, ws,
-                  H, Wd, tpw);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_block_bwd_a_kernel<T, decltype(c)::value>), dim3(gps, B), dim3(NB), 0, st, (const T*)dout, (const T*)y,
+                       (const T*)W1f, b1f, s, grn_b, (const T*)W2, ws, H, Wd, tpw);
+  });
   VSX_LAUNCH_CHECK();
   if (vsx_det_group_sum(ws, NE, 0, dW2, 1, B * gps, C * HD, st) || vsx_det_group_sum(ws, NE, C * HD, db2, 1, B * gps, C, st) ||
       vsx_det_group_sum(ws, NE, C * HD + C, P, B, gps, HD, st) || vsx_det_group_sum(ws, NE, C * HD + C + HD, S, B, gps, HD, st))
@@ -892,8 +898,11 @@ extern "C" int32_t vsx_narrow_block_bwd_b(const void* dout, const void* y, const
   const int HD = 4 * C, NE = HD * C + HD;
   VSX_CHECK(ws_floats >= (int64_t)B * gps * NE, "vsx_narrow_block_bwd_b: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  NARROW_DISPATCH(narrow_block_bwd_b_kernel, dim3(gps, B), (const T_*)dout, (const T_*)y, (const T_*)W1f, b1f, s, t, (const T_*)W2,
-                  (T_*)dy, ws, H, Wd, tpw);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_block_bwd_b_kernel<T, decltype(c)::value>), dim3(gps, B), dim3(NB), 0, st, (const T*)dout, (const T*)y,
+                       (const T*)W1f, b1f, s, t, (const T*)W2, (T*)dy, ws, H, Wd, tpw);
+  });
   VSX_LAUNCH_CHECK();
   if (vsx_det_group_sum(ws, NE, 0, dW1f, 1, B * gps, HD * C, st) || vsx_det_group_sum(ws, NE, HD * C, db1f, 1, B * gps, HD, st)) return 2;
   return 0;
@@ -910,7 +919,11 @@ extern "C" int32_t vsx_narrow_block_bwd_c(const void* dy, const void* x, const v
   const int NE = 49 * C + C;
   VSX_CHECK(ws_floats >= (int64_t)B * gps * NE, "vsx_narrow_block_bwd_c: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  NARROW_DISPATCH(narrow_block_bwd_c_kernel, dim3(gps, B), (const T_*)dy, (const T_*)x, (const T_*)dout, dw_w, (T_*)dx, ws, H, Wd, tpw);
+  narrow_dispatch(dtype, C, [&](auto tag, auto c) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((narrow_block_bwd_c_kernel<T, decltype(c)::value>), dim3(gps, B), dim3(NB), 0, st, (const T*)dy, (const T*)x,
+                       (const T*)dout, dw_w, (T*)dx, ws, H, Wd, tpw);
+  });
   VSX_LAUNCH_CHECK();
   if (vsx_det_group_sum(ws, NE, 0, ddw, 1, B * gps, 49 * C, st) || vsx_det_group_sum(ws, NE, 49 * C, ddb, 1, B * gps, C, st)) return 2;
   return 0;
@@ -922,12 +935,11 @@ extern "C" int32_t vsx_narrow_voxel_shuffle_bwd(const float* dout, void* dfeat, 
   const long total = (long)B * h * w * Cout * D * s * s;
   int g = vsx_cdiv(total, NB);
   if (g > 65536) g = 65536;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(narrow_voxel_shuffle_bwd_kernel<bf16_t>, dim3(g), dim3(NB), 0, (hipStream_t)stream, dout, (bf16_t*)dfeat, B, h, w,
-                       Cout, D, s, pool);
-  else
-    hipLaunchKernelGGL(narrow_voxel_shuffle_bwd_kernel<float>, dim3(g), dim3(NB), 0, (hipStream_t)stream, dout, (float*)dfeat, B, h, w,
-                       Cout, D, s, pool);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(narrow_voxel_shuffle_bwd_kernel<T>, dim3(g), dim3(NB), 0, (hipStream_t)stream, dout, (T*)dfeat, B, h, w, Cout, D, s,
+                       pool);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

@@ -250,14 +250,11 @@ static int ln_launch(bool fwd, const void* a0, const void* a1, void* out, float*
     if (iters < 1) iters = 1;
     int grid = vsx_cdiv(rows, RPI * iters);
     size_t sh = dgamma ? 2 * (size_t)C * sizeof(float) : 0;
-    if (gamma || dgamma)
-      hipLaunchKernelGGL((ln_bwd_kernel<T, G, CPL, true>), dim3(grid), dim3(256), sh, s, (const T*)a0, (const T*)a1,
-                         (const float*)mean, (const float*)rstd, gamma, (const T*)add, (T*)out, dgamma, dbeta, rows, C,
-                         iters, g_vsx_ln_stream & 1);
-    else
-      hipLaunchKernelGGL((ln_bwd_kernel<T, G, CPL, false>), dim3(grid), dim3(256), sh, s, (const T*)a0, (const T*)a1,
-                         (const float*)mean, (const float*)rstd, gamma, (const T*)add, (T*)out, dgamma, dbeta, rows, C,
-                         iters, g_vsx_ln_stream & 1);
+    vsx_by_bool(gamma || dgamma, [&](auto affine) {
+      hipLaunchKernelGGL((ln_bwd_kernel<T, G, CPL, decltype(affine)::value>), dim3(grid), dim3(256), sh, s, (const T*)a0, (const T*)a1,
+                         (const float*)mean, (const float*)rstd, gamma, (const T*)add, (T*)out, dgamma, dbeta, rows, C, iters,
+                         g_vsx_ln_stream & 1);
+    });
   }
   VSX_LAUNCH_CHECK();
   return 0;
@@ -295,28 +292,29 @@ static int ln_dispatch(bool fwd, const void* a0, const void* a1, void* out, floa
  * into fc1 on the host side, see viscy_amd/unext2.py). */
 extern "C" int32_t vsx_ln_fwd(const void* x, void* y, float* mean, float* rstd, const float* gamma, const float* beta,
                               int32_t rows, int32_t C, float eps, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(rows > 0 && C > 0 && C % vn == 0, "vsx_ln_fwd: rows=%d C=%d (C must be a multiple of %d)", rows, C, vn);
   VSX_CHECK(x && y && rstd, "vsx_ln_fwd: null pointer");
   VSX_CHECK((gamma == nullptr) == (beta == nullptr), "vsx_ln_fwd: gamma and beta must both be set or both NULL");
   hipStream_t s = (hipStream_t)stream;
-  return dtype == VSX_BF16
-             ? ln_dispatch<bf16_t>(true, x, nullptr, y, mean, rstd, gamma, beta, nullptr, nullptr, nullptr, rows, C, eps, s)
-             : ln_dispatch<float>(true, x, nullptr, y, mean, rstd, gamma, beta, nullptr, nullptr, nullptr, rows, C, eps, s);
+  return vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ln_dispatch<T>(true, x, nullptr, y, mean, rstd, gamma, beta, nullptr, nullptr, nullptr, rows, C, eps, s);
+  });
 }
 
 extern "C" int32_t vsx_ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                               const void* add, void* dx, float* dgamma, float* dbeta, int32_t rows, int32_t C,
                               int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(rows > 0 && C > 0 && C % vn == 0, "vsx_ln_bwd: rows=%d C=%d (C must be a multiple of %d)", rows, C, vn);
   VSX_CHECK(dy && x && rstd && dx, "vsx_ln_bwd: null pointer");
   VSX_CHECK((dgamma == nullptr) == (dbeta == nullptr), "vsx_ln_bwd: dgamma and dbeta must both be set or both NULL");
   hipStream_t s = (hipStream_t)stream;
-  return dtype == VSX_BF16 ? ln_dispatch<bf16_t>(false, dy, x, dx, (float*)mean, (float*)rstd, gamma, nullptr, add,
-                                                 dgamma, dbeta, rows, C, 0.f, s)
-                           : ln_dispatch<float>(false, dy, x, dx, (float*)mean, (float*)rstd, gamma, nullptr, add,
-                                                dgamma, dbeta, rows, C, 0.f, s);
+  return vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ln_dispatch<T>(false, dy, x, dx, (float*)mean, (float*)rstd, gamma, nullptr, add, dgamma, dbeta, rows, C, 0.f, s);
+  });
 }
 
 // ------------------------------------------------------------------ GRN statistics (fp32, [B, N])
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
 extern "C" int32_t vsx_grn_gelu_bwd(void* dz, const void* h, const float* s, const float* t, float* colsum, float* ws,
                                     int32_t ws_rows, int32_t M, int32_t N, int32_t hw, int32_t dtype,
                                     vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dz && h && s && t && colsum && ws && ws_rows > 0 && M > 0 && N > 0 && hw > 0 && N % vn == 0,
             "vsx_grn_gelu_bwd: bad arguments");
   int ncc = N / vn;
@@ -541,12 +539,10 @@ extern "C" int32_t vsx_grn_gelu_bwd(void* dz, const void* h, const float* s, con
   }
   dim3 grid(gx, gy);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(grn_gelu_bwd_kernel<bf16_t>, grid, dim3(nthreads), 0, st, (bf16_t*)dz, (const bf16_t*)h, s, t, ws, M, N,
-                       hw, tpr, g_vsx_grn_stream, rpb);
-  else
-    hipLaunchKernelGGL(grn_gelu_bwd_kernel<float>, grid, dim3(nthreads), 0, st, (float*)dz, (const float*)h, s, t, ws, M, N, hw,
-                       tpr, g_vsx_grn_stream, rpb);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(grn_gelu_bwd_kernel<T>, grid, dim3(nthreads), 0, st, (T*)dz, (const T*)h, s, t, ws, M, N, hw, tpr, g_vsx_grn_stream, rpb);
+  });
   VSX_LAUNCH_CHECK();
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(vsx_cdiv(N, 64), vsx_cdiv(gy, 64)), dim3(256), 0, st, ws, colsum, gy, N);
   VSX_LAUNCH_CHECK();
@@ -656,10 +652,10 @@ extern "C" int32_t vsx_grn_q_reduce(const float* Q, const float* cs, const void*
   // block until the launch has ~256 workgroups (the atomics per address grow to C / 8 at most)
   while (cb > 8 && (long)vsx_cdiv(N, QR_TH * 4) * G * vsx_cdiv(C, cb) < 256) cb /= 2;
   dim3 grid(vsx_cdiv(N, QR_TH * 4), G, vsx_cdiv(C, cb));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(grn_q_reduce_kernel<bf16_t>, grid, dim3(QR_TH), 0, st, Q, cs, (const bf16_t*)W2, s, beta, P, S, ws, db2, nb, C, cb);
-  else
-    hipLaunchKernelGGL(grn_q_reduce_kernel<float>, grid, dim3(QR_TH), 0, st, Q, cs, (const float*)W2, s, beta, P, S, ws, db2, nb, C, cb);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(grn_q_reduce_kernel<T>, grid, dim3(QR_TH), 0, st, Q, cs, (const T*)W2, s, beta, P, S, ws, db2, nb, C, cb);
+  });
   // dW2[c, j] += sum over the groups' partials (the [C, 4C] matrix seen as one row of C * 4C columns)
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(vsx_cdiv((long)C * N, 64), vsx_cdiv(G, 64)), dim3(256), 0, st, (const float*)ws, dW2, G,
                      C * N);

@@ -247,15 +247,12 @@ extern "C" int32_t vsx_knn_topk(const float* x, const float* inv, const int32_t*
   const bool vec = ft_vec_ok(x, d);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)qtiles, (unsigned)splits), block(FT_THREADS);
-#define KT_GO(VEC, KB) hipLaunchKernelGGL((knn_topk_kernel<VEC, KB>), grid, block, 0, s, x, inv, group, N, d, k, tps, pidx, psim, pcnt)
-  if (k <= 8) {
-    if (vec) KT_GO(true, 8); else KT_GO(false, 8);
-  } else if (k <= 24) {
-    if (vec) KT_GO(true, 24); else KT_GO(false, 24);
-  } else {
-    if (vec) KT_GO(true, 64); else KT_GO(false, 64);
-  }
-#undef KT_GO
+  vsx_by_int<8, 24, 64>(k <= 8 ? 8 : k <= 24 ? 24 : 64, [&](auto kb) {  // the smallest candidate buffer that holds k
+    vsx_by_bool(vec, [&](auto vec_) {
+      hipLaunchKernelGGL((knn_topk_kernel<decltype(vec_)::value, decltype(kb)::value>), grid, block, 0, s, x, inv, group, N, d, k, tps, pidx,
+                         psim, pcnt);
+    });
+  });
   hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const int*)pidx, (const float*)psim,
                      (const int*)pcnt, N, k, splits, idx, sim, cnt);
   VSX_LAUNCH_CHECK();

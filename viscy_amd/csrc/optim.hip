@@ -140,12 +140,10 @@ extern "C" int32_t vsx_prep_weight(const float* src, void* dst, void* dstT, cons
   VSX_CHECK(tapmode == 0 || (tapmode == 1 && Tn == 27), "vsx_prep_weight: tapmode 1 needs 27 taps");
   long total = (long)R * Cs * Tn;
   dim3 grid(vsx_cdiv(total, 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(prep_weight_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst,
-                       (bf16_t*)dstT, gamma, R, Cs, Tn, tapmode);
-  else
-    hipLaunchKernelGGL(prep_weight_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst,
-                       (float*)dstT, gamma, R, Cs, Tn, tapmode);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(prep_weight_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, (T*)dst, (T*)dstT, gamma, R, Cs, Tn, tapmode);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -351,12 +349,10 @@ extern "C" int32_t vsx_prep_head_dgrad(const float* W, void* dst, int32_t Cmid, 
   VSX_CHECK(W && dst && Cmid > 0 && C3 > 0 && Zout >= 3, "vsx_prep_head_dgrad: bad arguments (Zout=%d must be >= 3)", Zout);
   long total = (long)(Zout + 2) * C3 * 27 * Cmid;
   dim3 grid(vsx_cdiv(total, 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(prep_head_dgrad_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, W, (bf16_t*)dst, Cmid, C3,
-                       Zout);
-  else
-    hipLaunchKernelGGL(prep_head_dgrad_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, W, (float*)dst, Cmid, C3,
-                       Zout);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(prep_head_dgrad_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, W, (T*)dst, Cmid, C3, Zout);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -384,15 +380,15 @@ __global__ __launch_bounds__(256) void scale_weight_samples_kernel(const float* 
 }
 extern "C" int32_t vsx_scale_weight_samples(const float* W, const float* s, void* out, int32_t B, int32_t R, int32_t K,
                                             int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(W && s && out && B > 0 && R > 0 && K > 0 && K % vn == 0, "vsx_scale_weight_samples: bad arguments (K=%d)", K);
   long total = (long)B * R * (K / vn);
   int g = vsx_cdiv(total, 256);
   if (g > 8192) g = 8192;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(scale_weight_samples_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, W, s, (bf16_t*)out, B, R, K);
-  else
-    hipLaunchKernelGGL(scale_weight_samples_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, W, s, (float*)out, B, R, K);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(scale_weight_samples_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, W, s, (T*)out, B, R, K);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

@@ -314,10 +314,9 @@ extern "C" int32_t vsx_gram_centered(const float* x, int64_t n, int32_t d, const
   gm_split(n, d, &tiles, &pairs, &splits, &rps);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)pairs, (unsigned)splits), block(FT_THREADS);
-  if (ft_vec_ok(x, d))
-    hipLaunchKernelGGL(pca_gram_kernel<true>, grid, block, 0, s, x, mean, (long)n, d, tiles, (long)rps, (double*)ws);
-  else
-    hipLaunchKernelGGL(pca_gram_kernel<false>, grid, block, 0, s, x, mean, (long)n, d, tiles, (long)rps, (double*)ws);
+  vsx_by_bool(ft_vec_ok(x, d), [&](auto vec) {
+    hipLaunchKernelGGL(pca_gram_kernel<decltype(vec)::value>, grid, block, 0, s, x, mean, (long)n, d, tiles, (long)rps, (double*)ws);
+  });
   hipLaunchKernelGGL(pca_gram_fold_kernel, dim3((unsigned)pairs, FT_T * FT_T / 256), dim3(256), 0, s, (const double*)ws, splits, pairs, tiles, d,
                      gram);
   VSX_LAUNCH_CHECK();
@@ -333,10 +332,9 @@ extern "C" int32_t vsx_center_project(const float* x, int64_t n, int32_t d, cons
             "vsx_center_project: x, w and z must be 4-byte aligned, mean 8-byte aligned");
   const dim3 grid((unsigned)((n + FT_T - 1) / FT_T), (unsigned)((k + FT_T - 1) / FT_T)), block(FT_THREADS);
   hipStream_t s = (hipStream_t)stream;
-  if (ft_vec_ok(x, d) && vsx_al16(w))
-    hipLaunchKernelGGL(pca_project_kernel<true>, grid, block, 0, s, x, mean, w, (int)n, d, k, z);
-  else
-    hipLaunchKernelGGL(pca_project_kernel<false>, grid, block, 0, s, x, mean, w, (int)n, d, k, z);
+  vsx_by_bool(ft_vec_ok(x, d) && vsx_al16(w), [&](auto vec) {
+    hipLaunchKernelGGL(pca_project_kernel<decltype(vec)::value>, grid, block, 0, s, x, mean, w, (int)n, d, k, z);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

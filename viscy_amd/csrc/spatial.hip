@@ -85,7 +85,8 @@ __global__ __launch_bounds__(256) void stem_im2col_kernel(const float* __restric
 static int stem_im2col_launch(const float* x, void* P, const float* sub, const float* div, int32_t B, int32_t Cin, int32_t Z,
                               int32_t H, int32_t W, int32_t kz, int32_t ky, int32_t kx, int32_t ldp, int32_t dtype,
                               vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  const int vn = vsx_vec_elems(dtype);
+  hipStream_t s = (hipStream_t)stream;
   VSX_CHECK(x && P && B > 0 && Cin > 0, "vsx_stem_im2col: bad arguments");
   VSX_CHECK(Z % kz == 0 && H % ky == 0 && W % kx == 0, "vsx_stem_im2col: (%d,%d,%d) not divisible by kernel (%d,%d,%d)",
             Z, H, W, kz, ky, kx);
@@ -95,12 +96,10 @@ static int stem_im2col_launch(const float* x, void* P, const float* sub, const f
   VSX_CHECK((sub == nullptr) == (div == nullptr), "vsx_stem_im2col: sub/div must both be set or both NULL");
   long total = (long)B * (H / ky) * (W / kx) * (ldp / vn);
   dim3 grid(vsx_cdiv(total, 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(stem_im2col_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)P, sub, div, B,
-                       Cin, Z, H, W, kz, ky, kx, ldp);
-  else
-    hipLaunchKernelGGL(stem_im2col_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, (float*)P, sub, div, B,
-                       Cin, Z, H, W, kz, ky, kx, ldp);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(stem_im2col_kernel<T>, grid, dim3(256), 0, s, x, (T*)P, sub, div, B, Cin, Z, H, W, kz, ky, kx, ldp);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -131,10 +130,10 @@ __global__ __launch_bounds__(256) void pad_cols_kernel(const T* __restrict__ src
 extern "C" int32_t vsx_pad_cols(const void* src, void* dst, int32_t R, int32_t K, int32_t Kp, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(src && dst && R > 0 && K > 0 && Kp >= K, "vsx_pad_cols: bad arguments");
   dim3 grid(vsx_cdiv((long)R * Kp, 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(pad_cols_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, (bf16_t*)dst, R, K, Kp);
-  else
-    hipLaunchKernelGGL(pad_cols_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, (float*)dst, R, K, Kp);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(pad_cols_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)dst, R, K, Kp);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -192,26 +191,26 @@ __global__ __launch_bounds__(256) void col2im3x3_kernel(const T* __restrict__ dc
 
 extern "C" int32_t vsx_im2col3x3(const void* x, void* col, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                                  vsx_stream_t stream) {
-  const int vn = dtype == VSX_BF16 ? 8 : 4;
+  const int vn = vsx_vec_elems(dtype);
   VSX_CHECK(x && col && B > 0 && H > 0 && W > 0 && C > 0 && C % vn == 0, "vsx_im2col3x3: bad arguments (C=%d)", C);
   dim3 grid(vsx_cdiv((long)B * H * W * 9 * (C / vn), 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(im2col3x3_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)col, B, H, W, C);
-  else
-    hipLaunchKernelGGL(im2col3x3_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)col, B, H, W, C);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(im2col3x3_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)col, B, H, W, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int32_t vsx_col2im3x3(const void* dcol, void* dx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                                  vsx_stream_t stream) {
-  const int vn = dtype == VSX_BF16 ? 8 : 4;
+  const int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dcol && dx && B > 0 && H > 0 && W > 0 && C > 0 && C % vn == 0, "vsx_col2im3x3: bad arguments (C=%d)", C);
   dim3 grid(vsx_cdiv((long)B * H * W * (C / vn), 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(col2im3x3_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dcol, (bf16_t*)dx, B, H, W, C);
-  else
-    hipLaunchKernelGGL(col2im3x3_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dcol, (float*)dx, B, H, W, C);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(col2im3x3_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)dcol, (T*)dx, B, H, W, C);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -346,59 +345,52 @@ __global__ __launch_bounds__(256) void ps_cat_vec_kernel(const T* __restrict__ a
  * (viscy_models/components/blocks.py:138-146,170-171).  skip may be NULL (cs = 0). */
 extern "C" int32_t vsx_pixel_shuffle_cat_fwd(const void* low, const void* skip, void* out, int32_t B, int32_t h,
                                              int32_t w, int32_t c, int32_t cs, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(low && out && B > 0 && h > 0 && w > 0 && c > 0 && cs >= 0, "vsx_pixel_shuffle_cat_fwd: bad arguments");
   VSX_CHECK((cs == 0) == (skip == nullptr), "vsx_pixel_shuffle_cat_fwd: skip pointer / cs mismatch");
   VSX_CHECK((c + cs) % vn == 0, "vsx_pixel_shuffle_cat_fwd: c+cs=%d must be a multiple of %d", c + cs, vn);
+  hipStream_t s = (hipStream_t)stream;
   if (c % vn == 0 && cs % vn == 0) {  // whole vectors on both sides: the register-(de)interleaving form
     const long items = (long)B * h * w * (c / vn) + (long)B * 4 * h * w * (cs / vn);
-    dim3 g(vsx_cdiv(items, 256));
-    if (dtype == VSX_BF16)
-      hipLaunchKernelGGL((ps_cat_vec_kernel<bf16_t, false>), g, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)low,
-                         (const bf16_t*)skip, (bf16_t*)out, (bf16_t*)nullptr, B, h, w, c, cs);
-    else
-      hipLaunchKernelGGL((ps_cat_vec_kernel<float, false>), g, dim3(256), 0, (hipStream_t)stream, (const float*)low,
-                         (const float*)skip, (float*)out, (float*)nullptr, B, h, w, c, cs);
+    vsx_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((ps_cat_vec_kernel<T, false>), dim3(vsx_cdiv(items, 256)), dim3(256), 0, s, (const T*)low, (const T*)skip,
+                         (T*)out, (T*)nullptr, B, h, w, c, cs);
+    });
     VSX_LAUNCH_CHECK();
     return 0;
   }
-  long total = (long)B * 4 * h * w * ((c + cs) / vn);
-  dim3 grid(vsx_cdiv(total, 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(ps_cat_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)low,
-                       (const bf16_t*)skip, (bf16_t*)out, B, h, w, c, cs);
-  else
-    hipLaunchKernelGGL(ps_cat_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)low,
-                       (const float*)skip, (float*)out, B, h, w, c, cs);
+  const long total = (long)B * 4 * h * w * ((c + cs) / vn);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ps_cat_fwd_kernel<T>, dim3(vsx_cdiv(total, 256)), dim3(256), 0, s, (const T*)low, (const T*)skip, (T*)out, B, h, w,
+                       c, cs);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int32_t vsx_pixel_shuffle_cat_bwd(const void* dcat, void* dlow, void* dskip, int32_t B, int32_t h, int32_t w,
                                              int32_t c, int32_t cs, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dcat && dlow && B > 0 && h > 0 && w > 0 && c > 0 && cs >= 0, "vsx_pixel_shuffle_cat_bwd: bad arguments");
   VSX_CHECK((cs == 0) == (dskip == nullptr), "vsx_pixel_shuffle_cat_bwd: dskip pointer / cs mismatch");
   VSX_CHECK((c + cs) % vn == 0, "vsx_pixel_shuffle_cat_bwd: c+cs=%d must be a multiple of %d", c + cs, vn);
+  hipStream_t s = (hipStream_t)stream;
   if (c % vn == 0 && cs % vn == 0) {
     const long items = (long)B * h * w * (c / vn) + (long)B * 4 * h * w * (cs / vn);
-    dim3 g(vsx_cdiv(items, 256));
-    if (dtype == VSX_BF16)
-      hipLaunchKernelGGL((ps_cat_vec_kernel<bf16_t, true>), g, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dcat,
-                         (const bf16_t*)nullptr, (bf16_t*)dlow, (bf16_t*)dskip, B, h, w, c, cs);
-    else
-      hipLaunchKernelGGL((ps_cat_vec_kernel<float, true>), g, dim3(256), 0, (hipStream_t)stream, (const float*)dcat,
-                         (const float*)nullptr, (float*)dlow, (float*)dskip, B, h, w, c, cs);
+    vsx_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((ps_cat_vec_kernel<T, true>), dim3(vsx_cdiv(items, 256)), dim3(256), 0, s, (const T*)dcat, (const T*)nullptr,
+                         (T*)dlow, (T*)dskip, B, h, w, c, cs);
+    });
     VSX_LAUNCH_CHECK();
     return 0;
   }
-  long total = (long)B * 4 * h * w * ((c + cs) / vn);
-  dim3 grid(vsx_cdiv(total, 256));
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(ps_cat_bwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dcat,
-                       (bf16_t*)dlow, (bf16_t*)dskip, B, h, w, c, cs);
-  else
-    hipLaunchKernelGGL(ps_cat_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dcat,
-                       (float*)dlow, (float*)dskip, B, h, w, c, cs);
+  const long total = (long)B * 4 * h * w * ((c + cs) / vn);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ps_cat_bwd_kernel<T>, dim3(vsx_cdiv(total, 256)), dim3(256), 0, s, (const T*)dcat, (T*)dlow, (T*)dskip, B, h, w, c, cs);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -790,72 +782,70 @@ __global__ __launch_bounds__(256) void head_shuffle_bwd_strip_kernel(const bf16_
  * (channel = z*C3 + c3), so the 3x3x3 head convolution reads contiguous channel slices per z. */
 extern "C" int32_t vsx_head_shuffle_fwd(const void* dec, void* hin, int32_t B, int32_t h, int32_t w, int32_t C3,
                                         int32_t D, int32_t pool, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dec && hin && B > 0 && h > 0 && w > 0 && C3 > 0 && D > 0, "vsx_head_shuffle_fwd: bad arguments");
   VSX_CHECK((C3 * D) % vn == 0, "vsx_head_shuffle_fwd: C3*D=%d must be a multiple of %d", C3 * D, vn);
   long total = (long)B * 4 * h * w * (C3 * D / vn);
   dim3 grid(vsx_cdiv(total, 256));
+  hipStream_t s = (hipStream_t)stream;
   if (dtype == VSX_BF16 && pool && (g_vsx_head_rows & 8) && C3 * D == 56 && w % HS_TX == 0 && B <= 65535) {
     // column strips (round 6); rows per workgroup: two workgroups per CU in one round when the batch allows it
     const long strips = (long)B * (w / HS_TX);
     long rpw = (long)h * strips / 512;
     rpw = rpw < 8 ? 8 : (rpw > h ? h : rpw);
-    hipLaunchKernelGGL((head_shuffle_fwd_strip_kernel<7>), dim3(w / HS_TX, vsx_cdiv(h, rpw), B), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((head_shuffle_fwd_strip_kernel<7>), dim3(w / HS_TX, vsx_cdiv(h, rpw), B), dim3(256), 0, s,
                        (const bf16_t*)dec, (bf16_t*)hin, h, w, C3, D, (int)rpw);
     VSX_LAUNCH_CHECK();
     return 0;
   }
   if (C3 * D <= 64 && B <= 65535) {  // LDS-tiled permutation
-    if (dtype == VSX_BF16)
-      hipLaunchKernelGGL((head_shuffle_fwd_tiled_kernel<bf16_t, 8>), dim3(vsx_cdiv(w, 8), vsx_cdiv(h, 8), B), dim3(256), 0,
-                         (hipStream_t)stream, (const bf16_t*)dec, (bf16_t*)hin, h, w, C3, D, pool);
-    else
-      hipLaunchKernelGGL((head_shuffle_fwd_tiled_kernel<float, 4>), dim3(vsx_cdiv(w, 4), vsx_cdiv(h, 4), B), dim3(256), 0,
-                         (hipStream_t)stream, (const float*)dec, (float*)hin, h, w, C3, D, pool);
+    vsx_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      constexpr int TS = sizeof(T) == 2 ? 8 : 4;  // tile edge in decoder pixels
+      hipLaunchKernelGGL((head_shuffle_fwd_tiled_kernel<T, TS>), dim3(vsx_cdiv(w, TS), vsx_cdiv(h, TS), B), dim3(256), 0, s,
+                         (const T*)dec, (T*)hin, h, w, C3, D, pool);
+    });
     VSX_LAUNCH_CHECK();
     return 0;
   }
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(head_shuffle_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dec,
-                       (bf16_t*)hin, B, h, w, C3, D, pool);
-  else
-    hipLaunchKernelGGL(head_shuffle_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dec,
-                       (float*)hin, B, h, w, C3, D, pool);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(head_shuffle_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dec, (T*)hin, B, h, w, C3, D, pool);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int32_t vsx_head_shuffle_bwd(const void* dhin, void* ddec, int32_t B, int32_t h, int32_t w, int32_t C3,
                                         int32_t D, int32_t pool, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dhin && ddec && B > 0 && h > 0 && w > 0 && C3 > 0 && D > 0, "vsx_head_shuffle_bwd: bad arguments");
   VSX_CHECK((4 * C3 * D) % vn == 0, "vsx_head_shuffle_bwd: 4*C3*D must be a multiple of %d", vn);
   long total = (long)B * h * w * (4 * C3 * D / vn);
   dim3 grid(vsx_cdiv(total, 256));
+  hipStream_t s = (hipStream_t)stream;
   if (dtype == VSX_BF16 && pool && (g_vsx_head_rows & 16) && C3 * D == 56 && w % HS_TX == 0 && B <= 65535) {
     const long strips = (long)B * (w / HS_TX);
     long rpw = (long)h * strips / 512;
     rpw = rpw < 8 ? 8 : (rpw > h ? h : rpw);
-    hipLaunchKernelGGL((head_shuffle_bwd_strip_kernel<7>), dim3(w / HS_TX, vsx_cdiv(h, rpw), B), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((head_shuffle_bwd_strip_kernel<7>), dim3(w / HS_TX, vsx_cdiv(h, rpw), B), dim3(256), 0, s,
                        (const bf16_t*)dhin, (bf16_t*)ddec, h, w, C3, D, (int)rpw);
     VSX_LAUNCH_CHECK();
     return 0;
   }
   if (C3 * D <= 64 && B <= 65535) {  // LDS-tiled permutation
-    if (dtype == VSX_BF16)
-      hipLaunchKernelGGL((head_shuffle_bwd_tiled_kernel<bf16_t, 8>), dim3(vsx_cdiv(w, 8), vsx_cdiv(h, 8), B), dim3(256), 0,
-                         (hipStream_t)stream, (const bf16_t*)dhin, (bf16_t*)ddec, h, w, C3, D, pool);
-    else
-      hipLaunchKernelGGL((head_shuffle_bwd_tiled_kernel<float, 4>), dim3(vsx_cdiv(w, 4), vsx_cdiv(h, 4), B), dim3(256), 0,
-                         (hipStream_t)stream, (const float*)dhin, (float*)ddec, h, w, C3, D, pool);
+    vsx_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      constexpr int TS = sizeof(T) == 2 ? 8 : 4;  // tile edge in decoder pixels
+      hipLaunchKernelGGL((head_shuffle_bwd_tiled_kernel<T, TS>), dim3(vsx_cdiv(w, TS), vsx_cdiv(h, TS), B), dim3(256), 0, s,
+                         (const T*)dhin, (T*)ddec, h, w, C3, D, pool);
+    });
     VSX_LAUNCH_CHECK();
     return 0;
   }
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(head_shuffle_bwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dhin,
-                       (bf16_t*)ddec, B, h, w, C3, D, pool);
-  else
-    hipLaunchKernelGGL(head_shuffle_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dhin,
-                       (float*)ddec, B, h, w, C3, D, pool);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(head_shuffle_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dhin, (T*)ddec, B, h, w, C3, D, pool);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -935,29 +925,25 @@ extern "C" int32_t vsx_voxel_shuffle_fwd(const void* feat, float* out, int32_t B
   long total = (long)B * Cout * D * h * s * w * s;
   int g = vsx_cdiv(total, 256);
   if (g > 65536) g = 65536;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(voxel_shuffle_fwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)feat, out, B, h,
-                       w, Cout, D, s, pool);
-  else
-    hipLaunchKernelGGL(voxel_shuffle_fwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)feat, out, B, h, w,
-                       Cout, D, s, pool);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(voxel_shuffle_fwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)feat, out, B, h, w, Cout, D, s, pool);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int32_t vsx_voxel_shuffle_bwd(const float* dout, void* dfeat, int32_t B, int32_t h, int32_t w, int32_t Cout, int32_t D,
                                          int32_t s, int32_t pool, int32_t dtype, vsx_stream_t stream) {
-  int vn = dtype == VSX_BF16 ? 8 : 4;
+  int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dout && dfeat && B > 0 && h > 0 && w > 0 && Cout > 0 && D > 0 && s > 0, "vsx_voxel_shuffle_bwd: bad arguments");
   VSX_CHECK((Cout * D * s * s) % vn == 0, "vsx_voxel_shuffle_bwd: Cout*D*s*s=%d must be a multiple of %d", Cout * D * s * s, vn);
   long total = (long)B * h * w * (Cout * D * s * s / vn);
   int g = vsx_cdiv(total, 256);
   if (g > 65536) g = 65536;
-  if (dtype == VSX_BF16)
-    hipLaunchKernelGGL(voxel_shuffle_bwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, dout, (bf16_t*)dfeat, B, h, w,
-                       Cout, D, s, pool);
-  else
-    hipLaunchKernelGGL(voxel_shuffle_bwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, dout, (float*)dfeat, B, h, w, Cout,
-                       D, s, pool);
+  vsx_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(voxel_shuffle_bwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, dout, (T*)dfeat, B, h, w, Cout, D, s, pool);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

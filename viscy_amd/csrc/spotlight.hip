@@ -291,18 +291,13 @@ extern "C" int64_t vsx_spotlight_workspace(int32_t op, int64_t rows, int64_t n) 
   return 0;
 }
 
-#define SL_DISPATCH(KERNEL, ...)                                                                                          \
-  do {                                                                                                                    \
-    if (dtype == VSX_BF16) {                                                                                              \
-      if (mask_mode == VSX_SPOTLIGHT_THRESHOLD) KERNEL(bf16_t, VSX_SPOTLIGHT_THRESHOLD, __VA_ARGS__);                     \
-      else if (mask_mode == VSX_SPOTLIGHT_MASK_U8) KERNEL(bf16_t, VSX_SPOTLIGHT_MASK_U8, __VA_ARGS__);                    \
-      else KERNEL(bf16_t, VSX_SPOTLIGHT_MASK_F32, __VA_ARGS__);                                                           \
-    } else {                                                                                                              \
-      if (mask_mode == VSX_SPOTLIGHT_THRESHOLD) KERNEL(float, VSX_SPOTLIGHT_THRESHOLD, __VA_ARGS__);                      \
-      else if (mask_mode == VSX_SPOTLIGHT_MASK_U8) KERNEL(float, VSX_SPOTLIGHT_MASK_U8, __VA_ARGS__);                     \
-      else KERNEL(float, VSX_SPOTLIGHT_MASK_F32, __VA_ARGS__);                                                            \
-    }                                                                                                                     \
-  } while (0)
+// dtype x the three mask modes: f(vsx_type<T>, integral_constant<int, mode>)
+template <class F>
+static __forceinline__ void sl_dispatch(int dtype, int mask_mode, F&& f) {
+  vsx_by_dtype(dtype, [&](auto tag) {
+    vsx_by_int<VSX_SPOTLIGHT_THRESHOLD, VSX_SPOTLIGHT_MASK_U8, VSX_SPOTLIGHT_MASK_F32>(mask_mode, [&](auto mode) { f(tag, mode); });
+  });
+}
 
 static int sl_check(const char* who, const void* pred, int32_t dtype, const float* target, const void* mask, int32_t mask_mode,
                     const float* thr, int64_t rows, int64_t n, double k) {
@@ -328,10 +323,11 @@ extern "C" int32_t vsx_spotlight_fwd(const void* pred, int32_t dtype, const floa
   double* rowstat = part + rows * cpr * 5;
   const dim3 grid((unsigned)(rows * cpr)), block(SL_THREADS);
   hipStream_t s = (hipStream_t)stream;
-#define SL_FWD(TP, MODE, ...) \
-  hipLaunchKernelGGL((spotlight_sums_kernel<TP, MODE>), grid, block, 0, s, (const TP*)pred, target, mask, thr, part, (long)n, cpr, vec, k)
-  SL_DISPATCH(SL_FWD, 0);
-#undef SL_FWD
+  sl_dispatch(dtype, mask_mode, [&](auto tag, auto mode) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((spotlight_sums_kernel<T, decltype(mode)::value>), grid, block, 0, s, (const T*)pred, target, mask, thr, part,
+                       (long)n, cpr, vec, k);
+  });
   hipLaunchKernelGGL(spotlight_rows_kernel, dim3((unsigned)((rows + SL_THREADS / 64 - 1) / (SL_THREADS / 64))), block, 0, s,
                      (const double*)part, rowstat, (long)rows, (long)n, cpr, eps);
   hipLaunchKernelGGL(spotlight_finalize_kernel, dim3(1), block, 0, s, (const double*)rowstat, loss, coef, (long)rows, (long)n,
@@ -350,11 +346,11 @@ extern "C" int32_t vsx_spotlight_bwd(const void* pred, int32_t dtype, const floa
   const SlConst k = sl_const(sigmoid_k);
   const dim3 grid((unsigned)(rows * cpr)), block(SL_THREADS);
   hipStream_t s = (hipStream_t)stream;
-#define SL_BWD(TP, MODE, ...)                                                                                                    \
-  hipLaunchKernelGGL((spotlight_bwd_kernel<TP, MODE>), grid, block, 0, s, (const TP*)pred, target, mask, thr, coef, gout, (TP*)dpred, \
-                     (long)n, cpr, vec, k)
-  SL_DISPATCH(SL_BWD, 0);
-#undef SL_BWD
+  sl_dispatch(dtype, mask_mode, [&](auto tag, auto mode) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((spotlight_bwd_kernel<T, decltype(mode)::value>), grid, block, 0, s, (const T*)pred, target, mask, thr, coef, gout,
+                       (T*)dpred, (long)n, cpr, vec, k);
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
 typedef __bf16 bf16_t;
 
@@ -46,6 +47,38 @@ extern thread_local const char* g_vsx_last_kernel;  // api.hip: set by the GEMM 
 static inline int vsx_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool vsx_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }  // fit for 16-byte vector accesses
 int vsx_cu_count();  // compute units of the current device, asked once (256 where the query fails): api.hip
+
+// ------------------------------------------------------------------ host: runtime value → template argument
+// An entry point receives dtype / an alignment flag / a small channel count at run time and its kernel wants it as a template
+// argument.  Each helper calls the generic lambda `f` with a tag that carries the value in its TYPE and returns what `f`
+// returns (every arm must return the same type):
+//   vsx_by_dtype(dtype, [&](auto tag) { using T = typename decltype(tag)::type;  launch k<T>((const T*)x, ...); });
+//   vsx_by_bool(vec, [&](auto vec_) { launch k<decltype(vec_)::value>(...); });
+// VSX_CHECK / VSX_LAUNCH_CHECK return from the function they stand in: keep them outside the lambda, or let it return int.
+// The arm each return type names (bf16_t, true, V0) is instantiated first, so kernels keep the order of an if / else ladder.
+template <class T>
+struct vsx_type { typedef T type; };
+// VSX_BF16 -> bf16_t; every other code takes the float arm (the entries that care check dtype themselves)
+template <class F>
+static __forceinline__ auto vsx_by_dtype(int dtype, F&& f) -> decltype(f(vsx_type<bf16_t>{})) {
+  if (dtype == VSX_BF16) return f(vsx_type<bf16_t>{});
+  return f(vsx_type<float>{});
+}
+template <class F>
+static __forceinline__ auto vsx_by_bool(bool flag, F&& f) -> decltype(f(std::true_type{})) {
+  if (flag) return f(std::true_type{});
+  return f(std::false_type{});
+}
+// the first Vi == v; where none matches, the LAST Vi (the trailing `else` of a ladder)
+template <int V0, int... Vs, class F>
+static __forceinline__ auto vsx_by_int(int v, F&& f) -> decltype(f(std::integral_constant<int, V0>{})) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else if (v == V0) return f(std::integral_constant<int, V0>{});
+  else return vsx_by_int<Vs...>(v, f);
+}
+static inline int vsx_vec_elems(int dtype) {  // elements per 16-byte vector: 8 for bf16, 4 for float
+  return vsx_by_dtype(dtype, [](auto tag) { return 16 / (int)sizeof(typename decltype(tag)::type); });
+}
 
 // ------------------------------------------------------------------ element traits
 template <typename T>
