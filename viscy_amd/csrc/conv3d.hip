@@ -17,35 +17,17 @@
 //
 // Every reduction is per-workgroup partials + a fold in a fixed order: no atomics, bit-identical from run to run.
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "../../include/vsx.h"
-
-typedef __attribute__((ext_vector_type(4))) float c3_f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 c3_bf16x8;
 
 namespace {
 
 constexpr int C3_BM = 64, C3_BN = 64, C3_THREADS = 256;
 constexpr int C3_RED_THREADS = 256;
 
+// K step of a tile: one bf16 MFMA (32 deep) or four fp32 MFMAs (4 deep each)
 template <typename T>
-struct C3Frag;
-template <>
-struct C3Frag<bf16_t> {
-  typedef c3_bf16x8 type;
-  static constexpr int BK = 32;
-};
-template <>
-struct C3Frag<float> {
-  typedef float type;
-  static constexpr int BK = 16;
-};
-
-__device__ __forceinline__ c3_f32x4 c3_mfma(const c3_bf16x8& a, const c3_bf16x8& b, const c3_f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ c3_f32x4 c3_mfma(const float& a, const float& b, const c3_f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
+constexpr int C3_BK = sizeof(T) == 4 ? 16 : Frag<T>::MK;
 
 struct Tap {
   int dz, dy, dx, wt;
@@ -81,7 +63,7 @@ struct C3Args {
 
 template <typename T, typename TO, bool VEC>
 __global__ __launch_bounds__(C3_THREADS) void conv3d_igemm_kernel(const C3Args p) {
-  constexpr int BK = C3Frag<T>::BK;
+  constexpr int BK = C3_BK<T>;
   constexpr int VN = VT<T>::N;
   constexpr int ES = sizeof(T);
   constexpr int CPR = BK / VN;                  // 16-byte chunks per tile row (4)
@@ -91,7 +73,7 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_igemm_kernel(const C3Args p
   constexpr int EPI = C3_BM * CS_LD * 4;
   constexpr int LDS = MAIN > EPI ? MAIN : EPI;
   typedef typename VT<T>::vec vec;
-  typedef typename C3Frag<T>::type frag_t;
+  typedef typename Frag<T>::type frag_t;
   __shared__ __attribute__((aligned(16))) char smem[LDS];
   __shared__ int orow[C3_BM];
 
@@ -175,11 +157,8 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_igemm_kernel(const C3Args p
     }
   };
 
-  c3_f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (c3_f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[2][2];
+  mfma_zero(acc);
 
   char* As = smem;
   char* Bs = smem + C3_BM * RS;
@@ -208,7 +187,7 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_igemm_kernel(const C3Args p
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = c3_mfma(af[i], bf[j], acc[i][j]);
+        for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(af[i], bf[j], acc[i][j]);
     }
     __syncthreads();
   }
@@ -268,11 +247,11 @@ struct C3WArgs {
 
 template <typename T>
 __global__ __launch_bounds__(C3_THREADS) void conv3d_wgrad_kernel(const C3WArgs p) {
-  constexpr int BK = C3Frag<T>::BK;
+  constexpr int BK = C3_BK<T>;
   constexpr int PAD = 2;
   constexpr int LDP = C3_BM + PAD;             // LDS row (one voxel) of the P tile, in elements
   constexpr int LDQ = C3_BN + PAD;
-  typedef typename C3Frag<T>::type frag_t;
+  typedef typename Frag<T>::type frag_t;
   __shared__ T Ps[BK * LDP];
   __shared__ T Qs[BK * LDQ];
 
@@ -287,11 +266,8 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_wgrad_kernel(const C3WArgs 
   const T* Pg = reinterpret_cast<const T*>(p.P);
   const T* Qg = reinterpret_cast<const T*>(p.Q);
 
-  c3_f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (c3_f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[2][2];
+  mfma_zero(acc);
 
   // per-thread staging: element e of the (BK x 64) tiles, e = tid + 256 * i; voxel = e / 64, column = e % 64
   constexpr int EPT = BK * 64 / C3_THREADS;  // 8 (bf16) or 4 (fp32)
@@ -343,7 +319,7 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_wgrad_kernel(const C3WArgs 
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = c3_mfma(af[i], bf[j], acc[i][j]);
+        for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(af[i], bf[j], acc[i][j]);
     } else {
 #pragma unroll
       for (int kk = 0; kk < BK / 4; ++kk) {
@@ -356,7 +332,7 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_wgrad_kernel(const C3WArgs 
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = c3_mfma(af[i], bf[j], acc[i][j]);
+          for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(af[i], bf[j], acc[i][j]);
       }
     }
   }

@@ -26,10 +26,9 @@
 // 16*NXT + 6 are read by the K = 32 window of the last x tile: they are zeroed once per launch (A is zero there, but
 // 0 * garbage must not be NaN).
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "../../include/vsx.h"
 
-typedef __attribute__((ext_vector_type(4))) float dwm_f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 dwm_bf16x8;
 
 constexpr int DWM_THREADS = 1024;
 constexpr int DWM_CB = 32;      // channels per slab
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(DWM_THREADS) void dwconv7_mfma_kernel(const bf16_t*
     wsm[i] = c_base + cl < C ? w[(size_t)tap * C + c_base + cl] : 0.f;
   }
   __syncthreads();
-  dwm_bf16x8 afrag[CPW][7];
+  mf_bf16x8 afrag[CPW][7];
   float bias_v[CPW];
 #pragma unroll
   for (int cc = 0; cc < CPW; ++cc) {
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(DWM_THREADS) void dwconv7_mfma_kernel(const bf16_t*
         pk[e2] = f32x2_to_bf16x2_bits(v[0], v[1]);
       }
       uint4 q = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-      afrag[cc][ky] = __builtin_bit_cast(dwm_bf16x8, q);
+      afrag[cc][ky] = __builtin_bit_cast(mf_bf16x8, q);
     }
   }
 
@@ -201,15 +200,15 @@ __global__ __launch_bounds__(DWM_THREADS) void dwconv7_mfma_kernel(const bf16_t*
     for (int cc = 0; cc < CPW; ++cc) {
       const int chl = wave * CPW + cc;
       const unsigned short* plane = &lds[cur][dwm_plane_base(chl, G::PLANE)];
-      dwm_f32x4 acc[NXT];
+      mf_f32x4 acc[NXT];
 #pragma unroll
-      for (int xt = 0; xt < NXT; ++xt) acc[xt] = dwm_f32x4{bias_v[cc], bias_v[cc], bias_v[cc], bias_v[cc]};
+      for (int xt = 0; xt < NXT; ++xt) acc[xt] = mf_f32x4{bias_v[cc], bias_v[cc], bias_v[cc], bias_v[cc]};
 #pragma unroll
       for (int ky = 0; ky < 7; ++ky) {
 #pragma unroll
         for (int xt = 0; xt < NXT; ++xt) {
           const uint4 q = *reinterpret_cast<const uint4*>(plane + (p16 + ky) * G::PITCH + xt * 16 + kq * 8);
-          acc[xt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[cc][ky], __builtin_bit_cast(dwm_bf16x8, q), acc[xt], 0, 0, 0);
+          acc[xt] = mfma16(afrag[cc][ky], __builtin_bit_cast(mf_bf16x8, q), acc[xt]);
         }
       }
       // D: lane (row j = p16, columns kq*4 .. +3) -> the channel's own plane, row j, tile-local column
@@ -297,22 +296,9 @@ struct DwdGeom {
   static_assert(256 * PP == THREADS, "one output piece per thread");
 };
 
-// One wave-wide DMA piece: lane l's 16 bytes at `gsrc` land at LDS byte address lds_base + l * 16 (lds_base wave-uniform).  Issued
-// as inline assembly ON PURPOSE: hipcc puts `s_waitcnt vmcnt(0)` in front of LDS reads behind a `__builtin_amdgcn_global_load_lds`
-// whenever it cannot prove which LDS object the DMA writes (it could not here), which serialises the prefetch; this kernel counts
-// its own waits (dwd_wait_older_than) and orders LDS traffic with raw barriers.
-static __device__ __forceinline__ void dwd_dma16(const void* gsrc, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_base) : "memory", "m0");
-}
-static __device__ __forceinline__ uint32_t dwd_lds_addr(const void* p) {
-  return (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-// LDS traffic of this wave done, then the workgroup barrier — WITHOUT the vmcnt(0) a __syncthreads() carries
-static __device__ __forceinline__ void dwd_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// The DMA pieces go out in the raw form (lds_dma16_raw, mfma16.h): hipcc could not prove which LDS object the builtin's DMA writes
+// here and drained vmcnt(0) in front of the plane reads.  This kernel counts its own waits (wait_older_than) and orders LDS traffic
+// with barrier_lds().
 
 static __device__ __forceinline__ int dwd_plane_base(int ch) { return ch * DWD_PLANE + (ch >> 3) * 16; }
 
@@ -342,16 +328,15 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
   const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int p16 = lane & 15, kq = lane >> 4;
+  const MfLane ln = mf_lane(tid);  // the operand and C / D maps of lane (p16, kq): mfma16.h
+  const int lane = ln.lane, wave = ln.wave, p16 = ln.p16, kq = ln.kq;
 
   for (int i = tid; i < 49 * CB; i += THREADS) {
     const int tap = i / CB, cl = i - tap * CB;
     wsm[i] = w[(size_t)tap * C + c_base + cl];
   }
   __syncthreads();
-  dwm_bf16x8 afrag[CPW][7];
+  mf_bf16x8 afrag[CPW][7];
   float bias_v[CPW];
 #pragma unroll
   for (int cc = 0; cc < CPW; ++cc) {
@@ -375,7 +360,7 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
         pk[e2] = f32x2_to_bf16x2_bits(v[0], v[1]);
       }
       uint4 q = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-      afrag[cc][ky] = __builtin_bit_cast(dwm_bf16x8, q);
+      afrag[cc][ky] = __builtin_bit_cast(mf_bf16x8, q);
     }
   }
   {  // pad columns of the planes: read by the K = 32 window, multiplied by zeros of A, must be finite; never written afterwards
@@ -447,14 +432,14 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
         const int gy = at.y0 + (int)((xrc >> (16 * it + 8)) & 0xff) - 3, gx = at.x0 + (int)((xrc >> (16 * it)) & 0xff) - 3;
         const bool in = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
         const char* src = in ? xt + xbyte[it] : zsrc + ocv * 16;
-        dwd_dma16(src, dst + (wave + G::NW * it) * 1024);
+        lds_dma16_raw(src, dst + (wave + G::NW * it) * 1024);
       }
     }
   };
   auto issue_add = [&](const TileAt& at, uint32_t dst) {
     const bool in = at.y0 + orow < H && at.x0 + ocol < W;
     const char* src = in ? reinterpret_cast<const char*>(add + tile_origin(at)) + obyte : zsrc + ocv * 16;
-    dwd_dma16(src, dst + wave * 1024);
+    lds_dma16_raw(src, dst + wave * 1024);
   };
   auto transpose_in = [&](const char* rawb) {
 #pragma unroll
@@ -476,30 +461,30 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
   };
   auto wait_older_than = [&](int n) {  // every vector-memory operation but the n youngest has completed (n is wave-uniform)
     static_assert(G::XIT <= 2, "the wait below knows 0 .. 3 pieces in flight");
-    if (n >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (n >= 3) wait_vm<3>();
+    else if (n == 2) wait_vm<2>();
+    else if (n == 1) wait_vm<1>();
+    else wait_vm<0>();
   };
 
   // one tile: `rawc` / `addc` hold tile t (complete for this wave since the previous iteration's wait), `rawn` / `addn` receive
   // tile t + 1's shortcut operand now and tile t + 2's halo tile once rawc has been transposed
   auto tile_step = [&](int t, const TileAt& at, const TileAt& at1, const TileAt& at2, char* rawc, char* addc, char* addn) {
-    dwd_barrier();                                    // A: gather(t - 1) done by everyone; everyone's pieces of tile t landed
+    barrier_lds();                                    // A: gather(t - 1) done by everyone; everyone's pieces of tile t landed
     const bool more1 = t + 1 < t_end, more2 = t + 2 < t_end;
-    if (add && more1) issue_add(at1, dwd_lds_addr(addn));
+    if (add && more1) issue_add(at1, lds_addr(addn));
     transpose_in(rawc);
-    dwd_barrier();                                    // D: planes complete; rawc free
-    if (more2) issue_x(at2, dwd_lds_addr(rawc));
+    barrier_lds();                                    // D: planes complete; rawc free
+    if (more2) issue_x(at2, lds_addr(rawc));
 #pragma unroll
     for (int cc = 0; cc < CPW; ++cc) {
       const int chl = wave * CPW + cc;
       unsigned short* plane = &planes[dwd_plane_base(chl)];
-      dwm_f32x4 acc = dwm_f32x4{bias_v[cc], bias_v[cc], bias_v[cc], bias_v[cc]};
+      mf_f32x4 acc = mf_f32x4{bias_v[cc], bias_v[cc], bias_v[cc], bias_v[cc]};
 #pragma unroll
       for (int ky = 0; ky < 7; ++ky) {
         const uint4 q = *reinterpret_cast<const uint4*>(plane + (p16 + ky) * DWD_PITCH + kq * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[cc][ky], __builtin_bit_cast(dwm_bf16x8, q), acc, 0, 0, 0);
+        acc = mfma16(afrag[cc][ky], __builtin_bit_cast(mf_bf16x8, q), acc);
       }
       uint2 o;
       o.x = f32x2_to_bf16x2_bits(acc[0], acc[1]);
@@ -511,7 +496,7 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
     // and, issued BEFORE the halo pieces of t + 1?  No: order of issue is add(t+1) [this iteration], x(t+2) [this iteration];
     // x(t+1) and add(t) are older.  add(t+1) is needed by the NEXT gather only, so it may stay in flight as well.
     wait_older_than((add && more1 ? 1 : 0) + (more2 ? nx : 0));
-    dwd_barrier();                                    // H: every plane holds its channel's outputs
+    barrier_lds();                                    // H: every plane holds its channel's outputs
     const int cv = ocv, col = ocol, row = orow;
     const int gy = at.y0 + row, gx = at.x0 + col;
     if (gy < H && gx < W) {
@@ -535,9 +520,9 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
 
   TileAt a0 = tile_first(t_begin), a1 = tile_next(a0), a2 = tile_next(a1);
   __syncthreads();                                    // pad zeroing done (no DMA in flight yet)
-  issue_x(a0, dwd_lds_addr(raw0));
-  if (add) issue_add(a0, dwd_lds_addr(radd0));
-  if (t_begin + 1 < t_end) issue_x(a1, dwd_lds_addr(raw1));
+  issue_x(a0, lds_addr(raw0));
+  if (add) issue_add(a0, lds_addr(radd0));
+  if (t_begin + 1 < t_end) issue_x(a1, lds_addr(raw1));
   wait_older_than(t_begin + 1 < t_end ? nx : 0);      // tile t_begin complete for this wave
   for (int t = t_begin; t < t_end; t += 2) {
     tile_step(t, a0, a1, a2, raw0, radd0, radd1);
@@ -564,12 +549,11 @@ __global__ __launch_bounds__(CB * 32, CB == 16 ? 4 : 1) void dwconv7_mfma_dma_ke
 // registers for the whole launch; the diagonals are extracted once, at the end, through LDS atomics into one workspace
 // row per tile range — no global atomics, a fixed summation order.
 // Both operands are row-major [row][x] planes whose fragments run along the contraction (row) axis: they are fetched
-// with the gfx950 transpose read ds_read_b64_tr_b16 (lane (r, cseg) of a 16-lane group supplies the address of 4
-// contiguous columns of row r; lane l receives column l & 15 of the group's 4 rows) — the shift by ky is a row offset of
+// with the gfx950 transpose read ds_read_b64_tr_b16 (lds_tr4, mfma16.h: lane (r, cseg) of a 16-lane group supplies the address
+// of 4 contiguous columns of row r; lane l receives column l & 15 of the group's 4 rows) — the shift by ky is a row offset of
 // the address, never a misaligned access.  Same persistent 16-wave workgroups and 2-byte LDS transposition as the forward;
 // one LDS buffer (in + dy planes of 32 channels = 117 KB), the next tile's global loads are in flight under the MFMAs.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef short dwm_s16x4 __attribute__((ext_vector_type(4)));
 constexpr int DWM_WPITCH = 48;  // elements per plane row: tr reads of 4 rows x 16 columns (and of the paired group) hit distinct banks
 
 template <int NXT>
@@ -655,12 +639,9 @@ __global__ __launch_bounds__(DWM_THREADS) void dwconv7_wgrad_mfma_kernel(const b
     }
   };
 
-  dwm_f32x4 acc[2][8];
-#pragma unroll
-  for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[cc][k] = dwm_f32x4{0.f, 0.f, 0.f, 0.f};
-  const dwm_s16x4 ones = {(short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80};
+  mf_f32x4 acc[2][8];
+  mfma_zero(acc);
+  const mf_s16x4 ones = mf_ones4();
 
   load_tile(t_begin);
   __syncthreads();
@@ -675,15 +656,10 @@ __global__ __launch_bounds__(DWM_THREADS) void dwconv7_wgrad_mfma_kernel(const b
       const unsigned short* dp = dl + dwm_plane_base(chl, DPLANE) + (kq * 4 + tr_r) * P + tr_c;
 #pragma unroll
       for (int vb = 0; vb < TW; vb += 8) {
-        const dwm_s16x4 bfr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) dwm_s16x4*)(dp + vb));
-        acc[cc][7] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ones, bfr, acc[cc][7], 0, 0, 0);
+        const mf_s16x4 bfr = lds_tr4(dp + vb);
+        acc[cc][7] = mfma16_k16(ones, bfr, acc[cc][7]);
 #pragma unroll
-        for (int ky = 0; ky < 7; ++ky) {
-          const dwm_s16x4 afr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) dwm_s16x4*)(xp + ky * P + vb));
-          acc[cc][ky] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(afr, bfr, acc[cc][ky], 0, 0, 0);
-        }
+        for (int ky = 0; ky < 7; ++ky) acc[cc][ky] = mfma16_k16(lds_tr4(xp + ky * P + vb), bfr, acc[cc][ky]);
       }
     }
     __syncthreads();  // planes are rewritten by the next tile

@@ -11,11 +11,8 @@
 // fused epilogues (bias, GELU + GRN sum-of-squares, residual, IN statistics …) run on row-contiguous
 // 16-byte vectors and HBM stores are fully coalesced.
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "../../include/vsx.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 bool vsx_gemm_nt2_ok(const VsxGemm* p);           // gemm_nt2.hip
 bool vsx_gemm_nt2_lnbwd_ok(const VsxGemm* p);
@@ -98,34 +95,14 @@ __device__ __forceinline__ typename VT<T>::vec apply_prologue(const VsxGemm& p, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// MFMA fragments
+// MFMA fragments (Frag<T>, mfma16 and the lane map: mfma16.h)
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-struct Frag;
-template <>
-struct Frag<bf16_t> {
-  typedef bf16x8 type;
-  static constexpr int MK = 32;
-};
-template <>
-struct Frag<float> {
-  typedef float type;
-  static constexpr int MK = 4;
-};
-
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const float& a, const float& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // fragment of a [rows][k] (k contiguous) LDS tile, row stride RS bytes; kk = MFMA sub-step inside BK
 template <typename T>
 __device__ __forceinline__ typename Frag<T>::type lds_frag_rk(const char* tile, int row, int RS, int kk, int kq);
 template <>
-__device__ __forceinline__ bf16x8 lds_frag_rk<bf16_t>(const char* tile, int row, int RS, int kk, int kq) {
-  return *reinterpret_cast<const bf16x8*>(tile + row * RS + kk * 64 + kq * 16);
+__device__ __forceinline__ mf_bf16x8 lds_frag_rk<bf16_t>(const char* tile, int row, int RS, int kk, int kq) {
+  return *reinterpret_cast<const mf_bf16x8*>(tile + row * RS + kk * 64 + kq * 16);
 }
 template <>
 __device__ __forceinline__ float lds_frag_rk<float>(const char* tile, int row, int RS, int kk, int kq) {
@@ -219,11 +196,8 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 1) void gemm_nt_kernel(const V
     }
   };
 
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[FM][FN];
+  mfma_zero(acc);
 
   auto compute = [&](int buf) {
     const char* As = smem + buf * (BM + BN) * RS;
@@ -606,11 +580,8 @@ __global__ __launch_bounds__(256, BM == 256 ? 2 : ((BK == 64 && NBUF == 1) ? 3 :
     }
   };
 
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[FM][FN];
+  mfma_zero(acc);
   const int fragA = (wm * FM * 16 + p16) * RS, fragB = BM * RS + (wn * FN * 16 + p16) * RS;
   auto compute = [&](int buf) {
     const char* S = smem + buf * STAGE;
@@ -976,29 +947,18 @@ extern "C" int32_t vsx_gemm_nt_ln_bwd_supported(int64_t M, int32_t N, int32_t K,
 // gemm_tn : W[n][k] += sum_m X[m][n] * Y[m][k]
 // LDS tiles keep the natural [m][n] / [m][k] layout; the MFMA operands need 8 consecutive
 // contraction (m) values per lane, which gfx950's ds_read_b64_tr_b16 delivers straight from a
-// row-major tile (TR = true).  TR = false is the scalar-read fallback, also used for fp32.
-// k-slot ↔ m mapping inside a 32-row step (bf16): slot (kq, j) ↔ m = kq*4 + j (j < 4), 16 + kq*4 + j - 4.
+// row-major tile (TR = true: lds_tr8, whose comment in mfma16.h has the k-slot <-> m mapping of a 32-row step).
+// TR = false is the scalar-read fallback with the same mapping, also used for fp32.
 // ------------------------------------------------------------------------------------------------
 template <bool TR>
-__device__ __forceinline__ bf16x8 lds_frag_mn_bf16(const char* tile, int LDB, int col0, int p16, int kq) {
+__device__ __forceinline__ mf_bf16x8 lds_frag_mn_bf16(const char* tile, int LDB, int col0, int p16, int kq) {
   // tile: [32][LD] bf16, LDB = row stride bytes; returns the fragment for column col0 + p16
   if (TR) {
-    const int q = p16;
-    const char* a0 = tile + (kq * 4 + (q >> 2)) * LDB + (col0 + (q & 3) * 4) * 2;
-    const char* a1 = a0 + 16 * LDB;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a1));
-    union {
-      struct { s16x4 lo, hi; } s;
-      bf16x8 v;
-    } u;
-    u.s.lo = lo;
-    u.s.hi = hi;
-    return u.v;
+    return lds_tr8(tile, LDB, col0, p16, kq);
   } else {
     union {
       unsigned short h[8];
-      bf16x8 v;
+      mf_bf16x8 v;
     } u;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -1013,11 +973,11 @@ template <typename T, bool TR>
 __device__ __forceinline__ typename Frag<T>::type lds_frag_mn(const char* tile, int LDB, int col0, int p16, int kq,
                                                               int kk);
 template <>
-__device__ __forceinline__ bf16x8 lds_frag_mn<bf16_t, true>(const char* t, int LDB, int c0, int p16, int kq, int) {
+__device__ __forceinline__ mf_bf16x8 lds_frag_mn<bf16_t, true>(const char* t, int LDB, int c0, int p16, int kq, int) {
   return lds_frag_mn_bf16<true>(t, LDB, c0, p16, kq);
 }
 template <>
-__device__ __forceinline__ bf16x8 lds_frag_mn<bf16_t, false>(const char* t, int LDB, int c0, int p16, int kq, int) {
+__device__ __forceinline__ mf_bf16x8 lds_frag_mn<bf16_t, false>(const char* t, int LDB, int c0, int p16, int kq, int) {
   return lds_frag_mn_bf16<false>(t, LDB, c0, p16, kq);
 }
 template <>
@@ -1138,11 +1098,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const VsxGemm p, int rows_
     }
   };
 
-  f32x4 acc[F][F];
-#pragma unroll
-  for (int i = 0; i < F; ++i)
-#pragma unroll
-    for (int j = 0; j < F; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[F][F];
+  mfma_zero(acc);
   float csum = 0.f;  // bias-gradient partial for column n0 + tid (tile_k == 0 blocks only)
   const bool do_colsum = p.colsum != nullptr && tile_k == 0 && tid < BT;
 
@@ -1342,16 +1299,13 @@ __global__ __launch_bounds__(256, (BTK_ != 0 || PRO == 2) ? 2 : ((BMS == 64 && T
     }
   };
 
-  f32x4 acc[FN_][FK_];
-#pragma unroll
-  for (int i = 0; i < FN_; ++i)
-#pragma unroll
-    for (int j = 0; j < FK_; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[FN_][FK_];
+  mfma_zero(acc);
   float csum = 0.f;
   const bool do_colsum = p.colsum != nullptr && tile_k == 0 && tid < BTN;
-  f32x4 acc2[PRO == 2 ? FN_ : 1][PRO == 2 ? FK_ : 1];
+  mf_f32x4 acc2[PRO == 2 ? FN_ : 1][PRO == 2 ? FK_ : 1];
   float sreg[PRO == 2 ? FK_ : 1];
-  f32x4 acc1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // PRO == 2: column sums of X (fragments 2 wk, 2 wk + 1 of this wave's rows)
+  mf_f32x4 acc1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // PRO == 2: column sums of X (fragments 2 wk, 2 wk + 1 of this wave's rows)
   frag_t ones_frag;
   const bool want_p = PRO == 2 && p.aux != nullptr && p.red0 != nullptr;
   if constexpr (PRO == 2) {
@@ -1359,10 +1313,7 @@ __global__ __launch_bounds__(256, (BTK_ != 0 || PRO == 2) ? 2 : ((BMS == 64 && T
 #pragma unroll
     for (int j = 0; j < 8; ++j) one.h[j] = 0x3F80;
     ones_frag = one.v;
-#pragma unroll
-    for (int i = 0; i < FN_; ++i)
-#pragma unroll
-      for (int j = 0; j < FK_; ++j) acc2[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    mfma_zero(acc2);
     if (want_p) {
       const unsigned short* W2 = reinterpret_cast<const unsigned short*>(p.aux);
 #pragma unroll

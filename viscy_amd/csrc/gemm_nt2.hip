@@ -31,10 +31,8 @@
 // Dispatch (gemm.hip: vsx_gemm_nt): bf16, VSX_A_ROWS on both sides, no operand prologue, K % 32 == 0, M % 256 == 0,
 // hw % 64 == 0 where an epilogue is per sample; everything else stays on the first-generation kernels.
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "../../include/vsx.h"
-
-typedef __attribute__((ext_vector_type(4))) float nt2_f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 nt2_bf16x8;
 
 namespace {
 
@@ -66,6 +64,7 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
   constexpr int PRO_FLOATS = PRO ? 2 * 3072 : 4;   // s[b, :K] then beta[:K], K <= 3072
   __shared__ __attribute__((aligned(1024))) char smem[G::LDS_BYTES];
   __shared__ __attribute__((aligned(16))) float gsb[PRO_FLOATS];
+  // (mf_lane(tid) of mfma16.h, spelled out: through the struct hipcc orders the prologue's address arithmetic differently)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
@@ -101,13 +100,9 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
     const char* Ak = Ab + (size_t)kt * ROWB;
     const char* Bk = Bb + (size_t)kt * ROWB;
 #pragma unroll
-    for (int i = 0; i < G::NPA; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Ak + offA[i]),
-                                       (__attribute__((address_space(3))) void*)(S + (wave + 8 * i) * 1024), 16, 0, 0);
+    for (int i = 0; i < G::NPA; ++i) lds_dma16(Ak + offA[i], S + (wave + 8 * i) * 1024);
 #pragma unroll
-    for (int i = 0; i < G::NPB; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Bk + offB[i]),
-                                       (__attribute__((address_space(3))) void*)(S + A_BYTES + (wave + 8 * i) * 1024), 16, 0, 0);
+    for (int i = 0; i < G::NPB; ++i) lds_dma16(Bk + offB[i], S + A_BYTES + (wave + 8 * i) * 1024);
   };
 
   if constexpr (PRO) {
@@ -123,18 +118,13 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
     for (int c = wave; c * 64 < p.K; c += 8) {
       int i = c * 64 + lane;
       i = i < p.K ? i : p.K - 1;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gs + i),
-                                       (__attribute__((address_space(3))) void*)(gsb + c * 64), 4, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.grn_b + i),
-                                       (__attribute__((address_space(3))) void*)(gsb + 3072 + c * 64), 4, 0, 0);
+      lds_dma4(gs + i, gsb + c * 64);
+      lds_dma4(p.grn_b + i, gsb + 3072 + c * 64);
     }
   }
 
-  nt2_f32x4 acc[4][FN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (nt2_f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[4][FN];
+  mfma_zero(acc);
 
   // fragment addresses: lane (p16, kq) reads chunk kq of row (.. + p16) at position kq ^ swz(p16)
   const int fpos = (kq ^ ((p16 >> 2) & 2)) * 16;
@@ -142,9 +132,9 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
   const int fragB = A_BYTES + (wn * WN + p16) * ROWB + fpos;
   auto compute = [&](int st, int kt) {
     const char* S = smem + st * STAGE;
-    nt2_bf16x8 af[4];
+    mf_bf16x8 af[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const nt2_bf16x8*>(S + fragA + i * 16 * ROWB);
+    for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const mf_bf16x8*>(S + fragA + i * 16 * ROWB);
     if constexpr (PRO) {
       // lane (p16, kq) holds k = kt * 32 + kq * 8 .. + 7 of its rows
       const float* sp = gsb + kt * BK + kq * 8;
@@ -158,19 +148,19 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
         unpack<bf16_t>(__builtin_bit_cast(uint4, af[i]), f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], sv[e], bv[e]);
-        af[i] = __builtin_bit_cast(nt2_bf16x8, pack<bf16_t>(f));
+        af[i] = __builtin_bit_cast(mf_bf16x8, pack<bf16_t>(f));
       }
     }
 #pragma unroll
     for (int jg = 0; jg < FN; jg += 4) {  // B fragments four at a time (register budget of the 12-fragment geometry)
-      nt2_bf16x8 bf[4];
+      mf_bf16x8 bf[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const nt2_bf16x8*>(S + fragB + (jg + j) * 16 * ROWB);
+      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const mf_bf16x8*>(S + fragB + (jg + j) * 16 * ROWB);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][jg + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][jg + j], 0, 0, 0);
+          acc[i][jg + j] = mfma16(af[i], bf[j], acc[i][jg + j]);
     }
   };
 
@@ -215,13 +205,8 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
   int st = 0, stn = NST - 1;
   for (int kt = 0; kt < nk; ++kt) {
     // slab kt has landed for this wave (its pieces are the oldest outstanding); slab kt + 1 may still be in flight
-    if (kt + 1 < nk) {
-      if constexpr (G::PER_SLAB == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else if constexpr (G::PER_SLAB == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (kt + 1 < nk) wait_vm<G::PER_SLAB>();
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();  // ... for every wave; and every wave is done reading the stage that is refilled next
     if (kt + 2 < nk) issue(kt + 2, stn);
     if (RES_INLOOP && kt == nk - 3) res_prologue();
@@ -229,7 +214,9 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
     st = st == NST - 1 ? 0 : st + 1;
     stn = stn == NST - 1 ? 0 : stn + 1;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  // (the two halves of barrier_lds() without its compiler fence, here and below: with the fence hipcc no longer sinks the s_barrier
+  // under the epilogue's first address arithmetic)
+  wait_lgkm0();
   __builtin_amdgcn_s_barrier();  // the operand stages are dead: the staging patches overlay them
   if (RES && !RES_INLOOP) res_prologue();
 
@@ -357,7 +344,7 @@ __global__ __launch_bounds__(512, Nt2Geom<BN>::WAVES_PER_SIMD) void gemm_nt2_ker
 
   if constexpr (REDUCE) {
     if (p.hw % BM == 0) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm0();
       __builtin_amdgcn_s_barrier();
       if (tid < BN && n0 + tid < p.N) {
         const int w0 = tid / WN, c = tid % WN;  // N-half, column inside it
@@ -403,9 +390,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt2_lnbwd_kernel(const VsxGemm p)
   typedef Nt2Geom<BN> G;
   constexpr int FN = BN / 16, A_BYTES = G::A_BYTES, STAGE = G::STAGE, NCG = BN / 64;
   __shared__ __attribute__((aligned(1024))) char smem[G::LDS_BYTES];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int p16 = lane & 15, kq = lane >> 4;
+  const int tid = threadIdx.x;
+  const MfLane ln = mf_lane(tid);  // the operand and C / D maps of lane (p16, kq): mfma16.h
+  const int lane = ln.lane, wave = ln.wave, p16 = ln.p16, kq = ln.kq;
   int bid = blockIdx.x;
   const int m0 = bid * BM;
   NT2_STAMP(0);
@@ -428,38 +415,31 @@ __global__ __launch_bounds__(512, 2) void gemm_nt2_lnbwd_kernel(const VsxGemm p)
     const char* Ak = Ab + (size_t)kt * ROWB;
     const char* Bk = Bb + (size_t)kt * ROWB;
 #pragma unroll
-    for (int i = 0; i < G::NPA; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Ak + offA[i]),
-                                       (__attribute__((address_space(3))) void*)(S + (wave + 8 * i) * 1024), 16, 0, 0);
+    for (int i = 0; i < G::NPA; ++i) lds_dma16(Ak + offA[i], S + (wave + 8 * i) * 1024);
 #pragma unroll
-    for (int i = 0; i < G::NPB; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Bk + offB[i]),
-                                       (__attribute__((address_space(3))) void*)(S + A_BYTES + (wave + 8 * i) * 1024), 16, 0, 0);
+    for (int i = 0; i < G::NPB; ++i) lds_dma16(Bk + offB[i], S + A_BYTES + (wave + 8 * i) * 1024);
   };
 
-  nt2_f32x4 acc[2][FN];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (nt2_f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[2][FN];
+  mfma_zero(acc);
   const int fpos = (kq ^ ((p16 >> 2) & 2)) * 16;
   const int fragA = (wave * 32 + p16) * ROWB + fpos;
   const int fragB = A_BYTES + p16 * ROWB + fpos;
   auto compute = [&](int st) {
     const char* S = smem + st * STAGE;
-    nt2_bf16x8 af[2];
+    mf_bf16x8 af[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const nt2_bf16x8*>(S + fragA + i * 16 * ROWB);
+    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const mf_bf16x8*>(S + fragA + i * 16 * ROWB);
 #pragma unroll
     for (int jg = 0; jg < FN; jg += 4) {
-      nt2_bf16x8 bf[4];
+      mf_bf16x8 bf[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const nt2_bf16x8*>(S + fragB + (jg + j) * 16 * ROWB);
+      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const mf_bf16x8*>(S + fragB + (jg + j) * 16 * ROWB);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][jg + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][jg + j], 0, 0, 0);
+          acc[i][jg + j] = mfma16(af[i], bf[j], acc[i][jg + j]);
     }
   };
 
@@ -495,12 +475,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt2_lnbwd_kernel(const VsxGemm p)
   if (nk < 3) prefetch_rows();
   int st = 0, stn = NST - 1;
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) {
-      if constexpr (G::PER_SLAB == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (kt + 1 < nk) wait_vm<G::PER_SLAB>();
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     if (kt < 64) NT2_STAMP(8 + kt);
     if (kt + 2 < nk) issue(kt + 2, stn);
@@ -510,7 +486,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt2_lnbwd_kernel(const VsxGemm p)
     stn = stn == NST - 1 ? 0 : stn + 1;
   }
   NT2_STAMP(1);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm0();
   __builtin_amdgcn_s_barrier();
   NT2_STAMP(2);
 

@@ -7,6 +7,7 @@
 // lanes along x·z so both the 16-byte U reads and the 8-byte stores into the X-contiguous output
 // rows are coalesced.
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "../../include/vsx.h"
 
 #define HEAD_MAX_CMID 64
@@ -183,8 +184,6 @@ __global__ __launch_bounds__(256) void head_out_bwd1_kernel(const T* __restrict_
 // gradient through a ones column) in MFMA accumulators across the voxel loop.  The activation tensor ([M5, Cmid]: 2.7 GB per
 // step at B = 512) is never written and the separate skinny TN GEMM over it (M = 41.9 M, N = 8, K = 32: 2.3 ms at
 // 1.5 TB/s) disappears.  Per-sample partial sums go to dwp[b][CO4*CMID + CO4] with a few atomics per address.
-typedef __attribute__((ext_vector_type(4))) float head_f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 head_bf16x8;
 
 template <int CMID, int CO4>
 __global__ __launch_bounds__(256) void head_out_bwd1_wgrad_kernel(const bf16_t* __restrict__ U, const float* __restrict__ ssum,
@@ -216,12 +215,9 @@ __global__ __launch_bounds__(256) void head_out_bwd1_wgrad_kernel(const bf16_t* 
   const int H = 2 * d.H2, W = 2 * d.W2;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p16 = lane & 15, kq = lane >> 4;
-  head_f32x4 acc[NF + 1];
-#pragma unroll
-  for (int f = 0; f <= NF; ++f) acc[f] = (head_f32x4){0.f, 0.f, 0.f, 0.f};
-  const uint32_t one2 = p16 == 0 ? 0x3F803F80u : 0u;  // bf16 1.0 pairs: column 0 of the extra fragment sums dv (bias gradient)
-  const uint4 ones_bits = make_uint4(one2, one2, one2, one2);
-  const head_bf16x8 ones = *reinterpret_cast<const head_bf16x8*>(&ones_bits);
+  mf_f32x4 acc[NF + 1];
+  mfma_zero(acc);
+  const mf_bf16x8 ones = mf_ones8(p16 == 0);  // column 0 of the extra fragment sums dv (bias gradient)
   // per-lane partial sums of S1 = sum dn, S2 = sum dn * n^ and of the PReLU-slope gradient over this thread's voxels: reduced across
   // the wave ONCE after the voxel loop (the first version reduced every channel of every voxel row: 64 wave reductions of 6
   // dependent DPP operations per 64 voxels — 40 % of the kernel's VALU work)
@@ -282,14 +278,14 @@ __global__ __launch_bounds__(256) void head_out_bwd1_wgrad_kernel(const bf16_t* 
     __syncthreads();  // the wave's transposed rows are complete (block-wide barrier: trip counts are uniform)
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      head_bf16x8 af = *reinterpret_cast<const head_bf16x8*>(&dT[wv][p16 < CO4 ? p16 : 0][kb * 32 + kq * 8]);
-      if (p16 >= CO4) af = (head_bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      mf_bf16x8 af = *reinterpret_cast<const mf_bf16x8*>(&dT[wv][p16 < CO4 ? p16 : 0][kb * 32 + kq * 8]);
+      if (p16 >= CO4) af = mf_zero8();
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
-        const head_bf16x8 bf = *reinterpret_cast<const head_bf16x8*>(&aT[wv][f * 16 + p16][kb * 32 + kq * 8]);
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[f], 0, 0, 0);
+        const mf_bf16x8 bf = *reinterpret_cast<const mf_bf16x8*>(&aT[wv][f * 16 + p16][kb * 32 + kq * 8]);
+        acc[f] = mfma16(af, bf, acc[f]);
       }
-      acc[NF] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, ones, acc[NF], 0, 0, 0);
+      acc[NF] = mfma16(af, ones, acc[NF]);
     }
     __syncthreads();  // fragments read before the next iteration overwrites the rows
   }
@@ -411,7 +407,6 @@ __global__ __launch_bounds__(256) void head_out_bwd2_kernel(const T* __restrict_
 //     from row-major tiles (the U tile itself and the 16-byte dv rows) — the 2-byte transposing stores of the thread-per-voxel
 //     pass are gone;
 //   * S1 / S2 / dalpha partial sums live in the lane that owns the channel (8 per lane instead of 2 x Cmid per thread).
-typedef __attribute__((ext_vector_type(4))) short head_s16x4;
 constexpr int HR_TX = 64;
 #ifndef HR_DBG
 #define HR_DBG 0  // timing experiments (results wrong): 1 = no final atomics, 2 = no weight-gradient contraction, 4 = no per-voxel pass
@@ -444,23 +439,6 @@ __device__ __forceinline__ void hr_commit(const vsx_u32x4* regs, unsigned char* 
   }
 }
 
-__device__ __forceinline__ head_bf16x8 hr_pack8(const float* f) {
-  union { uint4 u; head_bf16x8 v; } t;
-  t.u = make_uint4(f32x2_to_bf16x2_bits(f[0], f[1]), f32x2_to_bf16x2_bits(f[2], f[3]), f32x2_to_bf16x2_bits(f[4], f[5]),
-                   f32x2_to_bf16x2_bits(f[6], f[7]));
-  return t.v;
-}
-
-// 8 voxels (contraction slots of a 32-row step, see gemm.hip lds_frag_mn_bf16) of column col0 + p16 out of a row-major LDS tile
-__device__ __forceinline__ head_bf16x8 hr_tr(const unsigned char* tile, int ldb, int col0, int p16, int kq) {
-  const unsigned char* a0 = tile + (kq * 4 + (p16 >> 2)) * ldb + (col0 + (p16 & 3) * 4) * 2;
-  const unsigned char* a1 = a0 + 16 * ldb;
-  union { struct { head_s16x4 lo, hi; } s; head_bf16x8 v; } u;
-  u.s.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((head_s16x4 __attribute__((address_space(3)))*)(a0));
-  u.s.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((head_s16x4 __attribute__((address_space(3)))*)(a1));
-  return u.v;
-}
-
 template <int CMID, int CO4>
 __global__ __launch_bounds__(512) void head_out_fwd_rows_kernel(const bf16_t* __restrict__ U, const float* __restrict__ ssum,
                                                                 const float* __restrict__ ssq, const float* __restrict__ w2,
@@ -482,7 +460,7 @@ __global__ __launch_bounds__(512) void head_out_fwd_rows_kernel(const bf16_t* __
   // A = W2 rows (m = output index), rows past CO4 zero, as TWO bf16 fragments hi + lo (lo = bf16(W2 - hi)): the weights enter with
   // 16 mantissa bits for one more MFMA per fragment on an idle pipe (bf16 weights alone moved the per-stage gradient error of the
   // bf16 engine from 0.6 - 0.9 x to 1.0 - 1.2 x the autocast yardstick of tests/test_gpu_model.py: every gradient passes here)
-  head_bf16x8 wf[KB], wl[KB];
+  mf_bf16x8 wf[KB], wl[KB];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
     float t[8], tl[8];
@@ -491,8 +469,8 @@ __global__ __launch_bounds__(512) void head_out_fwd_rows_kernel(const bf16_t* __
       t[j] = p16 < CO4 ? w2[p16 * CMID + kb * 32 + kq * 8 + j] : 0.f;
       tl[j] = t[j] - round_bf16(t[j]);
     }
-    wf[kb] = hr_pack8(t);
-    wl[kb] = hr_pack8(tl);
+    wf[kb] = mf_pack8(t);
+    wl[kb] = mf_pack8(tl);
   }
   float bias[4];
 #pragma unroll
@@ -512,7 +490,7 @@ __global__ __launch_bounds__(512) void head_out_fwd_rows_kernel(const bf16_t* __
 #pragma unroll
   for (int xb = 0; xb < HR_TX / 16; ++xb) {
     const unsigned char* row = tile + ((xb * 16 + p16) * Z + z) * G::RP;
-    head_f32x4 acc = (head_f32x4){0.f, 0.f, 0.f, 0.f};
+    mf_f32x4 acc = (mf_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       float u[8];
@@ -522,9 +500,9 @@ __global__ __launch_bounds__(512) void head_out_fwd_rows_kernel(const bf16_t* __
         const float n = (u[j] - mc[kb][j]) * rc[kb][j];
         u[j] = n > 0.f ? n : alpha * n;
       }
-      const head_bf16x8 af = hr_pack8(u);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[kb], af, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kb], af, acc, 0, 0, 0);
+      const mf_bf16x8 af = mf_pack8(u);
+      acc = mfma16(wl[kb], af, acc);
+      acc = mfma16(wf[kb], af, acc);
     }
     if (kq * 4 < CO4) {
       const int x = x0 + xb * 16 + p16;
@@ -569,7 +547,7 @@ __global__ __launch_bounds__(512) void head_out_bwd2_rows_kernel(const bf16_t* _
   }
   // A = W2^T: lane (p16 = channel within the fragment, kq) holds W2[k = 8 kq + j][16 cb + p16], k >= CO4 zero
   // (hi + lo bf16 fragments: dv IS bf16, so dA = W2^T dv comes out as with fp32 weights — see the forward)
-  head_bf16x8 wf[NCB], wl[NCB];
+  mf_bf16x8 wf[NCB], wl[NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
     float t[8], tl[8];
@@ -578,8 +556,8 @@ __global__ __launch_bounds__(512) void head_out_bwd2_rows_kernel(const bf16_t* _
       t[j] = kq * 8 + j < CO4 ? w2[(kq * 8 + j) * CMID + cb * 16 + p16] : 0.f;
       tl[j] = t[j] - round_bf16(t[j]);
     }
-    wf[cb] = hr_pack8(t);
-    wl[cb] = hr_pack8(tl);
+    wf[cb] = mf_pack8(t);
+    wl[cb] = mf_pack8(tl);
   }
   const float alpha = alpha_p[0];
   hr_commit<CMID>(ureg, tile, tid, nt);
@@ -598,12 +576,12 @@ __global__ __launch_bounds__(512) void head_out_bwd2_rows_kernel(const bf16_t* _
   for (int xb = 0; xb < HR_TX / 16; ++xb) {
     const int rloc = (xb * 16 + p16) * Z + z;
     unsigned char* row = tile + rloc * G::RP;
-    union { uint4 u; head_bf16x8 v; } bv;
+    union { uint4 u; mf_bf16x8 v; } bv;
     bv.u = kq * 8 < CO4 ? *reinterpret_cast<const uint4*>(dvs + rloc * DVR + kq * 16) : make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-      head_f32x4 dA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[cb], bv.v, (head_f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      dA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[cb], bv.v, dA, 0, 0, 0);
+      mf_f32x4 dA = mfma16(wl[cb], bv.v, (mf_f32x4){0.f, 0.f, 0.f, 0.f});
+      dA = mfma16(wf[cb], bv.v, dA);
       uint2* up = reinterpret_cast<uint2*>(row + (cb * 16 + kq * 4) * 2);
       const uint2 uu = *up;
       const float u[4] = {bf16_bits_to_f32(uu.x & 0xFFFFu), bf16_bits_to_f32(uu.x >> 16), bf16_bits_to_f32(uu.y & 0xFFFFu),
@@ -665,16 +643,15 @@ __device__ __forceinline__ void head_out_bwd1_rows_body(const bf16_t* __restrict
   const int p16 = lane & 15, kq = lane >> 4;
   head_load_stats(ssum, ssq, b, CMID, (float)d.Z * d.H2 * d.W2, eps, mu, rs);
   const float alpha = alpha_p[0];
-  const uint32_t one2 = p16 == 0 ? 0x3F803F80u : 0u;  // ones in column 0: the extra fragment sums dv over the voxels (bias gradient)
-  union { uint4 u; head_bf16x8 v; } ones;
+  // ones in column 0: the extra fragment sums dv over the voxels (bias gradient).  (mf_ones8(p16 == 0) spelled out: through the
+  // helper the CMID = 64 kernel allocates its registers differently)
+  const uint32_t one2 = p16 == 0 ? 0x3F803F80u : 0u;
+  union { uint4 u; mf_bf16x8 v; } ones;
   ones.u = make_uint4(one2, one2, one2, one2);
-  head_f32x4 accA[NF], accN[NF], accM[NF], accB = (head_f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    accA[f] = (head_f32x4){0.f, 0.f, 0.f, 0.f};
-    accN[f] = (head_f32x4){0.f, 0.f, 0.f, 0.f};
-    accM[f] = (head_f32x4){0.f, 0.f, 0.f, 0.f};
-  }
+  mf_f32x4 accA[NF], accN[NF], accM[NF], accB = (mf_f32x4){0.f, 0.f, 0.f, 0.f};
+  mfma_zero(accA);
+  mfma_zero(accN);
+  mfma_zero(accM);
   __syncthreads();
   float mc[NF], rc[NF];  // this lane's channel c = 16 f + p16
 #pragma unroll
@@ -728,12 +705,12 @@ __device__ __forceinline__ void head_out_bwd1_rows_body(const bf16_t* __restrict
       const unsigned char* v0 = dvt + ((kb * 32) * Z + z) * DVR;
       // every lane supplies its own slot address (the transposition takes column p16's values from the reads of the lanes
       // with (q & 3) == p16 / 4, whatever their own column); lanes past CO4 read into the next row and are zeroed
-      head_bf16x8 af = hr_tr(v0, Z * DVR, 0, p16, kq);
-      if (p16 >= CO4) af = (head_bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      mf_bf16x8 af = lds_tr8(v0, Z * DVR, 0, p16, kq);
+      if (p16 >= CO4) af = mf_zero8();
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
-        union { head_bf16x8 v; uint32_t w[4]; } raw, fa, fn, fm;
-        raw.v = hr_tr(t0, Z * G::RP, f * 16, p16, kq);
+        union { mf_bf16x8 v; uint32_t w[4]; } raw, fa, fn, fm;
+        raw.v = lds_tr8(t0, Z * G::RP, f * 16, p16, kq);
         if (!(HR_DBG & 4)) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -748,11 +725,11 @@ __device__ __forceinline__ void head_out_bwd1_rows_body(const bf16_t* __restrict
         } else {
           fa = raw; fn = raw; fm = raw;
         }
-        accA[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, fa.v, accA[f], 0, 0, 0);
-        accN[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, fn.v, accN[f], 0, 0, 0);
-        accM[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, fm.v, accM[f], 0, 0, 0);
+        accA[f] = mfma16(af, fa.v, accA[f]);
+        accN[f] = mfma16(af, fn.v, accN[f]);
+        accM[f] = mfma16(af, fm.v, accM[f]);
       }
-      accB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, ones.v, accB, 0, 0, 0);
+      accB = mfma16(af, ones.v, accB);
     }
     __syncthreads();  // dv rows of every wave are in LDS, every wave is done with the U tile
     {

@@ -10,36 +10,14 @@
 // Layouts (channels-last, as everywhere): hin [B*H2*W2, 7*8], U / dU [B*H2*W2, 5*32], W [32][27*8] with
 // k = ((dy*3 + dx)*3 + dz)*8 + c  (the VSX_A_CONV3 weight layout, so both paths share the prepared weights).
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "../../include/vsx.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 #define HC_C3 8
 #define HC_CMID 32
 #define HC_ZO 5
 #define HC_D7 7
 #define HC_K 216  // 27 * 8
-
-__device__ __forceinline__ f32x4 hc_mfma(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 hc_zero8() {
-  union { uint4 u; bf16x8 v; } t;
-  t.u = make_uint4(0u, 0u, 0u, 0u);
-  return t.v;
-}
-// 8 contraction values for one column out of a row-major LDS tile: two transposing 8-byte reads (rows r and r+16 of a
-// 32-row step); a0/a1 are THIS lane's addresses (see gemm.hip lds_frag_mn_bf16 for the slot mapping)
-__device__ __forceinline__ bf16x8 hc_tr(const char* a0, const char* a1) {
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a1));
-  union { struct { s16x4 lo, hi; } s; bf16x8 v; } u;
-  u.s.lo = lo;
-  u.s.hi = hi;
-  return u.v;
-}
 
 // ------------------------------------------------------------------------------------------------ forward
 // workgroup = 16x16 output pixels of one sample, all 5 planes; wave w owns pixel rows 4w..4w+3 (4 pixel fragments).
@@ -93,7 +71,7 @@ __global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __r
     }
   }
   // weights: 2 channel fragments x 7 K-steps (4 taps each; tap 27 does not exist -> zero), resident in registers
-  bf16x8 wf[2][7];
+  mf_bf16x8 wf[2][7];
   int toff[7];
 #pragma unroll
   for (int kk = 0; kk < 7; ++kk) {
@@ -104,7 +82,7 @@ __global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __r
     toff[kk] = (dy * 18 + dx) * HF_PS + dz * 16;
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf)
-      wf[nf][kk] = t < 27 ? *reinterpret_cast<const bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : hc_zero8();
+      wf[nf][kk] = t < 27 ? *reinterpret_cast<const mf_bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : mf_zero8();
   }
   float bs[2][4], s1[2][4], s2[2][4];
 #pragma unroll
@@ -122,12 +100,12 @@ __global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __r
     const int pbase = ((wave * 2 + mf) * 18 + p16) * HF_PS;
 #pragma unroll
     for (int z = 0; z < HC_ZO; ++z) {
-      f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+      mf_f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
       for (int kk = 0; kk < 7; ++kk) {
-        const bf16x8 pf = *reinterpret_cast<const bf16x8*>(tile + pbase + toff[kk] + z * 16);
+        const mf_bf16x8 pf = *reinterpret_cast<const mf_bf16x8*>(tile + pbase + toff[kk] + z * 16);
 #pragma unroll
-        for (int nf = 0; nf < 2; ++nf) acc[nf] = hc_mfma(wf[nf][kk], pf, acc[nf]);
+        for (int nf = 0; nf < 2; ++nf) acc[nf] = mfma16(wf[nf][kk], pf, acc[nf]);
       }
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf) {
@@ -227,7 +205,7 @@ __global__ __launch_bounds__(256, HCF_WPE) void head_conv_fwd_persist_kernel(con
     }
   };
   // weights: 2 channel fragments x 7 K-steps (4 taps each; tap 27 does not exist -> zero), resident in registers
-  bf16x8 wf[2][7];
+  mf_bf16x8 wf[2][7];
   int toff[7];
 #pragma unroll
   for (int kk = 0; kk < 7; ++kk) {
@@ -238,7 +216,7 @@ __global__ __launch_bounds__(256, HCF_WPE) void head_conv_fwd_persist_kernel(con
     toff[kk] = (dy * 18 + dx) * HF_PS + dz * 16;
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf)
-      wf[nf][kk] = t < 27 ? *reinterpret_cast<const bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : hc_zero8();
+      wf[nf][kk] = t < 27 ? *reinterpret_cast<const mf_bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : mf_zero8();
   }
   float bs[2][4];
 #pragma unroll
@@ -274,12 +252,12 @@ __global__ __launch_bounds__(256, HCF_WPE) void head_conv_fwd_persist_kernel(con
       const int pbase = ((wave * 2 + mf) * 18 + p16) * HF_PS;
 #pragma unroll
       for (int z = 0; z < HC_ZO; ++z) {
-        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        mf_f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int kk = 0; kk < 7; ++kk) {
-          const bf16x8 pf = *reinterpret_cast<const bf16x8*>(tile + pbase + toff[kk] + z * 16);
+          const mf_bf16x8 pf = *reinterpret_cast<const mf_bf16x8*>(tile + pbase + toff[kk] + z * 16);
 #pragma unroll
-          for (int nf = 0; nf < 2; ++nf) acc[nf] = hc_mfma(wf[nf][kk], pf, acc[nf]);
+          for (int nf = 0; nf < 2; ++nf) acc[nf] = mfma16(wf[nf][kk], pf, acc[nf]);
         }
 #pragma unroll
         for (int nf = 0; nf < 2; ++nf) {
@@ -351,11 +329,8 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const bf16_t* __re
   const int tiles_x = W2 / 16, tiles_y = H2 / 8;
   const int ntiles = B * tiles_y * tiles_x;
   // this wave's column fragments jf = wave, wave + 4, wave + 8, wave + 12 (< 14)
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[2][4];
+  mfma_zero(acc);
   // per-lane B-operand address pieces: column group cg = q & 3 -> 4 columns c = cg*4.. of the 16-column fragment:
   // c < 8 -> tap 2*jf, channels c..c+3; c >= 8 -> tap 2*jf + 1, channels c-8..
   const int slot = kq * 4 + (q >> 2);   // contraction slot (pixel within the first 16 of a 32-pixel step); +16 = next tile row
@@ -426,21 +401,21 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const bf16_t* __re
       const char* brow = hin_t + ((chunk * 2) * 18 + slot) * HF_PS;
 #pragma unroll
       for (int z = 0; z < HC_ZO; ++z) {
-        bf16x8 af[2], bfr[4];
+        mf_bf16x8 af[2], bfr[4];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) af[i] = hc_tr(arow + (z * 32 + i * 16) * 2, arow + 16 * HW_DS + (z * 32 + i * 16) * 2);
+        for (int i = 0; i < 2; ++i) af[i] = lds_tr8(arow + (z * 32 + i * 16) * 2, arow + 16 * HW_DS + (z * 32 + i * 16) * 2);
 #pragma unroll
         for (int jl = 0; jl < 4; ++jl) {
           // ONE transposing read for the whole wave (it exchanges data between lanes: never under divergent control flow);
           // lanes of the ones / zero columns just point at the constants
           const char* b0 = boff[jl] >= 0 ? brow + boff[jl] + z * 16 : (boff[jl] == -1 ? cptr1 : cptr0);
           const char* b1 = boff[jl] >= 0 ? b0 + 18 * HF_PS : b0;
-          bfr[jl] = hc_tr(b0, b1);
+          bfr[jl] = lds_tr8(b0, b1);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int jl = 0; jl < 4; ++jl) acc[i][jl] = hc_mfma(af[i], bfr[jl], acc[i][jl]);
+          for (int jl = 0; jl < 4; ++jl) acc[i][jl] = mfma16(af[i], bfr[jl], acc[i][jl]);
       }
     }
   }
@@ -494,15 +469,15 @@ __global__ void head_conv_dgrad_prep_kernel(const bf16_t* __restrict__ Wc, bf16_
 // first version had every wave fetch the fragments of every step from global memory — 360 KB of L1 traffic per workgroup for a
 // 58 KB halo tile: the pass ran at 2.5 TB/s of its bytes with the texture path busy on weights.
 template <int Z>
-__device__ __forceinline__ void hd_step(const char* halo, int pb, const char* wl, f32x4 (&acc)[2][4]) {
+__device__ __forceinline__ void hd_step(const char* halo, int pb, const char* wl, mf_f32x4 (&acc)[2][4]) {
   constexpr int FA = (Z & 1) ? (Z - 1) / 2 : Z / 2;
-  const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(wl + (Z * 2 + 0) * 1024);
-  const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(wl + (Z * 2 + 1) * 1024);
+  const mf_bf16x8 a0 = *reinterpret_cast<const mf_bf16x8*>(wl + (Z * 2 + 0) * 1024);
+  const mf_bf16x8 a1 = *reinterpret_cast<const mf_bf16x8*>(wl + (Z * 2 + 1) * 1024);
 #pragma unroll
   for (int mf = 0; mf < 2; ++mf) {
-    const bf16x8 pf = *reinterpret_cast<const bf16x8*>(halo + pb + mf * 18 * HD_PS);
-    acc[mf][FA] = hc_mfma(a0, pf, acc[mf][FA]);
-    acc[mf][FA + 1] = hc_mfma(a1, pf, acc[mf][FA + 1]);
+    const mf_bf16x8 pf = *reinterpret_cast<const mf_bf16x8*>(halo + pb + mf * 18 * HD_PS);
+    acc[mf][FA] = mfma16(a0, pf, acc[mf][FA]);
+    acc[mf][FA + 1] = mfma16(a1, pf, acc[mf][FA + 1]);
   }
 }
 
@@ -513,9 +488,9 @@ __global__ __launch_bounds__(256) void head_conv_dgrad_kernel(const bf16_t* __re
   __shared__ __attribute__((aligned(16))) char halo[10 * 18 * HD_PS];  // 60 KB
   __shared__ __attribute__((aligned(1024))) char wb0[10 * 1024];
   __shared__ __attribute__((aligned(1024))) char wb1[10 * 1024];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int p16 = lane & 15, kq = lane >> 4;
+  const int tid = threadIdx.x;
+  const MfLane ln = mf_lane(tid);  // the operand and C / D maps of lane (p16, kq): mfma16.h
+  const int lane = ln.lane, wave = ln.wave, p16 = ln.p16, kq = ln.kq;
   const int b = blockIdx.z, ty0 = blockIdx.y * 8, tx0 = blockIdx.x * 16;
   const size_t img = (size_t)b * H2 * W2;
   // the 10 KiB of tap `tap` -> buffer: pieces wave, wave + 4, wave + 8 (1 KiB = one wave instruction)
@@ -524,13 +499,8 @@ __global__ __launch_bounds__(256) void head_conv_dgrad_kernel(const bf16_t* __re
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int pc = wave + 4 * i;
-      // (inline assembly on purpose: behind the builtin hipcc drains vmcnt(0) in front of every LDS read whose object it cannot
-      // tell from the DMA's — here in every second tap — which serialises the prefetch; this kernel counts its own waits)
-      if (pc < 10) {
-        const char* src = wsrc + (size_t)(tap * 10 + pc) * 1024;
-        const uint32_t d = (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)(dst + pc * 1024);
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(d) : "memory", "m0");
-      }
+      // (the raw form: behind the builtin hipcc drains vmcnt(0) in every second tap, mfma16.h; this kernel counts its own waits)
+      if (pc < 10) lds_dma16_raw(wsrc + (size_t)(tap * 10 + pc) * 1024, lds_addr(dst + pc * 1024));
     }
   };
   wdma(0, wb0);
@@ -558,18 +528,15 @@ __global__ __launch_bounds__(256) void head_conv_dgrad_kernel(const bf16_t* __re
       }
     }
   }
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-    for (int f = 0; f < 4; ++f) acc[mf][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mf_f32x4 acc[2][4];
+  mfma_zero(acc);
   // wave w: output pixel rows 2w, 2w + 1; lane: pixel x = p16, channel quarter kq (8 of the 32 n per plane)
   const int pb0 = ((wave * 2) * 18 + p16) * HD_PS + kq * 16;
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
     // tap's weights (this wave's pieces: everything it has outstanding) and, at tap 0, the halo tile have landed for every wave;
     // every wave is done with the buffer that is refilled next
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm0_lgkm0();
     __builtin_amdgcn_s_barrier();
     if (tap + 1 < 9) wdma(tap + 1, (tap & 1) ? wb0 : wb1);
     const char* wl = ((tap & 1) ? wb1 : wb0) + lane * 16;

@@ -45,11 +45,9 @@
 //     the residual is read in the same 16-byte fragment layout as the input rows; the result leaves through a per-wave LDS
 //     transpose as one contiguous 16-byte-vector stream.
 #include "vsx_common.h"
+#include "mfma16.h"
 #include "wtasks.h"
 #include "../../include/vsx.h"
-
-typedef float mlp_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 mlp_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct MlpArgs {
   const bf16_t* xh;     // [M, C]  block LayerNorm output (affine folded into fc1)
@@ -104,10 +102,6 @@ __device__ __forceinline__ uint32_t mlp_relu_pair(uint32_t w) {
   typedef short mlp_s16x2 __attribute__((ext_vector_type(2)));
   const mlp_s16x2 z = {0, 0};
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(mlp_s16x2, w), z));
-}
-
-__device__ __forceinline__ mlp_f32x4 mlp_mfma(const mlp_bf16x8& a, const mlp_bf16x8& b, const mlp_f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 // MLP_TS (probe builds only: hipcc -DMLP_TS=1): s_memtime stamps of ONE workgroup's waves at the phase boundaries of every
@@ -170,9 +164,9 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
   __shared__ __attribute__((aligned(16))) char obuf[G::OUT_BYTES];
   __shared__ __attribute__((aligned(16))) float gt[G::GT_FLOATS];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int p16 = lane & 15, kq = lane >> 4;
+  const int tid = threadIdx.x;
+  const MfLane ln = mf_lane(tid);  // the operand and C / D maps of lane (p16, kq): mfma16.h
+  const int lane = ln.lane, wave = ln.wave, p16 = ln.p16, kq = ln.kq;
   const int m0 = blockIdx.x * G::BM;   // the tile lies inside one sample (dispatch: hw % BM == 0)
   const int b = m0 / a.hw;
   const int row0 = m0 + wave * WM;
@@ -249,21 +243,21 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
     }
   };
   // ---- this wave's LayerNorm rows as fc1 B fragments: lane (p, q) holds row p, k = kk*32 + q*8 .. +7
-  mlp_bf16x8 xf[MF][KK];
+  mf_bf16x8 xf[MF][KK];
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk)
-      xf[mf][kk] = *reinterpret_cast<const mlp_bf16x8*>(a.xh + (size_t)(row0 + mf * 16 + p16) * C + kk * 32 + kq * 8);
+      xf[mf][kk] = *reinterpret_cast<const mf_bf16x8*>(a.xh + (size_t)(row0 + mf * 16 + p16) * C + kk * 32 + kq * 8);
 
   // MODE 5: the normalised rows x^ as a second fragment set (operand of the recomputed fc1)
-  mlp_bf16x8 xg[RE ? MF : 1][RE ? KK : 1];
+  mf_bf16x8 xg[RE ? MF : 1][RE ? KK : 1];
   if constexpr (RE) {
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk)
-        xg[mf][kk] = *reinterpret_cast<const mlp_bf16x8*>(a.xh2 + (size_t)(row0 + mf * 16 + p16) * C + kk * 32 + kq * 8);
+        xg[mf][kk] = *reinterpret_cast<const mf_bf16x8*>(a.xh2 + (size_t)(row0 + mf * 16 + p16) * C + kk * 32 + kq * 8);
   }
   // MODE 7: x^ was never stored.  xg holds y: normalise it with the forward's own mean / rstd and the forward's expression
   // (bit-identical x^, hence bit-identical h).  dh leaves multiplied by the row's rstd, and the column sums of the parked tile
@@ -272,7 +266,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
   // gradient) and the row mean split into a bf16 head and tail (-> u = sum of dh' * mean to 2^-17, see vsx_mlp_bwd_dh_ln)
   setup_to_lds();   // (behind the row-fragment loads: everything is in flight together)
   float rsr[LNF ? MF : 1];
-  mlp_bf16x8 wS, wSl, wMh, wMl;
+  mf_bf16x8 wS, wSl, wMh, wMl;
   if constexpr (LNF) {
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf) {
@@ -281,7 +275,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
       rsr[mf] = rstd;
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
-        union { mlp_bf16x8 b; uint4 u; } cv;
+        union { mf_bf16x8 b; uint4 u; } cv;
         cv.b = xg[mf][kk];
         float v[8], o[8];
         unpack<bf16_t>(cv.u, v);
@@ -303,7 +297,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
       mh[j] = round_bf16(mean);
       ml[j] = mean - mh[j];
     }
-    union { mlp_bf16x8 b; uint4 u; } c1, c2, c3, c4;
+    union { mf_bf16x8 b; uint4 u; } c1, c2, c3, c4;
     c1.u = pack<bf16_t>(sg); c2.u = pack<bf16_t>(mh); c3.u = pack<bf16_t>(ml); c4.u = pack<bf16_t>(sl);
     wS = c1.b; wMh = c2.b; wMl = c3.b; wSl = c4.b;
   }
@@ -320,7 +314,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
         float v[KK][8];
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
-          union { mlp_bf16x8 b; uint4 u; } cv;
+          union { mf_bf16x8 b; uint4 u; } cv;
           cv.b = xf[mf][kk];
           unpack<bf16_t>(cv.u, v[kk]);
         }
@@ -348,7 +342,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
           float o[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) o[j] = (v[kk][j] - mean) * rstd;
-          union { mlp_bf16x8 b; uint4 u; } cv;
+          union { mf_bf16x8 b; uint4 u; } cv;
           cv.u = pack<bf16_t>(o);
           xf[mf][kk] = cv.b;
           if constexpr (STORE) {
@@ -365,28 +359,22 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
     }
   }
 
-  mlp_f32x4 oacc[MODE == 1 ? MF : 1][MODE == 1 ? NF : 1];
+  mf_f32x4 oacc[MODE == 1 ? MF : 1][MODE == 1 ? NF : 1];
   if constexpr (MODE == 1) {
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf) oacc[mf][nf] = (mlp_f32x4){0.f, 0.f, 0.f, 0.f};
+    mfma_zero(oacc);
   }
 
   // fc1 of one hidden sub-chunk (roles swapped): acc[hf][mf][r] = H[pixel mf*16 + p][hidden 32*hs + hf*16 + q*4 + r];
   // `W` = the W1 fragments of that sub-chunk in a stage buffer (+ lane * 16)
-  auto gemm1 = [&](const char* W, const auto& xfr, mlp_f32x4 (&acc)[2][MF]) {
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf) acc[hf][mf] = (mlp_f32x4){0.f, 0.f, 0.f, 0.f};
+  auto gemm1 = [&](const char* W, const auto& xfr, mf_f32x4 (&acc)[2][MF]) {
+    mfma_zero(acc);
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
-        const mlp_bf16x8 wa = *reinterpret_cast<const mlp_bf16x8*>(W + (hf * KK + kk) * 1024);
+        const mf_bf16x8 wa = *reinterpret_cast<const mf_bf16x8*>(W + (hf * KK + kk) * 1024);
 #pragma unroll
-        for (int mf = 0; mf < MF; ++mf) acc[hf][mf] = mlp_mfma(wa, xfr[mf][kk], acc[hf][mf]);
+        for (int mf = 0; mf < MF; ++mf) acc[hf][mf] = mfma16(wa, xfr[mf][kk], acc[hf][mf]);
       }
   };
   // bias, GELU, GRN in registers (same rounding points as the unfused kernels: h and g are bf16 values); MODE 0 adds g^2
@@ -395,7 +383,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
   // leave as 16-byte vectors, 128-byte row segments (8-byte stores straight from the accumulator layout — 32-byte segments —
   // ran at 2.4-2.8 TB/s and made this pass slower than the unfused GEMM)
   char* sb = obuf + wave * ((STORE_H ? 2 : 1) * WM * G::OB_RS);
-  auto activate = [&](int hs, const mlp_f32x4 (&acc)[2][MF], mlp_bf16x8 (&zf)[MF]) {
+  auto activate = [&](int hs, const mf_f32x4 (&acc)[2][MF], mf_bf16x8 (&zf)[MF]) {
     const float* vb = vec + hs * 32 + kq * 4;
     float b1v[2][4], sv[2][4], bv[2][4];
 #pragma unroll
@@ -456,7 +444,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
           }
         }
       if constexpr (MODE == 1) {
-        union { uint4 u; mlp_bf16x8 v; } pk;
+        union { uint4 u; mf_bf16x8 v; } pk;
         pk.u = pack<bf16_t>(z);
         zf[mf] = pk.v;
       }
@@ -468,22 +456,15 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
   // contraction index is the pixel.  X . X^T has the sums of squares on its diagonal (products of bf16 values are exact in
   // fp32: the arithmetic of fmaf(g, g, acc), in another order); X . 1 has the plain sums in every column.  Replaces 8 squares +
   // 32 DPP steps per lane and sub-chunk (a quarter of the VALU instructions of these passes: round 4).
-  auto tile_frag = [&](const char* tile, int col0) -> mlp_bf16x8 {
-    typedef short s16x4_t __attribute__((ext_vector_type(4)));
-    const char* a0 = tile + (kq * 4 + (p16 >> 2)) * G::OB_RS + (col0 + (p16 & 3) * 4) * 2;
-    union { struct { s16x4_t lo, hi; } s; mlp_bf16x8 v; } u;
-    u.s.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a0));
-    u.s.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a0 + 16 * G::OB_RS));
-    return u.v;
-  };
+  auto tile_frag = [&](const char* tile, int col0) -> mf_bf16x8 { return lds_tr8(tile, G::OB_RS, col0, p16, kq); };
   auto stats_mfma = [&](int hs, float* rw) {  // rw[32] = sum over the wave's pixels of g^2, this sub-chunk's 32 columns
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const char* gt_ = sb + (STORE_H ? WM * G::OB_RS : 0);
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
-      const mlp_bf16x8 X = tile_frag(gt_, (STORE ? (hs & 1) * 32 : 0) + ct * 16);
-      const mlp_f32x4 D = mlp_mfma(X, X, (mlp_f32x4){0.f, 0.f, 0.f, 0.f});
+      const mf_bf16x8 X = tile_frag(gt_, (STORE ? (hs & 1) * 32 : 0) + ct * 16);
+      const mf_f32x4 D = mfma16(X, X, (mf_f32x4){0.f, 0.f, 0.f, 0.f});
       // lane (n, q) holds D[4q + i][n]: the diagonal element of column n sits in lane (n, n / 4), register n % 4
       const int i = p16 & 3;
       const float dsel = i == 0 ? D[0] : (i == 1 ? D[1] : (i == 2 ? D[2] : D[3]));
@@ -493,23 +474,20 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
   auto colsum_mfma = [&](int hs, float* rw) {  // rw[32] = sum over the wave's pixels of the parked tile (dh), 32 columns
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    union { unsigned short h[8]; mlp_bf16x8 v; } one;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) one.h[j] = 0x3F80;
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
-      const mlp_bf16x8 X = tile_frag(sb, (hs & 1) * 32 + ct * 16);
+      const mf_bf16x8 X = tile_frag(sb, (hs & 1) * 32 + ct * 16);
       if constexpr (LNF) {  // the parked tile holds dh' = dh * rstd: sigma-weighted sums = sums of dh; mean-weighted sums = u
-        mlp_f32x4 D = mlp_mfma(X, wS, (mlp_f32x4){0.f, 0.f, 0.f, 0.f});
-        D = mlp_mfma(X, wSl, D);
-        mlp_f32x4 U = mlp_mfma(X, wMh, (mlp_f32x4){0.f, 0.f, 0.f, 0.f});
-        U = mlp_mfma(X, wMl, U);
+        mf_f32x4 D = mfma16(X, wS, (mf_f32x4){0.f, 0.f, 0.f, 0.f});
+        D = mfma16(X, wSl, D);
+        mf_f32x4 U = mfma16(X, wMh, (mf_f32x4){0.f, 0.f, 0.f, 0.f});
+        U = mfma16(X, wMl, U);
         if (p16 == 0) {
           *reinterpret_cast<float4*>(rw + ct * 16 + kq * 4) = make_float4(D[0], D[1], D[2], D[3]);
           *reinterpret_cast<float4*>(rw + NW * 32 + ct * 16 + kq * 4) = make_float4(U[0], U[1], U[2], U[3]);
         }
       } else {
-        const mlp_f32x4 D = mlp_mfma(X, one.v, (mlp_f32x4){0.f, 0.f, 0.f, 0.f});
+        const mf_f32x4 D = mfma16(X, mf_ones8(), (mf_f32x4){0.f, 0.f, 0.f, 0.f});
         if (p16 == 0) *reinterpret_cast<float4*>(rw + ct * 16 + kq * 4) = make_float4(D[0], D[1], D[2], D[3]);
       }
     }
@@ -555,7 +533,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
     }
   };
   // backward activation of one sub-chunk: acc = dz (fp32) of [WM pixels] x [32 hidden] in the accumulator layout
-  auto bwd_act = [&](int hs, const mlp_f32x4 (&acc)[2][MF], const mlp_f32x4 (&hacc)[2][MF], float (&r0)[2][4], float (&r1)[2][4]) {
+  auto bwd_act = [&](int hs, const mf_f32x4 (&acc)[2][MF], const mf_f32x4 (&hacc)[2][MF], float (&r0)[2][4], float (&r1)[2][4]) {
     if constexpr (BWD) {
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf)
@@ -650,8 +628,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
     for (int p = wave; p < G::NP; p += DW) {
       if ((RE || p < G::W1_PIECES) && s + 1 >= NHS) continue;
       const char* src = p < G::W1_PIECES ? src1 : src2;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + p * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + p * 1024), 16, 0, 0);
+      lds_dma16(src + p * 1024, dst + p * 1024);
     }
   };
   // MODE 2: lane (p, q) owns hidden q*4 .. q*4+3 of pixel p in each 16-column half: two 8-byte stores per output and
@@ -671,24 +648,20 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
       __builtin_amdgcn_wave_barrier();
     }
   };
-  mlp_f32x4 hcur[2][MF], hnxt[2][MF];
-  mlp_f32x4 gcur[RE ? 2 : 1][RE ? MF : 1], gnxt[RE ? 2 : 1][RE ? MF : 1];  // MODE 5: the recomputed fc1 accumulators
+  mf_f32x4 hcur[2][MF], hnxt[2][MF];
+  mf_f32x4 gcur[RE ? 2 : 1][RE ? MF : 1], gnxt[RE ? 2 : 1][RE ? MF : 1];  // MODE 5: the recomputed fc1 accumulators
   // prologue: W1 of sub-chunk 0 goes where "stage -1" would sit (buffer 1)
   {
     const char* src = a.wimg + lane * 16;
-    for (int p = wave; p < G::W1_PIECES; p += NW)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + p * 1024),
-                                       (__attribute__((address_space(3))) void*)(buf1 + p * 1024), 16, 0, 0);
+    for (int p = wave; p < G::W1_PIECES; p += NW) lds_dma16(src + p * 1024, buf1 + p * 1024);
     if constexpr (RE) {
       const char* srcf = a.wimg2 + lane * 16;
-      for (int p = wave; p < G::W1_PIECES; p += NW)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcf + p * 1024),
-                                         (__attribute__((address_space(3))) void*)(buf1 + (G::W1_PIECES + p) * 1024), 16, 0, 0);
+      for (int p = wave; p < G::W1_PIECES; p += NW) lds_dma16(srcf + p * 1024, buf1 + (G::W1_PIECES + p) * 1024);
     }
   }
   stage_load2(0, buf0);
   tile_load(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
   gemm1(buf1 + lane * 16, xf, hcur);
   if constexpr (RE) gemm1(buf1 + G::W1_PIECES * 1024 + lane * 16, xg, gcur);
@@ -755,7 +728,7 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
         else atomicAdd(a.colsq + (size_t)b * H4 + (hs - 1) * 32 + lane, t);
       }
     }
-    mlp_bf16x8 zf[MF];
+    mf_bf16x8 zf[MF];
     // three scheduling regions.  Inside the GEMM regions the fragment reads run three ahead of the MFMAs that consume them
     // (left alone, hipcc sinks every ds_read_b128 to just before its two MFMAs: read - wait - MFMA - MFMA chains with every
     // LDS latency exposed — 31 waits per sub-chunk at C = 224); the activation region in between is left to the compiler
@@ -797,9 +770,9 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
       // fc2: out[pixel][n] += Z[pixel][32 hidden] . W2[n][same 32 hidden, permuted alike in the image]
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) {
-        const mlp_bf16x8 wb = *reinterpret_cast<const mlp_bf16x8*>(S + (G::W1_PIECES + nf) * 1024);
+        const mf_bf16x8 wb = *reinterpret_cast<const mf_bf16x8*>(S + (G::W1_PIECES + nf) * 1024);
 #pragma unroll
-        for (int mf = 0; mf < MF; ++mf) oacc[mf][nf] = mlp_mfma(zf[mf], wb, oacc[mf][nf]);
+        for (int mf = 0; mf < MF; ++mf) oacc[mf][nf] = mfma16(zf[mf], wb, oacc[mf][nf]);
       }
       __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
@@ -828,13 +801,13 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
 #pragma unroll 1
   for (int hs = 0; hs < NHS; hs += 2) {
     if (hs > 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       { const int hs_ = hs; { const int hs = hs_ - 1; MLP_STAMP(6); } }
       __syncthreads();
     }
     MLP_STAMP(0);
     step(hs, buf0, buf1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     MLP_STAMP(6);
     __syncthreads();
     { const int hs_ = hs; { const int hs = hs_ + 1; MLP_STAMP(0); } }
@@ -879,10 +852,10 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
         for (int r = 0; r < 4; ++r) oacc[mf][nf][r] = (oacc[mf][nf][r] + bias) * rs;
     }
     // shortcut: OUT += RES . I  (B fragment of the identity: lane (n, q) holds 1.0 at slot j = h2*16 + n - q*8)
-    mlp_bf16x8 idB[2];
+    mf_bf16x8 idB[2];
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
-      union { unsigned short h[8]; mlp_bf16x8 v; } u;
+      union { unsigned short h[8]; mf_bf16x8 v; } u;
 #pragma unroll
       for (int j = 0; j < 8; ++j) u.h[j] = (h2 * 16 + p16 == kq * 8 + j) ? (unsigned short)0x3F80 : (unsigned short)0;
       idB[h2] = u.v;
@@ -891,9 +864,9 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a) {
     for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
-        const mlp_bf16x8 rf = *reinterpret_cast<const mlp_bf16x8*>(a.res + (size_t)(row0 + mf * 16 + p16) * C + kk * 32 + kq * 8);
+        const mf_bf16x8 rf = *reinterpret_cast<const mf_bf16x8*>(a.res + (size_t)(row0 + mf * 16 + p16) * C + kk * 32 + kq * 8);
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) oacc[mf][kk * 2 + h2] = mlp_mfma(rf, idB[h2], oacc[mf][kk * 2 + h2]);
+        for (int h2 = 0; h2 < 2; ++h2) oacc[mf][kk * 2 + h2] = mfma16(rf, idB[h2], oacc[mf][kk * 2 + h2]);
       }
     // per-wave transpose through LDS, 64 columns at a time: accumulator layout (4 rows x 1 column per lane) -> 16-byte
     // vectors, 8 lanes per 128-byte row segment
