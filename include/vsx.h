@@ -843,6 +843,35 @@ int32_t vsx_gram_centered(const float* x, int64_t n, int32_t d, const double* me
 int32_t vsx_center_project(const float* x, int64_t n, int32_t d, const double* mean, const float* w, int32_t k, float* z,
     vsx_stream_t stream);
 
+/* The data passes of a Newton iteration on the weighted logistic objective (csrc/logreg.hip, csrc/pca.hip;
+ * viscy_utils/evaluation/linear_classifier.py: sklearn LogisticRegression on frozen embeddings).  x, n, d, alignment, workspaces, the
+ * absence of atomics and the refusals are those of the PCA passes above: every output is a pure function of the inputs.
+ * logreg_rows: for every row i, in float64,
+ *     z_i = (sum_j x_ij w_j) + b      w [d] float64 on the device; fma over the features 4 l .. 4 l + 3, 256 + 4 l .. of lane l in ascending
+ *                                     order from 0, the 64 lanes added by the xor butterfly 32 .. 1, b last: one order for every alignment
+ *     y = +1 where labels[i] == pos, else -1;  c = cp or cn accordingly;  m = y z;  e = exp(-|m|)
+ *     sigma = 1 / (1 + e), 1 - sigma = e / (1 + e) for m >= 0, the two swapped for m < 0 (no cancellation)
+ *     loss = c (log1p(e) + max(-m, 0));  r = -c y (1 - sigma) = dloss/dz;  s = c sigma (1 - sigma) = d2loss/dz2;  q = fl32(sqrt(s))
+ *   z, r, s [n] float64, q [n] fp32, sums [3] float64 = {sum loss, sum r, sum s} (a wave owns a contiguous run of rows; its lane l adds rows
+ *   l, 64 + l, .. of the run in ascending order, then the butterfly; the four waves of a workgroup 0 .. 3; then the workgroups l, l + 64, ..
+ *   per lane and the butterfly); any of the five may be null.  With r, s, q and sums all
+ *   null the call computes the margins z alone and labels may be null: the decision function, with the dot order of the fit.
+ *   ws: vsx_logreg_rows_ws_bytes(n, d), needed where sums is not null.
+ * wcolsum: out [m, d] float64 = sum_i v_ki x_ij for v [m, n] float64, 1 <= m <= 4: fma in float64, x read once for all m; the row
+ *   split and fold of col_moments.  With v = {r, s} it yields the gradient X'r and the intercept column X's of the Hessian together.
+ * gram_scaled: gram [d, d] float64 = sum_i fl32(q_i c_ij) fl32(q_i c_il) with c_ij = fl32(x_ij - mean_j) as in gram_centered, q [n] fp32;
+ *   mean may be null (c_ij = x_ij).  The kernel, tiling, split plan (vsx_gram_rows_per_split, vsx_gram_ws_bytes), block sums and fold are
+ *   gram_centered's; the one difference is the fp32 multiply where the slab goes to LDS.  With q = fl32(sqrt(s)) it is the Hessian block
+ *   X' diag(s) X as a true Gram: symmetric bit for bit and positive semi-definite. */
+int64_t vsx_logreg_rows_ws_bytes(int64_t n, int32_t d);
+int32_t vsx_logreg_rows(const float* x, int64_t n, int32_t d, const double* w, double b, const int32_t* labels, int32_t pos, double cp,
+    double cn, double* z, double* r, double* s, float* q, double* sums, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int64_t vsx_wcolsum_ws_bytes(int64_t n, int32_t d, int32_t m);
+int32_t vsx_wcolsum(const float* x, int64_t n, int32_t d, const double* v, int32_t m, double* out, void* ws, int64_t ws_bytes,
+    vsx_stream_t stream);
+int32_t vsx_gram_scaled(const float* x, int64_t n, int32_t d, const double* mean, const float* q, double* gram, void* ws, int64_t ws_bytes,
+    vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

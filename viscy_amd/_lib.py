@@ -223,6 +223,11 @@ _SIGS = {
     "vsx_gram_rows_per_split": (_I64, [_I64, _I32]),
     "vsx_gram_centered": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _P]),
     "vsx_center_project": (_I32, [_P, _I64, _I32, _P, _P, _I32, _P, _P]),
+    "vsx_logreg_rows_ws_bytes": (_I64, [_I64, _I32]),
+    "vsx_logreg_rows": (_I32, [_P, _I64, _I32, _P, C.c_double, _P, _I32, C.c_double, C.c_double] + [_P] * 6 + [_I64, _P]),
+    "vsx_wcolsum_ws_bytes": (_I64, [_I64, _I32, _I32]),
+    "vsx_wcolsum": (_I32, [_P, _I64, _I32, _P, _I32, _P, _P, _I64, _P]),
+    "vsx_gram_scaled": (_I32, [_P, _I64, _I32, _P, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

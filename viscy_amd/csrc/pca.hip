@@ -3,6 +3,7 @@
 //
 //   vsx_col_moments     mean_j = sum_i x_ij / n,  m2_j = sum_i (x_ij - mean_j)^2            float64, two passes
 //   vsx_gram_centered   G_jl = sum_i fl32(x_ij - mean_j) fl32(x_il - mean_l)               float64 [d, d], symmetric, full
+//   vsx_gram_scaled     G_jl = sum_i fl32(q_i c_ij) fl32(q_i c_il),  c_ij = fl32(x_ij - mean_j)   the same kernel, one multiply more
 //   vsx_center_project  z_ic = sum_j fl32(x_ij - mean_j) w_cj                              fp32 [n, k], the dots of f32_tile.h
 //
 // No atomics anywhere: workgroups write partials to rows of the workspace that are theirs alone and a second kernel folds them in
@@ -16,14 +17,11 @@
 // block of GM_R = 128 rows in ascending row order and the block sum is then added to a float64 accumulator, block after block:
 // the fp32 part of the error is that of a 128-term sum (worst case 128 * 2^-24 relative to sum |c_j c_l|, the bound
 // vsx_mmd_sums' label product already carries) whatever n is; past the block everything is float64.
+#include "col_split.h"
 #include "f32_tile.h"
 #include "../../include/vsx.h"
 
 #define PCA_MAX_D 4096
-#define CM_COLS 64           // columns per workgroup of the moment passes (one wave wide: coalesced along d)
-#define CM_LANES 4           // row lanes per column
-#define CM_MIN_ROWS 512      // rows per workgroup at least
-#define CM_WANT_WGS 2048
 #define GM_R 128             // rows per fp32 block
 #define GM_KC 32             // rows per staged slab
 #define GM_LD 160            // floats per slab row: 128 + 32, rows 2 s and 2 s + 1 on different banks
@@ -63,28 +61,24 @@ __global__ __launch_bounds__(CM_COLS * CM_LANES) void pca_moment_kernel(const fl
     part[(size_t)blockIdx.y * d + col] = tot;
   }
 }
-// out[col] = the splits' partials in ascending order, times scale-by-division where div > 0
-__global__ __launch_bounds__(256) void pca_moment_fold_kernel(const double* __restrict__ part, int splits, int d, double div,
-                                                              double* __restrict__ out) {
-  const int col = blockIdx.x * 256 + threadIdx.x;
-  if (col >= d) return;
-  double tot = 0.0;
-  for (int s = 0; s < splits; ++s) tot += part[(size_t)s * d + col];
-  out[col] = div > 0.0 ? tot / div : tot;
-}
-
 // ------------------------------------------------------------------ (b) centred Gram
 // the centring of four fetched features as they go to LDS: float64 differences, each rounded once.  mu: the tile's means, 0
-// past d, where ft_row4 has fetched zeros; a row outside the split stays zero
-__device__ __forceinline__ float4 gm_centre4(const float4& v, bool row_ok, const double* mu) {
+// past d, where ft_row4 has fetched zeros; a row outside the split stays zero.  SCALED: each centred value times the row's
+// q in fp32, rounded once more
+template <bool SCALED>
+__device__ __forceinline__ float4 gm_centre4(const float4& v, bool row_ok, const double* mu, float q) {
   if (!row_ok) return make_float4(0.f, 0.f, 0.f, 0.f);
-  return make_float4((float)((double)v.x - mu[0]), (float)((double)v.y - mu[1]), (float)((double)v.z - mu[2]), (float)((double)v.w - mu[3]));
+  const float4 c = make_float4((float)((double)v.x - mu[0]), (float)((double)v.y - mu[1]), (float)((double)v.z - mu[2]), (float)((double)v.w - mu[3]));
+  if (!SCALED) return c;
+  return make_float4(__fmul_rn(q, c.x), __fmul_rn(q, c.y), __fmul_rn(q, c.z), __fmul_rn(q, c.w));
 }
 
-// grid (tile pairs, splits).  ws [split][pair][128][128] doubles, row-major in the tile
-template <bool VEC>
-__global__ __launch_bounds__(FT_THREADS, 1) void pca_gram_kernel(const float* __restrict__ x, const double* __restrict__ mean, long n, int d,
-                                                                 int tiles, long rows_per_split, double* __restrict__ ws) {
+// grid (tile pairs, splits).  ws [split][pair][128][128] doubles, row-major in the tile.  SCALED: qrow [n] scales the rows and
+// mean may be null (no centring)
+template <bool VEC, bool SCALED>
+__global__ __launch_bounds__(FT_THREADS, 1) void pca_gram_kernel(const float* __restrict__ x, const double* __restrict__ mean,
+                                                                 const float* __restrict__ qrow, long n, int d, int tiles,
+                                                                 long rows_per_split, double* __restrict__ ws) {
   __shared__ __attribute__((aligned(16))) float slab[2 * GM_SLAB];  // features of tile ti | of tile tj, the same rows
   __shared__ double mu[2][FT_T];
 
@@ -100,8 +94,9 @@ __global__ __launch_bounds__(FT_THREADS, 1) void pca_gram_kernel(const float* __
 
   if (t < FT_T) {
     const int ca = ti * FT_T + t, cb = tj * FT_T + t;
-    mu[0][t] = ca < d ? mean[ca] : 0.0;
-    mu[1][t] = cb < d ? mean[cb] : 0.0;
+    const bool centred = !SCALED || mean != nullptr;
+    mu[0][t] = centred && ca < d ? mean[ca] : 0.0;
+    mu[1][t] = centred && cb < d ? mean[cb] : 0.0;
   }
   __syncthreads();
 
@@ -110,7 +105,15 @@ __global__ __launch_bounds__(FT_THREADS, 1) void pca_gram_kernel(const float* __
   // one slab later, so the loads are in flight while the MFMAs of the slab before run
   const int nu = diag ? 4 : 8;
   float4 pre[8];
+  float qpre[4] = {1.f, 1.f, 1.f, 1.f};  // SCALED: q of the thread's four slab rows, (t >> 5) + 8 u
   auto fetch = [&](int ch) {
+    if (SCALED) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long r = r0 + (long)ch * GM_KC + (t >> 5) + 8 * u;
+        qpre[u] = r < r1 ? qrow[r] : 0.f;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       if (u < nu) {
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(FT_THREADS, 1) void pca_gram_kernel(const float* __
       if (u < nu) {
         const int g = (t + FT_THREADS * u) & 1023, q4 = 4 * (g & 31);
         *reinterpret_cast<float4*>(slab + (u >> 2) * GM_SLAB + (g >> 5) * GM_LD + q4) =
-            gm_centre4(pre[u], r0 + (long)ch * GM_KC + (g >> 5) < r1, &mu[u >> 2][q4]);
+            gm_centre4<SCALED>(pre[u], r0 + (long)ch * GM_KC + (g >> 5) < r1, &mu[u >> 2][q4], qpre[u & 3]);
       }
     }
     __syncthreads();
@@ -231,15 +234,6 @@ static int pca_shape(const char* who, int64_t n, int64_t d) {
 }
 static bool pca_shape_ok(int64_t n, int64_t d) { return n >= 2 && n < ((int64_t)1 << 31) && d >= 1 && d <= PCA_MAX_D; }
 
-// the moment passes: row splits of equal length, at least CM_MIN_ROWS rows each, about CM_WANT_WGS workgroups
-static void cm_split(int64_t n, int d, int* splits, int64_t* rps) {
-  const int64_t groups = (d + CM_COLS - 1) / CM_COLS;
-  int64_t want = (CM_WANT_WGS + groups - 1) / groups;
-  const int64_t most = (n + CM_MIN_ROWS - 1) / CM_MIN_ROWS;
-  if (want > most) want = most;
-  *rps = (n + want - 1) / want;
-  *splits = (int)((n + *rps - 1) / *rps);
-}
 // the Gram pass: splits of whole blocks, at least GM_MIN_BLOCKS each, so that pairs * splits is at most GM_WANT_WGS (or pairs)
 static void gm_split(int64_t n, int d, int* tiles, int* pairs, int* splits, int64_t* rps) {
   *tiles = (d + FT_T - 1) / FT_T;
@@ -278,9 +272,9 @@ extern "C" int32_t vsx_col_moments(const float* x, int64_t n, int32_t d, double*
   const dim3 grid((unsigned)((d + CM_COLS - 1) / CM_COLS), (unsigned)splits), block(CM_COLS * CM_LANES), fgrid((unsigned)((d + 255) / 256));
   double* part = (double*)ws;
   hipLaunchKernelGGL(pca_moment_kernel<0>, grid, block, 0, s, x, (const double*)nullptr, (long)n, d, (long)rps, part);
-  hipLaunchKernelGGL(pca_moment_fold_kernel, fgrid, dim3(256), 0, s, (const double*)part, splits, d, (double)n, mean);
+  hipLaunchKernelGGL(cm_fold_kernel, fgrid, dim3(256), 0, s, (const double*)part, splits, d, (double)n, mean);
   hipLaunchKernelGGL(pca_moment_kernel<1>, grid, block, 0, s, x, (const double*)mean, (long)n, d, (long)rps, part);
-  hipLaunchKernelGGL(pca_moment_fold_kernel, fgrid, dim3(256), 0, s, (const double*)part, splits, d, 0.0, m2);
+  hipLaunchKernelGGL(cm_fold_kernel, fgrid, dim3(256), 0, s, (const double*)part, splits, d, 0.0, m2);
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -301,13 +295,14 @@ extern "C" int64_t vsx_gram_ws_bytes(int64_t n, int32_t d) {
   return (int64_t)splits * pairs * FT_T * FT_T * 8;
 }
 
-extern "C" int32_t vsx_gram_centered(const float* x, int64_t n, int32_t d, const double* mean, double* gram, void* ws, int64_t ws_bytes,
-                                     vsx_stream_t stream) {
-  if (int rc = pca_shape("vsx_gram_centered", n, d)) return rc;
-  VSX_CHECK(x && mean && gram && ws, "vsx_gram_centered: null argument");
-  VSX_CHECK(((uintptr_t)x & 3) == 0 && (((uintptr_t)mean | (uintptr_t)gram | (uintptr_t)ws) & 7) == 0,
-            "vsx_gram_centered: x must be 4-byte aligned, mean, gram and ws 8-byte aligned");
-  VSX_CHECK(ws_bytes >= vsx_gram_ws_bytes(n, d), "vsx_gram_centered: the workspace must hold vsx_gram_ws_bytes = %ld bytes (got %ld)",
+// the Gram pass and its fold; q: the row scales of vsx_gram_scaled, null for vsx_gram_centered
+static int gm_launch(const char* who, const float* x, int64_t n, int32_t d, const double* mean, const float* q, double* gram, void* ws,
+                     int64_t ws_bytes, vsx_stream_t stream) {
+  if (int rc = pca_shape(who, n, d)) return rc;
+  VSX_CHECK(x && (mean || q) && gram && ws, "%s: null argument", who);
+  VSX_CHECK((((uintptr_t)x | (uintptr_t)q) & 3) == 0 && (((uintptr_t)mean | (uintptr_t)gram | (uintptr_t)ws) & 7) == 0,
+            "%s: x%s must be 4-byte aligned, mean, gram and ws 8-byte aligned", who, q ? " and q" : "");
+  VSX_CHECK(ws_bytes >= vsx_gram_ws_bytes(n, d), "%s: the workspace must hold vsx_gram_ws_bytes = %ld bytes (got %ld)", who,
             (long)vsx_gram_ws_bytes(n, d), (long)ws_bytes);
   int tiles, pairs, splits;
   int64_t rps;
@@ -315,12 +310,27 @@ extern "C" int32_t vsx_gram_centered(const float* x, int64_t n, int32_t d, const
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)pairs, (unsigned)splits), block(FT_THREADS);
   vsx_by_bool(ft_vec_ok(x, d), [&](auto vec) {
-    hipLaunchKernelGGL(pca_gram_kernel<decltype(vec)::value>, grid, block, 0, s, x, mean, (long)n, d, tiles, (long)rps, (double*)ws);
+    vsx_by_bool(q != nullptr, [&](auto scaled) {
+      hipLaunchKernelGGL((pca_gram_kernel<decltype(vec)::value, decltype(scaled)::value>), grid, block, 0, s, x, mean, q, (long)n, d, tiles,
+                         (long)rps, (double*)ws);
+    });
   });
   hipLaunchKernelGGL(pca_gram_fold_kernel, dim3((unsigned)pairs, FT_T * FT_T / 256), dim3(256), 0, s, (const double*)ws, splits, pairs, tiles, d,
                      gram);
   VSX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int32_t vsx_gram_centered(const float* x, int64_t n, int32_t d, const double* mean, double* gram, void* ws, int64_t ws_bytes,
+                                     vsx_stream_t stream) {
+  VSX_CHECK(mean, "vsx_gram_centered: null argument");
+  return gm_launch("vsx_gram_centered", x, n, d, mean, nullptr, gram, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t vsx_gram_scaled(const float* x, int64_t n, int32_t d, const double* mean, const float* q, double* gram, void* ws,
+                                   int64_t ws_bytes, vsx_stream_t stream) {
+  VSX_CHECK(q, "vsx_gram_scaled: null argument");
+  return gm_launch("vsx_gram_scaled", x, n, d, mean, q, gram, ws, ws_bytes, stream);
 }
 
 extern "C" int32_t vsx_center_project(const float* x, int64_t n, int32_t d, const double* mean, const float* w, int32_t k, float* z,

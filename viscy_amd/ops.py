@@ -1389,3 +1389,64 @@ def center_project(x: Tensor, mean: Tensor, w: Tensor) -> Tensor:
     z = torch.empty((n, k), dtype=torch.float32, device=x.device)
     check(lib().vsx_center_project(ptr(x), n, d, ptr(mean), ptr(w), k, ptr(z), stream()), "center_project")
     return z
+
+
+# ------------------------------------------------------------------ logistic-regression data passes (csrc/logreg.hip, csrc/pca.hip)
+def gram_scaled(x: Tensor, q: Tensor, mean: Tensor | None = None) -> Tensor:
+    """-> float64 (d, d): sum_i fl32(q_i c_i)' fl32(q_i c_i) with c = fl32(x - mean) (``mean=None``: c = x), q float32 (n,):
+    ``gram_centered``'s kernel, split plan and fold with one fp32 multiply more; symmetric bit for bit"""
+    n, d = _rows_f32(x, "gram_scaled")
+    _f32_vec(q, n, "gram_scaled: q")
+    if mean is not None:
+        _f64_vec(mean, d, "gram_scaled: mean")
+    ws = _ws(x.device, lib().vsx_gram_ws_bytes(n, d), torch.float64)
+    gram = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    check(lib().vsx_gram_scaled(ptr(x), n, d, ptr(mean), ptr(q), ptr(gram), ptr(ws), ws.nbytes, stream()), "gram_scaled")
+    return gram
+
+
+def wcolsum(x: Tensor, v: Tensor) -> Tensor:
+    """-> float64 (m, d): v x for v float64 (m, n), 1 <= m <= 4, x float32 (n, d) read once; float64 fma, fixed-order folds"""
+    n, d = _rows_f32(x, "wcolsum")
+    ptr(v)
+    if v.dtype != torch.float64 or v.dim() != 2 or v.shape[1] != n or not 1 <= v.shape[0] <= 4:
+        raise TypeError(f"wcolsum: v must be a float64 (m, {n}) tensor with 1 <= m <= 4, got {v.dtype} {tuple(v.shape)}")
+    m = v.shape[0]
+    ws = _ws(x.device, lib().vsx_wcolsum_ws_bytes(n, d, m), torch.float64)
+    out = torch.empty((m, d), dtype=torch.float64, device=x.device)
+    check(lib().vsx_wcolsum(ptr(x), n, d, ptr(v), m, ptr(out), ptr(ws), ws.nbytes, stream()), "wcolsum")
+    return out
+
+
+def logreg_margins(x: Tensor, w: Tensor, b: float) -> Tensor:
+    """-> float64 (n,): z = x w + b, the dot order of ``logreg_rows`` (the decision function shares it with the fit)"""
+    n, d = _rows_f32(x, "logreg_margins")
+    _f64_vec(w, d, "logreg_margins: w")
+    z = torch.empty(n, dtype=torch.float64, device=x.device)
+    check(lib().vsx_logreg_rows(ptr(x), n, d, ptr(w), float(b), None, 0, 0.0, 0.0, ptr(z), None, None, None, None, None, 0, stream()),
+          "logreg_margins")
+    return z
+
+
+def logreg_rows(x: Tensor, w: Tensor, b: float, labels: Tensor, pos: int, cp: float, cn: float, *, margins: bool = False,
+                derivatives: bool = True) -> dict[str, Tensor]:
+    """The row pass of the weighted logistic objective, float64: y = +1 where ``labels == pos`` else -1, c = cp | cn, m = y z.
+    -> {"sums": (3,) {sum loss, sum r, sum s}} and, with ``derivatives``, "r" = dloss/dz, "s" = d2loss/dz2 (float64 (n,), the two rows of "rs") and
+    "q" = fl32(sqrt(s)) (float32 (n,), the row scale of ``gram_scaled``); with ``margins`` also "z".  A line-search trial asks for
+    the sums alone."""
+    n, d = _rows_f32(x, "logreg_rows")
+    _f64_vec(w, d, "logreg_rows: w")
+    _i32(labels, n, "logreg_rows: labels")
+    dev = x.device
+    out = {"sums": torch.empty(3, dtype=torch.float64, device=dev)}
+    if derivatives:
+        out["rs"] = torch.empty((2, n), dtype=torch.float64, device=dev)   # r over s: the v of ``wcolsum``
+        out["r"], out["s"] = out["rs"][0], out["rs"][1]
+        out["q"] = torch.empty(n, dtype=torch.float32, device=dev)
+    if margins:
+        out["z"] = torch.empty(n, dtype=torch.float64, device=dev)
+    ws = _ws(dev, lib().vsx_logreg_rows_ws_bytes(n, d), torch.float64)
+    check(lib().vsx_logreg_rows(ptr(x), n, d, ptr(w), float(b), ptr(labels), int(pos), float(cp), float(cn), ptr(out.get("z")),
+                                ptr(out.get("r")), ptr(out.get("s")), ptr(out.get("q")), ptr(out["sums"]), ptr(ws), ws.nbytes, stream()),
+          "logreg_rows")
+    return out
