@@ -760,6 +760,7 @@ int32_t vsx_conv3d_from_cl(const void* y, float* out, int32_t B, int32_t C, int6
  * ws (4-byte aligned) holds vsx_knn_topk_ws_bytes(N, d, k) = O(N k) bytes, any contents.
  * knn_vote: pred[i] = the most frequent label among labels[idx[i][0 .. cnt[i])], ties to the smallest label; -1 for cnt[i] = 0.
  * pair_cosine_dist: out[p] = 1 - fl32(fl32(dot(x_pi[p], x_pj[p]) * inv[pi[p]]) * inv[pj[p]]). */
+#define VSX_KNN_MAX_K 64 /* largest k of vsx_knn_topk / vsx_knn_vote */
 int32_t vsx_row_inv_norm(const float* x, float* inv, int32_t N, int32_t d, float eps, vsx_stream_t stream);
 int64_t vsx_knn_topk_ws_bytes(int32_t N, int32_t d, int32_t k);
 int32_t vsx_knn_topk(const float* x, const float* inv, const int32_t* group, int32_t N, int32_t d, int32_t k, int32_t* idx, float* sim,
@@ -834,6 +835,7 @@ int32_t vsx_sqdist_upper(const float* xc, const float* norms, int32_t M, int32_t
  * center_project: z [n, k] fp32 = (x - mean) w' for w [k, d] fp32, k >= 1: the dots of csrc/f32_tile.h (one summation order) over the
  * centred rows; fold 1 / scale into w for standardised data.
  * The size queries answer 0 for shapes that are not served.  Every check runs before any launch. */
+#define VSX_PCA_MAX_D 4096 /* largest d of the PCA passes and of the logistic-regression passes below */
 int64_t vsx_col_moments_ws_bytes(int64_t n, int32_t d);
 int32_t vsx_col_moments(const float* x, int64_t n, int32_t d, double* mean, double* m2, void* ws, int64_t ws_bytes, vsx_stream_t stream);
 int64_t vsx_gram_ws_bytes(int64_t n, int32_t d);

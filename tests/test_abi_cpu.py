@@ -59,6 +59,153 @@ def test_struct_layout_matches_header():
         assert names == [f[0] for f in getattr(_lib, struct)._fields_], struct
 
 
+# ------------------------------------------------------------------------------------------------ the binding is derived from the header
+def _known_signatures():
+    """rows of the table viscy_amd/_lib.py held by hand before it read the header; together they use every type word of vsx.h"""
+    from viscy_amd._lib import VsxGemm, VsxGemmPlan, VsxWTask
+
+    C = ctypes
+    _I32, _F32, _P, _I64 = C.c_int32, C.c_float, C.c_void_p, C.c_int64
+    return {
+        "vsx_last_error": (C.c_char_p, []),
+        "vsx_set_flag": (_I32, [C.c_char_p, _I32]),
+        "vsx_gemm_plan": (_I32, [_I32, C.POINTER(VsxGemm), _I32, C.POINTER(VsxGemmPlan)]),
+        "vsx_weight_tasks": (_I32, [C.POINTER(VsxWTask), _I32, _P]),  # was _P: typed since ops.flush hands over the array itself
+        "vsx_ln_fwd": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _F32, _I32, _P]),
+        "vsx_mlp_det_floats": (_I64, [_I32, _I32, _I64, _I32]),
+        "vsx_spotlight_fwd": (_I32, [_P, _I32, _P, _P, _I32, _P, _I64, _I64, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
+        "vsx_logreg_rows": (_I32, [_P, _I64, _I32, _P, C.c_double, _P, _I32, C.c_double, C.c_double] + [_P] * 6 + [_I64, _P]),
+        "vsx_row_select": (_I32, [_P, _P, _P, _I64, _I64, _I64, C.POINTER(_I64), _I32, _P]),
+        "vsx_mmd_sums": (_I32, [_P, _P, _P, _I32, _I32, _I32, C.c_double, _P, _P, _I64, _P]),
+    }
+
+
+def _kind(t):
+    """a pointer to a scalar and a void pointer marshal alike; a char pointer, a struct pointer and every scalar stand for themselves"""
+    if isinstance(t, type) and issubclass(t, ctypes._Pointer) and not issubclass(t._type_, ctypes.Structure):
+        return ctypes.c_void_p
+    return t
+
+
+def test_parser_known_answers():
+    from viscy_amd import _lib
+
+    assert _kind(ctypes.POINTER(ctypes.c_int64)) is ctypes.c_void_p and _kind(ctypes.c_char_p) is ctypes.c_char_p
+    assert _kind(ctypes.POINTER(_lib.VsxGemm)) is ctypes.POINTER(_lib.VsxGemm) and _kind(ctypes.c_int64) is ctypes.c_int64
+    for name, (res, args) in _known_signatures().items():
+        got_res, got_args = _lib._SIGS[name]
+        assert got_res is res, name
+        assert [_kind(t) for t in got_args] == [_kind(t) for t in args], name
+    fn = _lib.lib().vsx_spotlight_fwd   # what the loaded library's functions carry is the table
+    assert (fn.restype, list(fn.argtypes)) == _lib._SIGS["vsx_spotlight_fwd"]
+
+
+def _host_cc():
+    import shutil
+
+    cc = shutil.which("cc") or "/opt/rocm/llvm/bin/clang"
+    assert os.path.exists(cc), "no host C compiler: neither cc nor /opt/rocm/llvm/bin/clang"
+    return cc
+
+
+def test_struct_layout_against_the_compiler(tmp_path):
+    """size, and offset and size of every field, of the three ctypes mirrors against what the C compiler lays out from vsx.h"""
+    import subprocess
+
+    from viscy_amd import _lib
+
+    structs = (_lib.VsxGemm, _lib.VsxGemmPlan, _lib.VsxWTask)
+    assert [len(s._fields_) for s in structs] == [35, 14, 14]
+    lines = ["#include <stdio.h>", '#include "vsx.h"', "int main(void) {"]
+    for s in structs:
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (s.__name__, s.__name__))
+        for f, _ in s._fields_:
+            lines.append('  printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (s.__name__, f, s.__name__, f, s.__name__, f))
+    lines += ["  return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([_host_cc(), "-I", os.path.join(ROOT, "include"), "-o", exe, str(tmp_path / "layout.c")], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")
+    want = []
+    for s in structs:
+        want.append("%s %d" % (s.__name__, ctypes.sizeof(s)))
+        want += ["%s.%s %d %d" % (s.__name__, f, getattr(s, f).offset, getattr(s, f).size) for f, _ in s._fields_]
+    assert out == want + [""]
+    assert _lib.VsxGemmPlan.family.offset == 0 and dict(_lib.VsxGemmPlan._fields_)["family"] is ctypes.c_char_p
+    assert dict(_lib.VsxGemm._fields_)["a_coff"] is ctypes.c_int32 * 8 and dict(_lib.VsxGemm._fields_)["A"] is ctypes.c_void_p
+
+
+_MINI_HEADER = """/* a header in the dialect of vsx.h */
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef void* vsx_stream_t;
+#define VSX_TWO 2 /* a constant */
+typedef struct VsxGemm { const void* A; int32_t M, tile[2]; } VsxGemm;
+%s
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_parser_refuses_what_it_does_not_know(monkeypatch):
+    from viscy_amd import _lib
+
+    class VsxGemm(ctypes.Structure):
+        pass
+
+    def parse(decl):
+        return _lib.parse_header(_MINI_HEADER % decl, {"VsxGemm": VsxGemm})
+
+    consts, fields, sigs = parse("int64_t vsx_ok(const VsxGemm* p, const char* s,\n    double x, vsx_stream_t stream);\nint32_t vsx_none(void);")
+    assert consts == {"TWO": 2}
+    assert fields == {"VsxGemm": [("A", ctypes.c_void_p), ("M", ctypes.c_int32), ("tile", ctypes.c_int32 * 2)]}
+    assert sigs == {"vsx_ok": (ctypes.c_int64, [ctypes.POINTER(VsxGemm), ctypes.c_char_p, ctypes.c_double, ctypes.c_void_p]),
+                    "vsx_none": (ctypes.c_int32, [])}
+    for bad, named in (
+        ("int32_t vsx_bad(uint16_t x, vsx_stream_t stream);", "uint16_t"),          # an unknown scalar
+        ("int32_t vsx_bad(const uint16_t* x);", "uint16_t"),                        # ... behind a pointer
+        ("uint16_t vsx_bad(int32_t x);", "uint16_t"),                               # ... returned
+        ("int32_t vsx_bad(const VsxOther* p);", "VsxOther"),                        # a struct without a mirror class
+        ("int32_t vsx_bad(float** x);", "float"),                                   # a pointer to a pointer
+        ("int32_t vsx_bad(int32_t, int32_t b);", "vsx_bad"),                        # a parameter without a name
+        ("int32_t vsx_bad(int32_t a, int32_t b;", "vsx_bad"),                       # a prototype that does not close
+        ("int32_t vsx_bad int32_t a);", "vsx_bad"),                                 # ... or open
+        ("typedef struct VsxOther { int32_t a; } VsxOther;", "VsxOther"),           # a struct without a mirror class
+        ("#define VSX_SHIFTED (1 << 3)", "VSX_SHIFTED"),                            # a constant that is not a plain integer
+    ):
+        with pytest.raises(ValueError, match=named) as e:
+            parse(bad)
+        assert "vsx.h" in str(e.value), bad
+    with pytest.raises(ValueError, match="VsxGemm"):   # `T* a, b` would make b a T, not a pointer
+        _lib.parse_header("typedef struct VsxGemm { const void* A, B; } VsxGemm;", {"VsxGemm": VsxGemm})
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(ROOT, "include", "missing.h"))
+    with pytest.raises(RuntimeError, match="include/missing.h"):
+        _lib._derive()
+
+
+def test_constants_are_the_headers():
+    from tests import ref_ops as R
+    from viscy_amd import _lib, ops, reduce
+
+    assert (_lib.VSX_F32, _lib.VSX_BF16, _lib.F32, _lib.BF16) == (0, 1, 0, 1)
+    assert _lib.EPI_LN_BWD == 6 and _lib.WTASK_REDUCE_ROWS == 6 and _lib.LOSS_SLOTS == 64 and _lib.LOSS_SLOT_STRIDE == 32
+    assert _lib.SPOTLIGHT_CHUNK == 16384 and _lib.NARROW_BWD_C == 5 and _lib.KNN_MAX_K == 64 and _lib.PCA_MAX_D == 4096
+    assert (_lib.GEMM_NT, _lib.GEMM_TN, _lib.WTASK_MAX, _lib.SPOTLIGHT_MASK_F32, _lib.SPOTLIGHT_WS_OTSU) == (0, 1, 40, 2, 1)
+    # tests/ref_ops.py states its own: the independent copy the GPU tests compute references with
+    for name in ("A_ROWS", "A_PATCH2", "A_CONV3", "PRO_NONE", "PRO_GRN", "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU_SQ", "EPI_BIAS_RES",
+                 "EPI_DZ", "EPI_BIAS_STATS"):
+        assert getattr(R, name) == getattr(_lib, name), name
+    # the product takes the limits it checks from the header
+    assert ops.KNN_MAX_K is _lib.KNN_MAX_K and ops.SPOTLIGHT_CHUNK is _lib.SPOTLIGHT_CHUNK
+    assert reduce.MAX_FEATURES == _lib.PCA_MAX_D
+    for f, old, new in (("online_eval.hip", "KT_MAX_K", "VSX_KNN_MAX_K"), ("pca.hip", "PCA_MAX_D", "VSX_PCA_MAX_D"),
+                        ("logreg.hip", "LR_MAX_D", "VSX_PCA_MAX_D")):
+        src = open(os.path.join(ROOT, "viscy_amd", "csrc", f)).read()
+        assert "#define %s %s\n" % (old, new) in src, f
+
+
 def test_no_cpu_fallback():
     from viscy_amd import ops
     from viscy_amd.losses import MixedLoss

@@ -18,7 +18,7 @@
 #include "f32_tile.h"
 #include "../../include/vsx.h"
 
-#define LR_MAX_D 4096
+#define LR_MAX_D VSX_PCA_MAX_D
 #define LR_WAVES 4
 #define LR_WANT_WGS 2048     // eight workgroups per compute unit
 #define LR_MIN_ROWS 16       // rows per workgroup at least: w is staged once for them

@@ -24,7 +24,7 @@
 #include <math.h>
 
 #define KT_MAX_SPLITS 8
-#define KT_MAX_K 64
+#define KT_MAX_K VSX_KNN_MAX_K
 
 // (a) inverse row norms: ft_inv_norm_kernel of f32_tile.h
 // ------------------------------------------------------------------ (d) cosine distance of listed pairs: one wave per pair

@@ -21,7 +21,7 @@
 #include "f32_tile.h"
 #include "../../include/vsx.h"
 
-#define PCA_MAX_D 4096
+#define PCA_MAX_D VSX_PCA_MAX_D
 #define GM_R 128             // rows per fp32 block
 #define GM_KC 32             // rows per staged slab
 #define GM_LD 160            // floats per slab row: 128 + 32, rows 2 s and 2 s + 1 on different banks

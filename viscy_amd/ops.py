@@ -155,7 +155,7 @@ def gemm(
     p.b_bstride = b_bstride
     p.rscale = ptr(rscale)
     if plan is not None:
-        return check(lib().vsx_gemm_plan(0 if kind == "nt" else 1, C.byref(p), dtype_code(dtype), C.byref(plan)), f"gemm_plan_{kind}")
+        return check(lib().vsx_gemm_plan(L.GEMM_NT if kind == "nt" else L.GEMM_TN, C.byref(p), dtype_code(dtype), C.byref(plan)), f"gemm_plan_{kind}")
     if kind == "nt" and epi == L.EPI_BIAS_GELU_SQ:
         _det(A.device, lambda: _gemm_det_floats(p, dtype))
     fn = lib().vsx_gemm_nt if kind == "nt" else lib().vsx_gemm_tn
@@ -164,7 +164,7 @@ def gemm(
 
 def _gemm_det_floats(p: VsxGemm, dtype: torch.dtype) -> int:
     plan = VsxGemmPlan()
-    check(lib().vsx_gemm_plan(0, C.byref(p), dtype_code(dtype), C.byref(plan)), "gemm_plan_nt")
+    check(lib().vsx_gemm_plan(L.GEMM_NT, C.byref(p), dtype_code(dtype), C.byref(plan)), "gemm_plan_nt")
     return plan.det_floats
 
 
@@ -177,7 +177,7 @@ def tn_grn_stats_ok(M: int, N: int, K: int, hw: int, dtype: torch.dtype) -> bool
     p = VsxGemm()   # the statistics launch as the block issues it: pointer fields only say which operands are there
     p.A = p.B = p.C = p.grn_s = p.grn_b = p.aux = p.red0 = 1
     p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldx, p.nz, p.pro, p.hw = M, N, K, K, N, K, K, 1, L.PRO_GRN, hw
-    return lib().vsx_gemm_plan(1, C.byref(p), L.VSX_BF16, C.byref(VsxGemmPlan())) == 0
+    return lib().vsx_gemm_plan(L.GEMM_TN, C.byref(p), L.VSX_BF16, C.byref(VsxGemmPlan())) == 0
 
 
 def dgrad_ln_bwd(dh: Tensor, WT: Tensor, xh: Tensor, rstd: Tensor, M: int, C: int, K: int,
@@ -419,7 +419,7 @@ def flush() -> None:
     arr = (L.VsxWTask * len(_BATCH))(*_BATCH)
     del _BATCH[:]
     try:
-        check(lib().vsx_weight_tasks(C.addressof(arr), len(arr), stream()), "weight_tasks")
+        check(lib().vsx_weight_tasks(arr, len(arr), stream()), "weight_tasks")
     finally:  # (a failed launch must not leave stale addresses behind for the next list: ADVICE r4)
         del _BATCH_KEEP[:]
         del _BATCH_WRITTEN[:]
@@ -917,9 +917,6 @@ def voxel_shuffle_bwd(dout: Tensor, B: int, h: int, w: int, Cout: int, D: int, s
 
 
 # ------------------------------------------------------------------ narrow-channel family (csrc/narrow.hip): the 2x2-stem FCMAE
-NARROW_STEM, NARROW_PROJ, NARROW_FWD1, NARROW_BWD_A, NARROW_BWD_B, NARROW_BWD_C = range(6)
-
-
 def _narrow_ws(dev, op: int, B: int, n: int, C: int, K: int = 0) -> Tensor:
     """per-workgroup partials of a narrow launch, sized by the library"""
     floats = int(lib().vsx_narrow_ws_floats(op, B, n, C, K))
@@ -945,7 +942,7 @@ def narrow_stem_wgrad(x: Tensor, df: Tensor, dW: Tensor, db: Tensor, kernel: tup
     B, Cin, Z, H, Wd = x.shape
     kz, ky, kx = kernel
     C0, K = df.shape[1], Cin * kz * ky * kx
-    ws = _narrow_ws(x.device, NARROW_STEM, B, df.shape[0], C0, K)
+    ws = _narrow_ws(x.device, L.NARROW_STEM, B, df.shape[0], C0, K)
     check(lib().vsx_narrow_stem_wgrad(ptr(x), ptr(df), ptr(dW), ptr(db), ptr(ws), ws.numel(), B, Cin, Z, H, Wd, kz, ky, kx, C0,
                                       dtype_code(df.dtype), stream()), "narrow_stem_wgrad")
 
@@ -964,7 +961,7 @@ def narrow_proj_bwd(dout: Tensor, cat: Tensor, mean: Tensor, rstd: Tensor, gamma
                     db: Tensor, M: int, Ccat: int, C: int) -> Tensor:
     """returns dxn [M, Ccat] (gradient of the LayerNorm's affine output); dW [C, Ccat] / db [C] accumulate"""
     dxn = torch.empty((M, Ccat), dtype=cat.dtype, device=cat.device)
-    ws = _narrow_ws(cat.device, NARROW_PROJ, 1, M, C, Ccat)
+    ws = _narrow_ws(cat.device, L.NARROW_PROJ, 1, M, C, Ccat)
     check(lib().vsx_narrow_proj_bwd(ptr(dout), ptr(cat), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(W), ptr(dxn), ptr(dW), ptr(db),
                                     ptr(ws), ws.numel(), M, Ccat, C, dtype_code(cat.dtype), stream()), "narrow_proj_bwd")
     return dxn
@@ -974,7 +971,7 @@ def narrow_block_fwd1(x: Tensor, dw_w: Tensor, dw_b: Tensor, W1f: Tensor, b1f: T
                       C: int) -> Tensor:
     """ConvNeXt-V2 block at C in {4, 8}, pass 1: returns the depthwise output y; colsq [B, 4C] += per-sample sum gelu(h)^2"""
     y = torch.empty_like(x)
-    ws = _narrow_ws(x.device, NARROW_FWD1, B, H * W, C)
+    ws = _narrow_ws(x.device, L.NARROW_FWD1, B, H * W, C)
     check(lib().vsx_narrow_block_fwd1(ptr(x), ptr(dw_w), ptr(dw_b), ptr(W1f), ptr(b1f), ptr(y), ptr(colsq), ptr(ws), ws.numel(), B, H, W,
                                       C, dtype_code(x.dtype), stream()), "narrow_block_fwd1")
     return y
@@ -990,7 +987,7 @@ def narrow_block_fwd2(y: Tensor, x: Tensor, W1f: Tensor, b1f: Tensor, s: Tensor,
 
 def narrow_block_bwd_a(dout: Tensor, y: Tensor, W1f: Tensor, b1f: Tensor, s: Tensor, grn_b: Tensor, W2: Tensor, dW2: Tensor, db2: Tensor,
                        P: Tensor, S: Tensor, B: int, H: int, W: int, C: int) -> None:
-    ws = _narrow_ws(y.device, NARROW_BWD_A, B, H * W, C)
+    ws = _narrow_ws(y.device, L.NARROW_BWD_A, B, H * W, C)
     check(lib().vsx_narrow_block_bwd_a(ptr(dout), ptr(y), ptr(W1f), ptr(b1f), ptr(s), ptr(grn_b), ptr(W2), ptr(dW2), ptr(db2), ptr(P),
                                        ptr(S), ptr(ws), ws.numel(), B, H, W, C, dtype_code(y.dtype), stream()), "narrow_block_bwd_a")
 
@@ -998,7 +995,7 @@ def narrow_block_bwd_a(dout: Tensor, y: Tensor, W1f: Tensor, b1f: Tensor, s: Ten
 def narrow_block_bwd_b(dout: Tensor, y: Tensor, W1f: Tensor, b1f: Tensor, s: Tensor, t: Tensor, W2: Tensor, dW1f: Tensor, db1f: Tensor,
                        B: int, H: int, W: int, C: int) -> Tensor:
     dy = torch.empty_like(y)
-    ws = _narrow_ws(y.device, NARROW_BWD_B, B, H * W, C)
+    ws = _narrow_ws(y.device, L.NARROW_BWD_B, B, H * W, C)
     check(lib().vsx_narrow_block_bwd_b(ptr(dout), ptr(y), ptr(W1f), ptr(b1f), ptr(s), ptr(t), ptr(W2), ptr(dy), ptr(dW1f), ptr(db1f),
                                        ptr(ws), ws.numel(), B, H, W, C, dtype_code(y.dtype), stream()), "narrow_block_bwd_b")
     return dy
@@ -1007,7 +1004,7 @@ def narrow_block_bwd_b(dout: Tensor, y: Tensor, W1f: Tensor, b1f: Tensor, s: Ten
 def narrow_block_bwd_c(dy: Tensor, x: Tensor, dout: Tensor, dw_w: Tensor, ddw: Tensor, ddb: Tensor, B: int, H: int, W: int,
                        C: int) -> Tensor:
     dx = torch.empty_like(x)
-    ws = _narrow_ws(x.device, NARROW_BWD_C, B, H * W, C)
+    ws = _narrow_ws(x.device, L.NARROW_BWD_C, B, H * W, C)
     check(lib().vsx_narrow_block_bwd_c(ptr(dy), ptr(x), ptr(dout), ptr(dw_w), ptr(dx), ptr(ddw), ptr(ddb), ptr(ws), ws.numel(), B, H, W,
                                        C, dtype_code(x.dtype), stream()), "narrow_block_bwd_c")
     return dx
@@ -1143,7 +1140,7 @@ def c3_from_cl(y: Tensor, B: int, spatial: Sequence[int]) -> Tensor:
 
 
 # ------------------------------------------------------------------ OnlineEvalCallback (csrc/online_eval.hip)
-KNN_MAX_K = 64
+KNN_MAX_K = L.KNN_MAX_K
 
 
 def _rows_f32(x: Tensor, what: str) -> tuple[int, int]:

@@ -38,9 +38,11 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from . import _lib as L
+
 __all__ = ["compute_pca", "StandardScaler", "PCA", "pca_from_moments", "scale_from_moments", "PcaFit"]
 
-MAX_FEATURES = 4096  # PCA_MAX_D of csrc/pca.hip
+MAX_FEATURES = L.PCA_MAX_D  # largest d the PCA and logistic-regression kernels serve
 META_COLUMNS = ("id", "fov_name", "t", "track_id")  # the reference's pca_dict order
 
 

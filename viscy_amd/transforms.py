@@ -18,6 +18,7 @@ torch's generator (RNG streams of kornia / MONAI cannot be reproduced); every tr
 
 from __future__ import annotations
 
+import ctypes
 import math
 
 from typing import Iterable, Sequence
@@ -882,7 +883,7 @@ def row_select(x: Tensor, ranks: Sequence[int]) -> Tensor:
     if not (_dev_ok(x) and x.ndim == 2):
         raise RuntimeError("row_select needs a contiguous float32 (rows, n) tensor on the HIP device (no CPU fallback)")
     rows, n = x.shape
-    rk = (L._I64 * len(ranks))(*[int(r) for r in ranks])
+    rk = (ctypes.c_int64 * len(ranks))(*[int(r) for r in ranks])
     nbytes = lib().vsx_row_select_ws_bytes(rows, len(ranks))
     ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=x.device)
     out = torch.empty((rows, len(ranks)), dtype=torch.float32, device=x.device)
