@@ -874,6 +874,41 @@ int32_t vsx_wcolsum(const float* x, int64_t n, int32_t d, const double* v, int32
 int32_t vsx_gram_scaled(const float* x, int64_t n, int32_t d, const double* mean, const float* q, double* gram, void* ws, int64_t ws_bytes,
     vsx_stream_t stream);
 
+/* The device passes of the temporal-smoothness evaluation (csrc/smoothness.hip; viscy_utils/evaluation/smoothness.py
+ * compute_embeddings_smoothness and find_distribution_peak, viscy_utils/evaluation/distance.py compute_track_displacement).  No atomics;
+ * every output is a pure function of the inputs, bit-identical from run to run.  Every check runs before any launch; anything not served
+ * is refused with a non-zero status.
+ * standardize: z_ij = fl32( double(fl32(double(x_ij) - mean_j)) / scale_j ), IEEE float64 subtraction and division: what sklearn's
+ *   StandardScaler.transform does to a float32 matrix with its float64 mean_ and scale_ (X -= mean_; X /= scale_).  x, z [n, d] fp32
+ *   row-major, any 4-byte alignment, z may be x; mean, scale [d] float64; n >= 1, d >= 1.
+ * pair_dist: out[p] float64 = the distance of rows u = x[pi[p]] and v = x[pj[p]] of x [n, d] fp32 (any 4-byte alignment; one 16-byte read
+ *   per four features where d % 4 == 0 and x is 16-byte aligned, else scalar reads of the same features into the same lanes).  One wave per
+ *   pair.  ONE summation order for every alignment, vsx_logreg_rows': lane l adds features 4 l .. 4 l + 3, 256 + 4 l .. in ascending order
+ *   from 0.0, then the 64 lane sums s are added by the xor butterfly, s_l <- s_l + s_(l xor o) for o = 32, 16, .. 1.
+ *     metric VSX_PAIR_COSINE     uv = sum u_c v_c, uu = sum u_c^2, vv = sum v_c^2 in float64 (each product is exact, so fma = mul, add);
+ *                                out = 1 - uv / (max(sqrt(uu), eps) * max(sqrt(vv), eps)), the product, division and difference each rounded
+ *                                once.  eps = 0: a zero row gives 0 / 0 = NaN (scipy's cdist); eps = 1e-12: F.normalize's rule, distance 1.
+ *     metric VSX_PAIR_EUCLIDEAN  out = sqrt(sum (u_c - v_c)^2): the float64 difference, its square and the add are rounded separately
+ *                                (no fma); eps is not read.  i == j gives exactly 0.
+ *   1 <= P < 2^33, 1 <= n < 2^31, d >= 1, eps >= 0.  A pair with an index outside [0, n) reads nothing and gets NaN.
+ * kde_gauss: out[g] = sum_i exp(-a (grid[g] - data[i])^2), float64 throughout, library exp; the normalisation 1 / (n sqrt(2 pi cov)) with
+ *   a = 1 / (2 cov) is the caller's.  data [n], grid [m], out [m] float64, 1 <= n < 2^31, 1 <= m <= 2^20.  A workgroup keeps a tile of
+ *   VSX_KDE_TILE grid points in registers and streams one chunk of data through LDS; a thread adds its chunk's terms in ascending i from
+ *   0.0; the per-chunk partials [chunks][m] go to ws and are added in ascending chunk order.  The chunk length is a whole number of slabs
+ *   of VSX_KDE_CHUNK data, chosen so that tiles x chunks is about 2048 workgroups, and is a function of (n, m) alone:
+ *   chunks = vsx_kde_gauss_ws_bytes(n, m) / (8 m); n <= VSX_KDE_CHUNK is one chunk.  ws: 8-byte aligned, any contents,
+ *   vsx_kde_gauss_ws_bytes(n, m) bytes (0 for shapes that are not served). */
+#define VSX_PAIR_COSINE 0
+#define VSX_PAIR_EUCLIDEAN 1
+#define VSX_KDE_TILE 512   /* grid points of a workgroup of vsx_kde_gauss */
+#define VSX_KDE_CHUNK 1024 /* data per LDS slab of vsx_kde_gauss; chunks are whole slabs */
+int32_t vsx_standardize(const float* x, const double* mean, const double* scale, float* z, int64_t n, int32_t d, vsx_stream_t stream);
+int32_t vsx_pair_dist(const float* x, int32_t n, const int32_t* pi, const int32_t* pj, int64_t P, int32_t d, int32_t metric, double eps,
+    double* out, vsx_stream_t stream);
+int64_t vsx_kde_gauss_ws_bytes(int64_t n, int64_t m);
+int32_t vsx_kde_gauss(const double* data, int64_t n, const double* grid, int64_t m, double a, double* out, void* ws, int64_t ws_bytes,
+    vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1447,3 +1447,56 @@ def logreg_rows(x: Tensor, w: Tensor, b: float, labels: Tensor, pos: int, cp: fl
                                 ptr(out.get("r")), ptr(out.get("s")), ptr(out.get("q")), ptr(out["sums"]), ptr(ws), ws.nbytes, stream()),
           "logreg_rows")
     return out
+
+
+# ------------------------------------------------------------------ temporal smoothness (csrc/smoothness.hip)
+PAIR_METRICS = {"cosine": L.PAIR_COSINE, "euclidean": L.PAIR_EUCLIDEAN}
+
+
+def standardize(x: Tensor, mean: Tensor, scale: Tensor, out: Tensor | None = None) -> Tensor:
+    """-> float32 (n, d): fl32(double(fl32(double(x) - mean)) / scale), sklearn's ``StandardScaler.transform`` of a float32 matrix
+    bit for bit; mean, scale float64 (d,).  ``out`` may be ``x`` (in place)"""
+    n, d = _rows_f32(x, "standardize")
+    _f64_vec(mean, d, "standardize: mean")
+    _f64_vec(scale, d, "standardize: scale")
+    if out is None:
+        out = torch.empty_like(x)
+    elif _rows_f32(out, "standardize: out") != (n, d):
+        raise TypeError(f"standardize: out must be a float32 ({n}, {d}) tensor, got {tuple(out.shape)}")
+    check(lib().vsx_standardize(ptr(x), ptr(mean), ptr(scale), ptr(out), n, d, stream()), "standardize")
+    return out
+
+
+def pair_dist(x: Tensor, pi: Tensor, pj: Tensor, metric: str = "cosine", eps: float = 0.0) -> Tensor:
+    """-> float64 (P,): the ``metric`` ("cosine" | "euclidean") distance of rows pi[p] and pj[p] of x float32 (n, d), float64 sums
+    in one fixed order.  Cosine: 1 - uv / (max(|u|, eps) max(|v|, eps)); ``eps=0`` is scipy's cdist (NaN for a zero row), ``1e-12``
+    is ``F.normalize``'s rule.  An index outside [0, n) gives NaN"""
+    n, d = _rows_f32(x, "pair_dist")
+    if metric not in PAIR_METRICS:
+        raise ValueError(f"pair_dist: metric {metric!r} must be 'cosine' or 'euclidean'")
+    if n >= 2 ** 31:  # the library takes n as int32: ctypes would wrap it silently
+        raise ValueError(f"pair_dist: x has {n} rows, the kernel serves fewer than 2^31")
+    p = pi.numel()
+    _i32(pi, p, "pair_dist: pi")
+    _i32(pj, p, "pair_dist: pj")
+    out = torch.empty(p, dtype=torch.float64, device=x.device)
+    if p:
+        check(lib().vsx_pair_dist(ptr(x), n, ptr(pi), ptr(pj), p, d, PAIR_METRICS[metric], float(eps), ptr(out), stream()), "pair_dist")
+    return out
+
+
+def kde_chunks(n: int, m: int) -> int:
+    """how many chunks ``kde_gauss`` splits n data into for m grid points: a function of (n, m) alone"""
+    return int(lib().vsx_kde_gauss_ws_bytes(int(n), int(m))) // (8 * int(m))
+
+
+def kde_gauss(data: Tensor, grid: Tensor, a: float) -> Tensor:
+    """-> float64 (m,): sum_i exp(-a (grid_g - data_i)^2) for data (n,), grid (m,) float64; fixed-order sums, bit-identical from run
+    to run.  The caller normalises (``1 / (n sqrt(2 pi cov))`` with ``a = 1 / (2 cov)``)"""
+    n, m = data.numel(), grid.numel()
+    _f64_vec(data, n, "kde_gauss: data")
+    _f64_vec(grid, m, "kde_gauss: grid")
+    ws = _ws(data.device, lib().vsx_kde_gauss_ws_bytes(n, m), torch.float64)
+    out = torch.empty(m, dtype=torch.float64, device=data.device)
+    check(lib().vsx_kde_gauss(ptr(data), n, ptr(grid), m, float(a), ptr(out), ptr(ws), ws.nbytes, stream()), "kde_gauss")
+    return out
