@@ -156,7 +156,7 @@ def test_every_refusal_fires_before_a_device_is_looked_for(monkeypatch):
     def no_device(*a, **k):
         raise AssertionError("a device was looked for")
 
-    monkeypatch.setattr(reduce, "_device", no_device)
+    monkeypatch.setattr(reduce, "device_of", no_device)
     rng = np.random.RandomState(0)
     X = rng.randn(6, 3).astype(np.float32)
     bad = X.copy()

@@ -41,10 +41,10 @@ from torch import Tensor, nn
 
 from . import _lib as L
 from .flat import CoreProxy
-from .unext2 import _Conv, _Core, _Encoder, _Holder, _LN, _Stem
+from .unext2 import Conv, Core, Encoder, Holder, LN, Stem
 
 
-class _BN(_Holder):
+class _BN(Holder):
     def __init__(self, c: int):
         super().__init__()
         self.weight = nn.Parameter(torch.ones(c))
@@ -54,15 +54,15 @@ class _BN(_Holder):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
 
-class _Tail(_Holder):
+class _Tail(Holder):
     def __init__(self, feat: int, embedding_dim: int, projection_dim: int):
         super().__init__()
-        self.norm = _LN(feat)
-        self.fc0, self.bn1 = _Conv((embedding_dim, feat)), _BN(embedding_dim)
-        self.fc3, self.bn4 = _Conv((projection_dim, embedding_dim)), _BN(projection_dim)
+        self.norm = LN(feat)
+        self.fc0, self.bn1 = Conv((embedding_dim, feat)), _BN(embedding_dim)
+        self.fc3, self.bn4 = Conv((projection_dim, embedding_dim)), _BN(projection_dim)
 
 
-class _EmbedCore(_Core):
+class _EmbedCore(Core):
     def __init__(self, in_channels, in_stack_depth, stem_kernel_size, depths, dims, embedding_dim, projection_dim, v1):
         super().__init__()
         kz = stem_kernel_size[0]
@@ -75,14 +75,14 @@ class _EmbedCore(_Core):
         self.cfg = dict(in_channels=in_channels, out_channels=0, in_stack_depth=in_stack_depth, out_stack_depth=0,
                         depths=tuple(depths), dims=tuple(dims), conv_mlp=False, stem_kernel=tuple(stem_kernel_size), ratio=ratio,
                         head="embed")
-        self.encoder_stages = _Encoder(depths, dims, False, v1=v1)
-        self.stem = _Stem(in_channels, dims[0] // ratio, tuple(stem_kernel_size))
+        self.encoder_stages = Encoder(depths, dims, False, v1=v1)
+        self.stem = Stem(in_channels, dims[0] // ratio, tuple(stem_kernel_size))
         self.tail = _Tail(dims[-1], embedding_dim, projection_dim)
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
         for name, mod in self.named_modules():
-            if isinstance(mod, _Conv) and name.startswith("encoder_stages"):  # timm _init_weights
+            if isinstance(mod, Conv) and name.startswith("encoder_stages"):  # timm _init_weights
                 nn.init.trunc_normal_(mod.weight, std=0.02)
                 nn.init.zeros_(mod.bias)
         for conv in (self.stem.conv, self.tail.fc0, self.tail.fc3):  # torch defaults (Conv3d / Linear)
@@ -115,11 +115,11 @@ class ContrastiveEncoder(CoreProxy, nn.Module):
             core.cfg["drop_path"] = torch.linspace(0, float(drop_path_rate), sum(depths)).tolist()
         object.__setattr__(self, "_core", core)  # NOT a registered submodule: its parameters appear below, under reference names
         self.stem = core.stem
-        enc = _Holder()
+        enc = Holder()
         enc.stem = nn.Sequential(nn.Identity(), core.encoder_stages.stem_1)
         enc.stages = nn.Sequential(*[getattr(core.encoder_stages, f"stages_{i}") for i in range(4)])
         enc.norm_pre = nn.Identity()
-        head = _Holder()
+        head = Holder()
         head.norm = core.tail.norm
         enc.head = head
         self.encoder = enc

@@ -23,11 +23,6 @@
 #define LR_WANT_WGS 2048     // eight workgroups per compute unit
 #define LR_MIN_ROWS 16       // rows per workgroup at least: w is staged once for them
 
-__device__ __forceinline__ double lr_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // FULL: labels, loss and derivatives; else the margins alone.  part [workgroup][3] = the run's {sum loss, sum r, sum s}: lane l of
 // a wave adds rows l, 64 + l, .. of the wave's run in ascending order, the lanes are added by the butterfly, the waves 0 .. 3
 template <bool VEC, bool FULL>
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(LR_WAVES * 64) void lr_rows_kernel(const float* __r
         if (VEC || c + 2 < d) acc = fma((double)v.z, lr_w[c + 2], acc);
         if (VEC || c + 3 < d) acc = fma((double)v.w, lr_w[c + 3], acc);
       }
-      const double dot = lr_wave_sum(acc) + b;
+      const double dot = wave_sum_f64(acc) + b;
       if (lane == j) zi = dot;
     }
     if (lane < cnt) {
@@ -83,7 +78,7 @@ __global__ __launch_bounds__(LR_WAVES * 64) void lr_rows_kernel(const float* __r
     }
   }
   if (FULL && part) {
-    t_loss = lr_wave_sum(t_loss), t_r = lr_wave_sum(t_r), t_s = lr_wave_sum(t_s);
+    t_loss = wave_sum_f64(t_loss), t_r = wave_sum_f64(t_r), t_s = wave_sum_f64(t_s);
     if (lane == 0) red[0][wave] = t_loss, red[1][wave] = t_r, red[2][wave] = t_s;
     __syncthreads();
     if (threadIdx.x < 3) {
@@ -100,7 +95,7 @@ __global__ __launch_bounds__(192) void lr_sums_fold_kernel(const double* __restr
   const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
   double tot = 0.0;
   for (int g = lane; g < wgs; g += 64) tot += part[(size_t)g * 3 + k];
-  tot = lr_wave_sum(tot);
+  tot = wave_sum_f64(tot);
   if (lane == 0) sums[k] = tot;
 }
 

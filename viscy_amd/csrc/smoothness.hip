@@ -22,11 +22,6 @@
 #define KD_WANT_WGS 2048           // eight workgroups per compute unit
 static_assert(KD_TILE == KD_THREADS * KD_GP, "a workgroup's grid tile is its threads' registers");
 
-__device__ __forceinline__ double sm_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // acc + (u - v)^2 with the difference, the square and the add each rounded once.  The __dmul_rn / __dadd_rn of this toolchain are
 // plain operators, which the compiler's default contraction would fuse into one fma: the pragma is what keeps them apart
 __device__ __forceinline__ double sm_add_sqdiff(double acc, double u, double v) {
@@ -78,8 +73,8 @@ __global__ __launch_bounds__(SM_WAVES * 64) void sm_pair_kernel(const float* __r
         }
       }
     }
-    uu = sm_wave_sum(uu);
-    if (METRIC == 0) uv = sm_wave_sum(uv), vv = sm_wave_sum(vv);
+    uu = wave_sum_f64(uu);
+    if (METRIC == 0) uv = wave_sum_f64(uv), vv = wave_sum_f64(vv);
     if (lane == 0) {
       if (METRIC == 0) {
         const double nu = fmax(sqrt(uu), eps), nv = fmax(sqrt(vv), eps);

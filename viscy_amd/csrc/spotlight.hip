@@ -126,12 +126,6 @@ __device__ __forceinline__ void sl_add(SlAcc& a, float p, float t, float m, cons
   a.I = fmaf(s, m, a.I);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------ forward: per-chunk partials of the five sums
 template <typename TP, int MODE>
 __global__ __launch_bounds__(SL_THREADS) void spotlight_sums_kernel(const TP* __restrict__ P, const float* __restrict__ T,

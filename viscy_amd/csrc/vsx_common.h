@@ -284,6 +284,12 @@ __device__ __forceinline__ float group_sum(float v) {  // sum over aligned group
   return v;
 }
 __device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
+// float64 wave total in every lane: the __shfl_xor butterfly from 32 down to 1.  The order is part of the result of the float64
+// reductions that use it (logreg.hip, smoothness.hip, spotlight.hip): keep it.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 // wave total delivered to lane 63 only, without LDS traffic: the two row-crossing steps are the gfx9 DPP row broadcasts
 // (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) instead of two ds_bpermute + s_waitcnt.  For
 // reductions whose result one lane accumulates (head_out_bwd1: 64 of them per voxel).

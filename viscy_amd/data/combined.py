@@ -198,7 +198,7 @@ class BatchedConcatDataset(ConcatDataset):
         return d, idx if d == 0 else idx - self.cumulative_sizes[d - 1]
 
     def __getitems__(self, indices: list[int]) -> list[dict]:
-        from .hcs import _collate_samples
+        from .hcs import collate_samples
 
         grouped = defaultdict(list)
         for idx in indices:
@@ -207,7 +207,7 @@ class BatchedConcatDataset(ConcatDataset):
         out = []
         for d, sample_indices in grouped.items():
             ds = self.datasets[d]
-            mb = ds.__getitems__(sample_indices) if hasattr(ds, "__getitems__") else _collate_samples([ds[i] for i in sample_indices])
+            mb = ds.__getitems__(sample_indices) if hasattr(ds, "__getitems__") else collate_samples([ds[i] for i in sample_indices])
             mb["_dataset_idx"] = d
             out.append(mb)
         return out
@@ -264,15 +264,15 @@ class ConcatDataModule(_DMBase):
                 "pin_memory": self.pin_memory and torch.cuda.is_available()}
 
     def train_dataloader(self):
-        from .hcs import _collate_samples
+        from .hcs import collate_samples
 
         return DataLoader(self.train_dataset, shuffle=True, batch_size=self.batch_size // max(self.train_patches_per_stack, 1),
-                          collate_fn=_collate_samples, drop_last=True, **self._dataloader_kwargs())
+                          collate_fn=collate_samples, drop_last=True, **self._dataloader_kwargs())
 
     def val_dataloader(self):
-        from .hcs import _collate_samples
+        from .hcs import collate_samples
 
-        return DataLoader(self.val_dataset, shuffle=False, batch_size=self.batch_size, drop_last=False, collate_fn=_collate_samples,
+        return DataLoader(self.val_dataset, shuffle=False, batch_size=self.batch_size, drop_last=False, collate_fn=collate_samples,
                           **self._dataloader_kwargs())
 
     def on_after_batch_transfer(self, batch, dataloader_idx: int):

@@ -292,7 +292,7 @@ class SlidingWindowDataset(Dataset):
         return [build(im) for im in images] if isinstance(images, list) else build(images)
 
 
-def _collate_samples(batch):
+def collate_samples(batch):
     """viscy_data/_utils.py:112-136: flatten per-stack lists of patches, stack tensors, keep indices as lists."""
     flat = []
     for b in batch:
@@ -537,7 +537,7 @@ class HCSDataModule(_DMBase):
             sampler = DistributedSampler(ds, shuffle=shuffle, seed=self.seed, drop_last=drop_last)
             shuffle = False
         return DataLoader(ds, batch_size=batch_size, num_workers=self.num_workers, shuffle=shuffle, sampler=sampler,
-                          drop_last=drop_last, collate_fn=_collate_samples, pin_memory=self.pin_memory and torch.cuda.is_available(),
+                          drop_last=drop_last, collate_fn=collate_samples, pin_memory=self.pin_memory and torch.cuda.is_available(),
                           persistent_workers=self.persistent_workers and self.num_workers > 0,
                           prefetch_factor=self.prefetch_factor if self.num_workers else None)
 

@@ -11,7 +11,7 @@ checkpoints load with ``strict=True`` — the reference's ``state_dict()`` keys,
 
 Arithmetic: the dense FCMAE network is the UNeXt2 schedule with a different parameter naming, explicit encoder widths
 (``nn.Linear`` MLPs) and — unless ``head_conv`` — the parameter-free ``PixelToVoxelShuffleHead`` (``vsx_voxel_shuffle_*``).
-The reference-named tree below shares its ``nn.Parameter`` objects with the engine's own tree (``viscy_amd.unext2._Core``),
+The reference-named tree below shares its ``nn.Parameter`` objects with the engine's own tree (``viscy_amd.unext2.Core``),
 so the flat-buffer engine, the fused AdamW and the data-parallel all-reduce work unchanged.  Sparse masked pre-training
 (``mask_ratio > 0``) runs the same kernel schedule with the kept tokens of every encoder block gathered into compact row
 matrices (``vsx_rows_select``; see ``stage_row_maps``).
@@ -26,17 +26,17 @@ import torch
 from torch import Tensor, nn
 
 from .flat import CoreProxy
-from .unext2 import _Conv, _Core, _Holder
+from .unext2 import Conv, Core, Holder
 
 
-class _FcmaeCore(_Core):
+class _FcmaeCore(Core):
     def __init__(self, in_channels, out_channels, encoder_blocks, dims, stem_kernel_size, in_stack_depth, decoder_conv_blocks,
                  head_conv, head_conv_expansion_ratio, head_conv_pool):
         super().__init__()
         # MaskedAdaptiveProjection.conv2d (fcmae.py:348-353): the stem of Z == 1 inputs.  A parameter of the core, so it lives
         # in the engine's flat buffers and trains like the rest; registered FIRST = next to the 3-D stem at the tail of the
         # (reverse-forward-order) flat buffer, i.e. in the gradient bucket that is reduced last.
-        self.stem2d = _Conv((dims[0], in_channels, stem_kernel_size[1], stem_kernel_size[2]))
+        self.stem2d = Conv((dims[0], in_channels, stem_kernel_size[1], stem_kernel_size[2]))
         nn.init.trunc_normal_(self.stem2d.weight, std=0.02)
         self._build(in_channels=in_channels, out_channels=out_channels, in_stack_depth=in_stack_depth,
                     out_stack_depth=in_stack_depth, depths=tuple(encoder_blocks), dims=tuple(dims), conv_mlp=False,
@@ -45,25 +45,25 @@ class _FcmaeCore(_Core):
                     head_expansion_ratio=head_conv_expansion_ratio)
 
 
-def _share(src: nn.Module) -> _Holder:
+def _share(src: nn.Module) -> Holder:
     """a holder whose ``weight`` / ``bias`` ARE the parameters of ``src`` (same objects, other name)"""
-    h = _Holder()
+    h = Holder()
     h.weight, h.bias = src.weight, src.bias
     return h
 
 
-class _BlockView(_Holder):
+class _BlockView(Holder):
     def __init__(self, blk):
         super().__init__()
         self.dwconv = _share(blk.conv_dw)
         self.layernorm = _share(blk.norm)
-        mlp = _Holder()
+        mlp = Holder()
         mlp.fc1, mlp.grn, mlp.fc2 = _share(blk.mlp.fc1), _share(blk.mlp.grn), _share(blk.mlp.fc2)
         self.mlp = mlp
         self.drop_path, self.shortcut = nn.Identity(), nn.Identity()
 
 
-class _StageView(_Holder):
+class _StageView(Holder):
     def __init__(self, st):
         super().__init__()
         if isinstance(st.downsample, nn.Identity):
@@ -136,7 +136,7 @@ class FullyConvolutionalMAE(CoreProxy, nn.Module):
         if encoder_drop_path_rate:  # fcmae.py:404-414: the SAME rate for every encoder block (published recipes: 0.1)
             core.cfg["drop_path"] = [float(encoder_drop_path_rate)] * sum(encoder_blocks)
         object.__setattr__(self, "_core", core)  # NOT a registered submodule: its parameters appear below, under reference names
-        enc, stem = _Holder(), _Holder()
+        enc, stem = Holder(), Holder()
         stem.conv3d = _share(core.stem.conv)
         stem.conv2d = _share(core.stem2d)  # Z == 1 inputs (fcmae.py:369-370)
         stem.norm = _share(core.encoder_stages.stem_1)

@@ -28,6 +28,9 @@ i.e. at the optimum to float64, whatever ``tol`` (liblinear's own rule with ``to
 ``n_iter_`` counts Newton iterations; ``decision_function`` and the probabilities are float64; there is no CPU path for the data
 passes (``RuntimeError`` without a HIP device); d > 4096 raises ``NotImplementedError``.
 
+Input checks, the device rule, the single-row rule and the shared draw of the stratified split are ``evalkit``'s; the projection
+kernel's wrapper and the width limit are ``reduce.project`` / ``reduce.served``.
+
 ``adata`` is duck-typed (``.X``, ``.obs`` DataFrame, and ``.obsm`` / ``.uns`` mappings for predict).  ``load_and_combine_datasets``
 and the two wandb functions of the reference module are not here: they are anndata / wandb plumbing.
 """
@@ -43,8 +46,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .online_eval import _approximate_mode, average_ranks
-from .reduce import PCA, StandardScaler, _device, _project, _rows, _served, _to_device
+from .evalkit import as_matrix, average_ranks, device_of, padded_to_two_rows, stratified_shuffle_parts, to_device, upload
+from .reduce import PCA, StandardScaler, project, served
 
 __all__ = ["LogisticRegression", "LinearClassifierPipeline", "train_linear_classifier", "predict_with_classifier", "newton_fit",
            "NewtonResult", "class_weights", "stratified_split", "group_shuffle_split", "classification_report", "roc_auc"]
@@ -174,30 +177,20 @@ def class_weights(class_weight, classes: np.ndarray, y_idx: np.ndarray) -> np.nd
 def stratified_split(y, train_size: float, seed: int) -> tuple[np.ndarray, np.ndarray]:
     """-> (train, test) row indices of ``train_test_split(..., train_size=train_size, random_state=seed, stratify=y,
     shuffle=True)``, in sklearn's order: ``n_train = floor(train_size n)``, the rest is the test part; class allocations by
-    ``_approximate_mode``, one permutation per class, then one of each part.  numpy's legacy ``RandomState`` stream is frozen, so
-    the restatement draws what sklearn draws."""
+    ``approximate_mode`` and one permutation per class (``evalkit.stratified_shuffle_parts``), then one of each part."""
     y = np.asarray(y)
     n = len(y)
     n_train = int(np.floor(train_size * n))
     n_test = n - n_train
-    classes, y_idx = np.unique(y, return_inverse=True)
-    y_idx = y_idx.reshape(-1)
-    counts = np.bincount(y_idx)
+    classes, counts = np.unique(y, return_counts=True)
     if n_train < 1 or n_test < 1:
         raise ValueError(f"train_size={train_size} leaves an empty part of {n} rows")
     if counts.min() < 2:
         raise ValueError("The least populated class in y has only 1 member, which is too few.")
     if n_train < len(classes) or n_test < len(classes):
         raise ValueError(f"train ({n_train}) and test ({n_test}) parts must each hold at least one row per class ({len(classes)})")
-    class_indices = np.split(np.argsort(y_idx, kind="mergesort"), np.cumsum(counts)[:-1])
     rng = np.random.RandomState(seed)
-    n_i = _approximate_mode(counts, n_train, rng)
-    t_i = _approximate_mode(counts - n_i, n_test, rng)
-    train, test = [], []
-    for c in range(len(classes)):
-        perm = class_indices[c].take(rng.permutation(counts[c]), mode="clip")
-        train.extend(perm[: n_i[c]])
-        test.extend(perm[n_i[c]: n_i[c] + t_i[c]])
+    train, test = stratified_shuffle_parts(y, n_train, n_test, rng)
     return rng.permutation(train), rng.permutation(test)
 
 
@@ -275,7 +268,7 @@ class _DeviceObjective:
     def __call__(self, w, b, want_hessian):
         from . import ops
 
-        wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.x.device)
+        wd = upload(w, self.x.device, np.float64)
         out = ops.logreg_rows(self.x, wd, float(b), self.labels, self.pos, self.cp, self.cn, derivatives=bool(want_hessian))
         if not want_hessian:
             return float(out["sums"][0]), None, None, None, None, None
@@ -332,7 +325,7 @@ class LogisticRegression:
         return min(float(self.tol) * max(min(n_pos, n - n_pos), 1) / n, 1e-10)
 
     def fit(self, X, y, sample_weight=None):
-        X = _rows(X)
+        X = as_matrix(X, min_rows=2, min_cols=1)
         y = np.asarray(y)
         if y.ndim != 1 or len(y) != X.shape[0]:
             raise ValueError(f"y {y.shape} must hold one label per row of X {tuple(X.shape)}")
@@ -341,10 +334,10 @@ class LogisticRegression:
         if len(classes) < 2:
             raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {classes[0]!r}")
         self._check_served(len(classes), sample_weight)
-        _served(X.shape[1])
-        x = _to_device(X, _device(X))
+        served(X.shape[1])
+        x = to_device(X, device_of(X, who="reduce"))
         n, d = x.shape
-        labels = torch.from_numpy(y_idx.astype(np.int32)).to(x.device)
+        labels = upload(y_idx, x.device, np.int32)
         liblinear = self.solver == "liblinear"
         results = []
         for pos, cp, cn in self.problems(classes, y_idx):
@@ -365,18 +358,13 @@ class LogisticRegression:
 
         if not hasattr(self, "coef_"):
             raise RuntimeError("this LogisticRegression is not fitted yet")
-        X = X.detach() if torch.is_tensor(X) else np.asarray(X)
-        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"X {tuple(X.shape)} must be (rows, {self.n_features_in_})")
-        x = _to_device(X, _device(X))
+        X = as_matrix(X, width=self.n_features_in_, finite=False)
+        x = to_device(X, device_of(X, who="reduce"))
         if x.shape[0] == 0:
             return np.zeros((0, len(self.coef_)))
-        one = x.shape[0] == 1   # the kernels serve n >= 2: a single row rides with a copy of itself
-        if one:
-            x = torch.cat((x, x))
-        z = [ops.logreg_margins(x, torch.from_numpy(np.ascontiguousarray(w)).to(x.device), float(b)) for w, b in zip(self.coef_, self.intercept_)]
-        z = torch.stack(z, dim=1).cpu().numpy()
-        return z[:1] if one else z
+        x, n = padded_to_two_rows(x)
+        z = [ops.logreg_margins(x, upload(w, x.device), float(b)) for w, b in zip(self.coef_, self.intercept_)]
+        return torch.stack(z, dim=1).cpu().numpy()[:n]
 
     def decision_function(self, X) -> np.ndarray:
         z = self._margins(X)
@@ -405,11 +393,11 @@ class LogisticRegression:
 
 # ------------------------------------------------------------------------------------------------ the reference module's surface
 def _scale_on_device(scaler: StandardScaler, x: Tensor) -> Tensor:
-    return _project(x, scaler.mean_, np.ascontiguousarray(np.diag(1.0 / scaler.scale_).astype(np.float32)))
+    return project(x, scaler.mean_, scaler.projection_weights())
 
 
 def _reduce_on_device(pca: PCA, x: Tensor) -> Tensor:
-    return _project(x, pca.fit_.data_mean, pca.fit_.projection_weights())
+    return project(x, pca.fit_.data_mean, pca.fit_.projection_weights())
 
 
 class LinearClassifierPipeline:
@@ -420,16 +408,13 @@ class LinearClassifierPipeline:
 
     def _transform(self, X) -> Tensor:
         """the preprocessing on the device: X goes there once and stays"""
-        X = X.detach() if torch.is_tensor(X) else np.asarray(X)
-        x = _to_device(X, _device(X))
-        one = x.shape[0] == 1
-        if one:
-            x = torch.cat((x, x))
+        X = as_matrix(X, finite=False)
+        x, n = padded_to_two_rows(to_device(X, device_of(X, who="reduce")))
         if self.scaler is not None:
             x = _scale_on_device(self.scaler, x)
         if self.pca is not None:
             x = _reduce_on_device(self.pca, x)
-        return x[:1] if one else x
+        return x[:n]
 
     def transform(self, X) -> np.ndarray:
         return self._transform(X).cpu().numpy()
@@ -476,8 +461,8 @@ def train_linear_classifier(adata, task: str, use_scaling: bool = True, use_pca:
     classifier_params = {} if classifier_params is None else classifier_params
     X_full = adata.X if isinstance(adata.X, np.ndarray) or torch.is_tensor(adata.X) else adata.X.toarray()
     y_full = adata.obs[task].to_numpy(dtype=object)
-    X_full = _rows(X_full)
-    x = _to_device(X_full, _device(X_full))
+    X_full = as_matrix(X_full, min_rows=2, min_cols=1)
+    x = to_device(X_full, device_of(X_full, who="reduce"))
     scaler = pca = None
     if use_scaling:
         scaler = StandardScaler().fit(x)

@@ -31,7 +31,7 @@ def _npix_cached(dims, C, dev):
     return t
 
 
-class _MixedLossFn(torch.autograd.Function):
+class MixedLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, preds: Tensor, target: Tensor, a1: float, a2: float, a3: float):
         if preds.shape != target.shape or preds.ndim != 5:
@@ -159,7 +159,7 @@ class MixedLoss(nn.Module):
         if not preds.is_cuda:
             raise RuntimeError("viscy_amd.MixedLoss runs on MI355X HIP kernels only (no CPU / eager fallback)")
         L.lib()
-        return _MixedLossFn.apply(preds, target, float(self.l1_alpha), float(self.l2_alpha), float(self.ms_dssim_alpha))
+        return MixedLossFn.apply(preds, target, float(self.l1_alpha), float(self.l2_alpha), float(self.ms_dssim_alpha))
 
 
 class _MaskedMSEFn(torch.autograd.Function):
@@ -224,7 +224,7 @@ class _SpotlightFn(torch.autograd.Function):
         else:
             thr = O.otsu_threshold(T)
         loss, coef = O.spotlight_fwd(P, T, M, thr, lambda_mse=lambda_mse, sigmoid_k=sigmoid_k, eps=eps)
-        # scratch this Function alone writes and reads (detached, never exposed): plain attributes, as in _MixedLossFn
+        # scratch this Function alone writes and reads (detached, never exposed): plain attributes, as in MixedLossFn
         ctx.saved = (P, T, M, thr, coef, sigmoid_k, pred.dtype)
         return loss
 

@@ -15,7 +15,8 @@ draw as the reference: ``default_rng(0).choice`` for the median heuristic's subs
 per permutation, the first ``n`` entries of which form the X group.
 
 Inputs are numpy arrays or torch tensors; a tensor already on the device is used in place.  There is no CPU path: without a HIP
-device the functions raise ``RuntimeError``.
+device the functions raise ``RuntimeError``.  The input checks and the device rule are ``evalkit``'s (``as_matrix`` without a row or
+column minimum: the two-rows-a-side rule of the unbiased estimate is checked here).
 
 Deliberate differences from the reference:
 
@@ -32,28 +33,13 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from .evalkit import as_matrix, device_of, to_device
+
 __all__ = ["median_heuristic", "gaussian_rbf_kernel", "compute_mmd_unbiased", "mmd_permutation_test", "permutation_labels"]
 
 
-def _rows(a, name: str):
-    """a 2-D numpy array or tensor of finite values (checked where it lives)"""
-    if torch.is_tensor(a):
-        a = a.detach()
-        if a.dim() != 2:
-            raise ValueError(f"{name} must be a (rows, d) matrix, got {tuple(a.shape)}")
-        if not bool(torch.isfinite(a).all()):
-            raise ValueError("Input X contains NaN or infinity.")
-        return a
-    a = np.asarray(a)
-    if a.ndim != 2:
-        raise ValueError(f"{name} must be a (rows, d) matrix, got {a.shape}")
-    if not np.isfinite(a).all():
-        raise ValueError("Input X contains NaN or infinity.")
-    return a
-
-
 def _pair(X, Y):
-    X, Y = _rows(X, "X"), _rows(Y, "Y")
+    X, Y = as_matrix(X, "X"), as_matrix(Y, "Y")
     if X.shape[1] != Y.shape[1]:
         raise ValueError(f"X {tuple(X.shape)} and Y {tuple(Y.shape)} differ in width")
     return X, Y
@@ -66,22 +52,12 @@ def _bandwidth(bandwidth) -> float:
     return bandwidth
 
 
-def _device(*arrays) -> torch.device:
-    for a in arrays:
-        if torch.is_tensor(a) and a.is_cuda:
-            return a.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("viscy_amd.mmd needs the HIP device (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_device(a, dev: torch.device) -> Tensor:
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float32))  # a copy: the caller's array may be read-only
-    return t.to(device=dev, dtype=torch.float32)
+def _device(X, Y) -> torch.device:
+    return device_of(X, Y, who="mmd")
 
 
 def _pool(X, Y, dev: torch.device) -> Tensor:
-    return torch.cat((_to_device(X, dev), _to_device(Y, dev)), dim=0).contiguous()
+    return torch.cat((to_device(X, dev), to_device(Y, dev)), dim=0)
 
 
 def permutation_labels(n: int, m: int, n_permutations: int, seed: int) -> np.ndarray:

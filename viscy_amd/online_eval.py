@@ -9,7 +9,8 @@ The reference computes the three on the host (sklearn's brute-force k-NN once pe
 Here the k-NN probe is one pass of ``vsx_knn_topk`` for all folds at once: a fold is a *group*, and a row's candidates are the
 rows of the other groups, which is exactly "fit on the other folds, predict this one"; the N x N similarity matrix is never
 stored.  The splits themselves are O(N) host work and restate sklearn's draw for draw (``stratified_kfold_ids``,
-``stratified_holdout_ids``), so the folds are the reference's folds.
+``stratified_holdout_ids``), so the folds are the reference's folds.  The holdout's draw and the tie-averaged ranks are ``evalkit``'s
+(``stratified_shuffle_parts``, ``average_ranks``), shared with ``linear_classifier``.
 
 Differences from the reference, all at its edges:
 
@@ -32,6 +33,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 from torch import Tensor
+
+from .evalkit import as_matrix, average_ranks, stratified_shuffle_parts, to_device, upload
 
 _logger = logging.getLogger("viscy_amd")
 
@@ -57,51 +60,23 @@ def stratified_kfold_ids(labels, n_splits: int) -> np.ndarray:
     return folds
 
 
-def _approximate_mode(class_counts: np.ndarray, n_draws: int, rng: np.random.RandomState) -> np.ndarray:
-    """sklearn.utils.extmath._approximate_mode: proportional allocation, remainders by size, exact ties by ``rng.choice``"""
-    continuous = class_counts / class_counts.sum() * n_draws
-    floored = np.floor(continuous)
-    need = int(n_draws - floored.sum())
-    if need > 0:
-        remainder = continuous - floored
-        for value in np.sort(np.unique(remainder))[::-1]:
-            (inds,) = np.where(remainder == value)
-            add = min(len(inds), need)
-            inds = rng.choice(inds, size=add, replace=False)
-            floored[inds] += 1
-            need -= add
-            if need == 0:
-                break
-    return floored.astype(int)
-
-
 def stratified_holdout_ids(labels, test_size: float, seed: int = 0) -> np.ndarray:
     """1 for the rows ``train_test_split(..., test_size=test_size, stratify=labels, random_state=seed)`` puts into the test part,
     0 for its train part.  That split is one draw of ``StratifiedShuffleSplit``: ``n_test = ceil(test_size * n)``, class
-    allocations by ``_approximate_mode``, then one ``RandomState.permutation`` per class.  numpy's legacy ``RandomState`` stream is
-    frozen, so the restatement draws what sklearn draws."""
+    allocations and one permutation per class by ``evalkit.stratified_shuffle_parts``."""
     y = np.asarray(labels)
     n = len(y)
     n_test = int(math.ceil(test_size * n))
     n_train = n - n_test
-    _, y_idx = np.unique(y, return_inverse=True)
-    y_idx = y_idx.reshape(-1)
-    counts = np.bincount(y_idx)
+    counts = np.unique(y, return_counts=True)[1]
     n_classes = len(counts)
     if counts.min() < 2:
         raise ValueError("The least populated class has only 1 member: a stratified holdout needs 2 per class")
     if n_train < n_classes or n_test < n_classes:
         raise ValueError(f"train ({n_train}) and test ({n_test}) parts must each hold at least one row per class ({n_classes})")
-    class_indices = np.split(np.argsort(y_idx, kind="mergesort"), np.cumsum(counts)[:-1])
-    rng = np.random.RandomState(seed)
-    n_i = _approximate_mode(counts, n_train, rng)
-    t_i = _approximate_mode(counts - n_i, n_test, rng)
-    ids = np.zeros(n, dtype=np.int64)
-    ids[:] = -1
-    for c in range(n_classes):
-        perm = class_indices[c].take(rng.permutation(counts[c]), mode="clip")
-        ids[perm[: n_i[c]]] = 0
-        ids[perm[n_i[c]: n_i[c] + t_i[c]]] = 1
+    train, test = stratified_shuffle_parts(y, n_train, n_test, np.random.RandomState(seed))
+    ids = np.full(n, -1, dtype=np.int64)
+    ids[train], ids[test] = 0, 1
     assert (ids >= 0).all()  # n_train + n_test = n: every row lands in one part
     return ids
 
@@ -125,29 +100,6 @@ def track_pairs(track_ids, min_track_len: int = 2) -> tuple[np.ndarray, np.ndarr
     return pi, pj
 
 
-def average_ranks(t):
-    """tie-averaged ranks 1 .. n as ``scipy.stats.rankdata`` (float64); a torch tensor is ranked on its device (sort +
-    ``unique_consecutive``), anything else with numpy"""
-    if torch.is_tensor(t):
-        v, order = torch.sort(t.reshape(-1))
-        _, inverse, counts = torch.unique_consecutive(v, return_inverse=True, return_counts=True)
-        last = torch.cumsum(counts, 0).to(torch.float64)
-        avg = last - (counts.to(torch.float64) - 1.0) / 2.0
-        ranks = torch.empty(v.numel(), dtype=torch.float64, device=t.device)
-        ranks[order] = avg[inverse]
-        return ranks
-    a = np.asarray(t).reshape(-1)
-    order = np.argsort(a, kind="stable")
-    v = a[order]
-    new = np.concatenate(([True], v[1:] != v[:-1]))
-    inverse = np.cumsum(new) - 1
-    counts = np.bincount(inverse)
-    avg = np.cumsum(counts) - (counts - 1) / 2.0
-    ranks = np.empty(len(a), dtype=np.float64)
-    ranks[order] = avg[inverse]
-    return ranks
-
-
 def spearman_rho(a, b) -> float:
     """Spearman's rho: the Pearson correlation of the two tie-averaged rank vectors, in float64 (NaN for a constant vector)"""
     ra, rb = average_ranks(a), average_ranks(b)
@@ -167,13 +119,11 @@ def knn_predict(features: Tensor, labels, group, k: int) -> tuple[Tensor, Tensor
     ``k`` cosine-nearest rows among the other groups (``group >= 0`` and different from the row's), and the encoded labels"""
     from . import ops
 
-    if not bool(torch.isfinite(features).all()):
-        raise ValueError("Input X contains NaN or infinity.")  # sklearn's check_array message
+    features = as_matrix(features)  # non-finite values: sklearn's check_array message
     classes, y = np.unique(np.asarray(labels), return_inverse=True)
-    x = features.detach().to(torch.float32).contiguous()
-    dev = x.device
-    y_d = torch.from_numpy(y.reshape(-1).astype(np.int32)).to(dev)
-    g_d = torch.from_numpy(np.asarray(group).reshape(-1).astype(np.int32)).to(dev)
+    x = to_device(features, features.device)
+    y_d = upload(y.reshape(-1), x.device, np.int32)
+    g_d = upload(np.asarray(group).reshape(-1), x.device, np.int32)
     inv = ops.row_inv_norm(x, 0.0)
     idx, _, cnt = ops.knn_topk(x, inv, g_d, k)
     return ops.knn_vote(idx, cnt, y_d), y_d, classes
@@ -184,7 +134,7 @@ def knn_accuracy(features: Tensor, labels, group, k: int, score_groups: Sequence
     the fold ids and every fold is scored (``cross_val_score(...).mean()``); holdout: ``group`` = 0 (train) / 1 (test) and only
     group 1 is scored.  A group with fewer than ``k`` candidate rows votes among those there are."""
     pred, y, _ = knn_predict(features, labels, group, k)
-    g_d = torch.from_numpy(np.asarray(group).reshape(-1).astype(np.int64)).to(pred.device)
+    g_d = upload(np.asarray(group).reshape(-1), pred.device, np.int64)
     hit = (pred == y).to(torch.float64)
     accs = torch.stack([hit[g_d == int(g)].mean() for g in score_groups])
     return float(accs.mean().item())
@@ -230,13 +180,13 @@ def temporal_smoothness(features: Tensor, track_ids, timepoints) -> float:
     pi, pj = track_pairs(track_ids)
     if len(pi) < 3:
         return float("nan")
-    x = features.detach().to(torch.float32).contiguous()
+    x = to_device(features.detach(), features.device)
     t = np.asarray(timepoints).reshape(-1).astype(np.float64)
     dt = np.abs(t[pi] - t[pj])
     inv = ops.row_inv_norm(x, 1e-10)
     dev = x.device
-    dist_ = ops.pair_cosine_dist(x, inv, torch.from_numpy(pi.astype(np.int32)).to(dev), torch.from_numpy(pj.astype(np.int32)).to(dev))
-    return spearman_rho(torch.from_numpy(dt).to(dev), dist_)
+    dist_ = ops.pair_cosine_dist(x, inv, upload(pi, dev, np.int32), upload(pj, dev, np.int32))
+    return spearman_rho(upload(dt, dev), dist_)
 
 
 # ------------------------------------------------------------------------------------------------ the callback

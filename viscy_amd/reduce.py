@@ -16,7 +16,8 @@ folded into W, so one projection kernel serves both ``normalize_features`` setti
 
 Inputs are numpy arrays or torch tensors; a tensor already on the device is used in place.  A mapping with ``"features"`` and any of
 ``"id"``, ``"fov_name"``, ``"t"``, ``"track_id"`` stands in for the reference's xarray ``Dataset``.  There is no CPU path for the data
-passes: without a HIP device ``fit`` / ``transform`` / ``compute_pca`` raise ``RuntimeError``.
+passes: without a HIP device ``fit`` / ``transform`` / ``compute_pca`` raise ``RuntimeError``.  The checks, the device rule and the
+uploads are ``evalkit``'s; ``project`` and ``served`` are what ``linear_classifier`` shares with the estimators here.
 
 Deliberate differences from sklearn:
 
@@ -39,8 +40,9 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
+from .evalkit import as_matrix, column, device_of, padded_to_two_rows, to_device, upload
 
-__all__ = ["compute_pca", "StandardScaler", "PCA", "pca_from_moments", "scale_from_moments", "PcaFit"]
+__all__ = ["compute_pca", "StandardScaler", "PCA", "pca_from_moments", "scale_from_moments", "PcaFit", "project", "served"]
 
 MAX_FEATURES = L.PCA_MAX_D  # largest d the PCA and logistic-regression kernels serve
 META_COLUMNS = ("id", "fov_name", "t", "track_id")  # the reference's pca_dict order
@@ -140,50 +142,18 @@ def pca_from_moments(n: int, mean64, m2_64, gram64, n_components=None, normalize
                   n_components_=int(k), noise_variance_=noise)
 
 
-# ------------------------------------------------------------------------------------------------ input plumbing
-def _rows(X, name: str = "X"):
-    """a 2-D numpy array or tensor with at least two rows of finite values (checked where it lives)"""
-    if torch.is_tensor(X):
-        X = X.detach()
-        if X.dim() != 2:
-            raise ValueError(f"{name} must be a (rows, d) matrix, got {tuple(X.shape)}")
-        finite = bool(torch.isfinite(X).all())
-    else:
-        X = np.asarray(X)
-        if X.ndim != 2:
-            raise ValueError(f"{name} must be a (rows, d) matrix, got {X.shape}")
-        finite = bool(np.isfinite(X).all())
-    if X.shape[0] < 2:
-        raise ValueError(f"{name} needs at least two rows (got {X.shape[0]})")
-    if X.shape[1] < 1:
-        raise ValueError(f"{name} needs at least one feature")
-    if not finite:
-        raise ValueError("Input X contains NaN or infinity.")
-    return X
-
-
-def _served(d: int) -> None:
+# ------------------------------------------------------------------------------------------------ what the estimators share
+def served(d: int) -> None:
+    """``NotImplementedError`` for more features than the PCA and logistic-regression kernels serve"""
     if d > MAX_FEATURES:
         raise NotImplementedError(f"d={d} features: the PCA kernels serve d <= {MAX_FEATURES}")
 
 
-def _device(X) -> torch.device:
-    if torch.is_tensor(X) and X.is_cuda:
-        return X.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("viscy_amd.reduce needs the HIP device (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_device(X, dev: torch.device) -> Tensor:
-    t = X if torch.is_tensor(X) else torch.from_numpy(np.array(X, dtype=np.float32))  # a copy: the caller's array may be read-only
-    return t.to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _project(x: Tensor, mean64: np.ndarray, w32: np.ndarray) -> Tensor:
+def project(x: Tensor, mean64: np.ndarray, w32: np.ndarray) -> Tensor:
+    """``vsx_center_project``: (x - mean64) w32', float32 on x's device"""
     from . import ops
 
-    return ops.center_project(x, torch.from_numpy(np.ascontiguousarray(mean64)).to(x.device), torch.from_numpy(w32).to(x.device))
+    return ops.center_project(x, upload(mean64, x.device), upload(w32, x.device))
 
 
 # ------------------------------------------------------------------------------------------------ estimators
@@ -194,9 +164,9 @@ class StandardScaler:
     def fit(self, X, y=None):
         from . import ops
 
-        X = _rows(X)
-        _served(X.shape[1])
-        x = _to_device(X, _device(X))
+        X = as_matrix(X, min_rows=2, min_cols=1)
+        served(X.shape[1])
+        x = to_device(X, device_of(X, who="reduce"))
         mean, m2 = ops.col_moments(x)
         self.mean_ = mean.cpu().numpy()
         self.var_, self.scale_ = scale_from_moments(x.shape[0], self.mean_, m2.cpu().numpy())
@@ -207,21 +177,16 @@ class StandardScaler:
     def _check(self, X):
         if not hasattr(self, "scale_"):
             raise RuntimeError("this StandardScaler is not fitted yet")
-        if torch.is_tensor(X):
-            X = X.detach()
-        else:
-            X = np.asarray(X)
-        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"X {tuple(X.shape)} must be (rows, {self.n_features_in_})")
-        return X
+        return as_matrix(X, width=self.n_features_in_, finite=False)
+
+    def projection_weights(self) -> np.ndarray:
+        """float32 (d, d): the diagonal ``1 / scale_``, the W of ``vsx_center_project``"""
+        return np.ascontiguousarray(np.diag(1.0 / self.scale_).astype(np.float32))
 
     def transform(self, X) -> np.ndarray:
         X = self._check(X)
-        x = _to_device(X, _device(X))
-        if x.shape[0] < 2:  # the kernels serve n >= 2: a single row rides with a copy of itself
-            return self.transform(torch.cat((x, x)))[:1]
-        w = np.ascontiguousarray(np.diag(1.0 / self.scale_).astype(np.float32))
-        return _project(x, self.mean_, w).cpu().numpy()
+        x, n = padded_to_two_rows(to_device(X, device_of(X, who="reduce")))
+        return project(x, self.mean_, self.projection_weights()).cpu().numpy()[:n]
 
     def fit_transform(self, X, y=None) -> np.ndarray:
         return self.fit(X).transform(X)
@@ -242,10 +207,10 @@ class PCA:
     def _fit(self, X):
         from . import ops
 
-        X = _rows(X)
+        X = as_matrix(X, min_rows=2, min_cols=1)
         _resolve_components(self.n_components, X.shape[0], X.shape[1])
-        _served(X.shape[1])
-        x = _to_device(X, _device(X))
+        served(X.shape[1])
+        x = to_device(X, device_of(X, who="reduce"))
         mean, m2 = ops.col_moments(x)
         gram = ops.gram_centered(x, mean)
         fit = pca_from_moments(x.shape[0], mean.cpu().numpy(), m2.cpu().numpy(), gram.cpu().numpy(), self.n_components,
@@ -267,18 +232,14 @@ class PCA:
         return self
 
     def _transform(self, x: Tensor) -> np.ndarray:
-        return _project(x, self.fit_.data_mean, self.fit_.projection_weights()).cpu().numpy()
+        return project(x, self.fit_.data_mean, self.fit_.projection_weights()).cpu().numpy()
 
     def transform(self, X) -> np.ndarray:
         if not hasattr(self, "fit_"):
             raise RuntimeError("this PCA is not fitted yet")
-        X = X.detach() if torch.is_tensor(X) else np.asarray(X)
-        if X.ndim != 2 or X.shape[1] != self.n_features_in_:
-            raise ValueError(f"X {tuple(X.shape)} must be (rows, {self.n_features_in_})")
-        x = _to_device(X, _device(X))
-        if x.shape[0] < 2:
-            return self._transform(torch.cat((x, x)))[:1]
-        return self._transform(x)
+        X = as_matrix(X, width=self.n_features_in_, finite=False)
+        x, n = padded_to_two_rows(to_device(X, device_of(X, who="reduce")))
+        return self._transform(x)[:n]
 
     def fit_transform(self, X, y=None) -> np.ndarray:
         return self._transform(self._fit(X))
@@ -293,7 +254,7 @@ def compute_pca(embedding_dataset, n_components=None, normalize_features=True):
 
     if isinstance(embedding_dataset, Mapping):
         features = embedding_dataset["features"]
-        pca_dict = {c: _column(embedding_dataset[c]) for c in META_COLUMNS if c in embedding_dataset}
+        pca_dict = {c: column(embedding_dataset[c]) for c in META_COLUMNS if c in embedding_dataset}
     else:
         features, pca_dict = embedding_dataset, {}
     features = getattr(features, "values", features) if not torch.is_tensor(features) else features
@@ -302,8 +263,3 @@ def compute_pca(embedding_dataset, n_components=None, normalize_features=True):
         pca_dict[f"PC{i + 1}"] = pc_features[:, i]
     return pc_features, pd.DataFrame(pca_dict)
 
-
-def _column(v):
-    if torch.is_tensor(v):
-        return v.detach().cpu().numpy()
-    return np.asarray(getattr(v, "values", v))

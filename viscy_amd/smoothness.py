@@ -12,7 +12,8 @@ the host builds the pair lists (vectorised, in the reference's order) and the de
 
 What stays on the host is O(pairs): mean / std / median, the normalisation of the density and scipy's ``find_peaks(height=)`` restated
 in numpy.  The distances come back as float64 arrays because the return type asks for them.  There is no CPU path for the three
-passes: without a HIP device the functions raise ``RuntimeError``.  scipy and sklearn are not imported.
+passes: without a HIP device the functions raise ``RuntimeError``.  scipy and sklearn are not imported.  Input handling is
+``evalkit``'s; the features are not checked for finite values here (``StandardScaler.fit`` does that for the smoothness).
 
 Deliberate differences from the reference:
 
@@ -29,6 +30,8 @@ from collections.abc import Mapping
 
 import numpy as np
 import torch
+
+from .evalkit import as_matrix, column, device_of, to_device, upload
 
 __all__ = ["find_distribution_peak", "compute_embeddings_smoothness", "compute_track_displacement", "adjacent_pairs", "random_pairs",
            "track_pairs", "find_peaks_height", "kde_curve"]
@@ -87,7 +90,7 @@ def _kde_cov(data: np.ndarray) -> float:
 
 def _codes(values) -> tuple[np.ndarray, int]:
     """-> (the rank of every value among the sorted distinct values, how many there are)"""
-    arr = _column(values)
+    arr = column(values)
     if arr.dtype == object:   # names: hashed once and only the distinct ones sorted, as groupby does; 6 x np.unique at 10^6 rows
         import pandas as pd
 
@@ -156,7 +159,7 @@ def track_pairs(fov, track, t):
     tracks in first-appearance order, the rows of a track sorted by t (stably); track k is rows[starts[k] : starts[k] + lengths[k]].
     Its pairs are, for off = 1 .. T - 1 and ascending i, (i, i + off)"""
     key = _track_keys(fov, track)
-    t = _column(t)
+    t = column(t)
     if len(t) != len(key):
         raise ValueError("t must have one entry per row")
     uniq, first, inv = np.unique(key, return_index=True, return_inverse=True)
@@ -180,40 +183,18 @@ def _offset_major(T: int, cache: dict) -> tuple[np.ndarray, np.ndarray]:
 
 
 # ------------------------------------------------------------------------------------------------ input plumbing
-def _column(v) -> np.ndarray:
-    if torch.is_tensor(v):
-        return v.detach().cpu().numpy()
-    return np.asarray(getattr(v, "values", v))
-
-
-def _device(X) -> torch.device:
-    if torch.is_tensor(X) and X.is_cuda:
-        return X.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("viscy_amd.smoothness needs the HIP device (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _features(X) -> torch.Tensor:
-    """float32 (N, d) on the device; a device tensor is used in place"""
-    dev = _device(X)
-    if not torch.is_tensor(X):
-        X = torch.from_numpy(np.array(getattr(X, "values", X), dtype=np.float32))   # a copy: the caller's array may be read-only
-    X = X.detach()
-    if X.dim() != 2:
-        raise ValueError(f"features must be a (rows, d) matrix, got {tuple(X.shape)}")
-    return X.to(device=dev, dtype=torch.float32).contiguous()
+    """float32 (N, d) on the device; a device tensor is used in place.  The device is looked for first; the values are not"""
+    dev = device_of(X, who="smoothness")
+    return to_device(as_matrix(X, "features", finite=False, unwrap=True), dev)
 
 
 def _pair_dist(x: torch.Tensor, pi: np.ndarray, pj: np.ndarray, metric: str, eps: float) -> np.ndarray:
     from . import ops
 
-    dev = x.device
     if len(pi) and not (0 <= min(pi.min(), pj.min()) and max(pi.max(), pj.max()) < min(x.shape[0], 2 ** 31)):
         raise ValueError(f"pair indices must lie in [0, {min(x.shape[0], 2 ** 31)}): the kernel takes them as int32")
-    pi_d = torch.from_numpy(pi.astype(np.int32)).to(dev)
-    pj_d = torch.from_numpy(pj.astype(np.int32)).to(dev)
-    return ops.pair_dist(x, pi_d, pj_d, metric, eps).cpu().numpy()
+    return ops.pair_dist(x, upload(pi, x.device, np.int32), upload(pj, x.device, np.int32), metric, eps).cpu().numpy()
 
 
 def _metric(distance_metric: str) -> str:
@@ -228,16 +209,16 @@ def find_distribution_peak(data, method="kde_robust") -> float:
     bandwidth on ``linspace(min, max, 1000)`` (``vsx_kde_gauss``), peaks at least a tenth of the maximum high, the grid argmax where
     there is none; ``"histogram"``: the same rule on 50 density bins, on the host"""
     if method == "histogram":
-        density, edges = np.histogram(_column(data), bins=HIST_BINS, density=True)
+        density, edges = np.histogram(column(data), bins=HIST_BINS, density=True)
         return _highest_peak(0.5 * (edges[:-1] + edges[1:]), density)
     elif method == "kde_robust":
         from . import ops
 
-        host = np.ascontiguousarray(np.atleast_1d(np.asarray(_column(data), dtype=np.float64)).reshape(-1))
+        host = np.ascontiguousarray(np.atleast_1d(np.asarray(column(data), dtype=np.float64)).reshape(-1))
         cov = _kde_cov(host)
-        dev = _device(data)
+        dev = device_of(data, who="smoothness")
         x_range = np.linspace(np.min(host), np.max(host), GRID_POINTS)
-        sums = ops.kde_gauss(torch.from_numpy(host).to(dev), torch.from_numpy(x_range).to(dev), 1.0 / (2.0 * cov))
+        sums = ops.kde_gauss(upload(host, dev), upload(x_range, dev), 1.0 / (2.0 * cov))
         return _highest_peak(x_range, kde_curve(host, sums.cpu().numpy()))
     else:
         raise ValueError(f"Unknown method: {method}. Use 'histogram' or 'kde_robust'.")
@@ -255,12 +236,11 @@ def compute_embeddings_smoothness(features_ad, distance_metric="cosine", time_of
     say = print if verbose else (lambda *a: None)
     x = _features(features_ad.X)
     obs = features_ad.obs
-    n_rows = len(_column(obs["fov_name"]))
+    n_rows = len(column(obs["fov_name"]))
     if n_rows != x.shape[0]:
         raise ValueError(f"obs has {n_rows} rows, X {x.shape[0]}")
     scaler = StandardScaler().fit(x)
-    moments = [torch.from_numpy(np.ascontiguousarray(v)).to(x.device) for v in (scaler.mean_, scaler.scale_)]
-    z = ops.standardize(x, *moments)
+    z = ops.standardize(x, upload(scaler.mean_, x.device), upload(scaler.scale_, x.device))
 
     pi, pj, piecewise, splits = adjacent_pairs(obs["fov_name"], obs["track_id"], time_offsets)
     say(f"{len(pi)} pairs of temporal neighbours at offsets {list(time_offsets)}")
@@ -292,7 +272,7 @@ def compute_track_displacement(embedding_dataset, distance_metric="cosine") -> d
     if not isinstance(embedding_dataset, Mapping):
         raise TypeError("embedding_dataset must be a mapping with 'features', 'fov_name', 'track_id' and 't'")
     x = _features(embedding_dataset["features"])
-    t = _column(embedding_dataset["t"])
+    t = column(embedding_dataset["t"])
     rows, starts, lengths = track_pairs(embedding_dataset["fov_name"], embedding_dataset["track_id"], t)
     if len(rows) != x.shape[0]:
         raise ValueError(f"the metadata have {len(rows)} rows, the features {x.shape[0]}")

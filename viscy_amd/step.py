@@ -89,18 +89,18 @@ class TrainStep:
 
     # ---- direct driver
     def _loss_and_grad(self, pred):
-        from .losses import MixedLoss, _MixedLossFn
+        from .losses import MixedLoss, MixedLossFn
 
         if isinstance(self.crit, MixedLoss):  # the criterion's kernels, without an autograd graph around them
             class _Ctx:
                 pass
 
             ctx = _Ctx()
-            loss = _MixedLossFn.forward(ctx, pred, self.t, float(self.crit.l1_alpha), float(self.crit.l2_alpha),
+            loss = MixedLossFn.forward(ctx, pred, self.t, float(self.crit.l1_alpha), float(self.crit.l2_alpha),
                                         float(self.crit.ms_dssim_alpha))
             if getattr(self, "_one", None) is None or self._one.device != pred.device:
                 self._one = torch.ones((), dtype=torch.float32, device=pred.device)  # created once, outside any capture
-            return loss, _MixedLossFn.backward(ctx, self._one)[0]
+            return loss, MixedLossFn.backward(ctx, self._one)[0]
         p = pred.detach().requires_grad_(True)
         with torch.enable_grad():
             loss = self.crit(p, self.t)

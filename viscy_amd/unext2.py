@@ -44,95 +44,95 @@ CONVNEXTV2_CFGS = {  # timm convnextv2_* (depths, dims, conv_mlp)
 # ------------------------------------------------------------------------------------------------
 # parameter holders (names / shapes = reference; forward is never called)
 # ------------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
+class Holder(nn.Module):
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("viscy_amd parameter holder: run the model through UNeXt2.forward (HIP kernels)")
 
 
-class _LN(_Holder):
+class LN(Holder):
     def __init__(self, c: int):
         super().__init__()
         self.weight = nn.Parameter(torch.ones(c))
         self.bias = nn.Parameter(torch.zeros(c))
 
 
-class _Conv(_Holder):
+class Conv(Holder):
     def __init__(self, shape: tuple[int, ...]):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(shape))
         self.bias = nn.Parameter(torch.zeros(shape[0]))
 
 
-class _GRN(_Holder):
+class _GRN(Holder):
     def __init__(self, c: int):
         super().__init__()
         self.weight = nn.Parameter(torch.zeros(c))
         self.bias = nn.Parameter(torch.zeros(c))
 
 
-class _Mlp(_Holder):
+class _Mlp(Holder):
     def __init__(self, c: int, conv_mlp: bool):
         super().__init__()
-        self.fc1 = _Conv((4 * c, c, 1, 1) if conv_mlp else (4 * c, c))
+        self.fc1 = Conv((4 * c, c, 1, 1) if conv_mlp else (4 * c, c))
         self.grn = _GRN(4 * c)
-        self.fc2 = _Conv((c, 4 * c, 1, 1) if conv_mlp else (c, 4 * c))
+        self.fc2 = Conv((c, 4 * c, 1, 1) if conv_mlp else (c, 4 * c))
 
 
-class _Block(_Holder):
+class _Block(Holder):
     def __init__(self, c: int, conv_mlp: bool):
         super().__init__()
-        self.conv_dw = _Conv((c, 1, 7, 7))
-        self.norm = _LN(c)
+        self.conv_dw = Conv((c, 1, 7, 7))
+        self.norm = LN(c)
         self.mlp = _Mlp(c, conv_mlp)
 
 
-class _MlpV1(_Holder):
+class _MlpV1(Holder):
     def __init__(self, c: int):
         super().__init__()
-        self.fc1 = _Conv((4 * c, c))
-        self.fc2 = _Conv((c, 4 * c))
+        self.fc1 = Conv((4 * c, c))
+        self.fc2 = Conv((c, 4 * c))
 
 
-class _BlockV1(_Holder):
+class _BlockV1(Holder):
     """timm ConvNeXtBlock of the V1 family: layer scale ``gamma`` (ls_init_value 1e-6), plain MLP, no GRN"""
 
     def __init__(self, c: int):
         super().__init__()
         self.gamma = nn.Parameter(1e-6 * torch.ones(c))
-        self.conv_dw = _Conv((c, 1, 7, 7))
-        self.norm = _LN(c)
+        self.conv_dw = Conv((c, 1, 7, 7))
+        self.norm = LN(c)
         self.mlp = _MlpV1(c)
 
 
-class _Stage(_Holder):
+class _Stage(Holder):
     def __init__(self, cin: int, cout: int, stride: int, depth: int, conv_mlp: bool, v1: bool = False):
         super().__init__()
         if cin != cout or stride > 1:
             ks = 2 if stride > 1 else 1
-            self.downsample = nn.Sequential(_LN(cin), _Conv((cout, cin, ks, ks)))
+            self.downsample = nn.Sequential(LN(cin), Conv((cout, cin, ks, ks)))
         else:
             self.downsample = nn.Identity()
         self.blocks = nn.Sequential(*[(_BlockV1(cout) if v1 else _Block(cout, conv_mlp)) for _ in range(depth)])
 
 
-class _Encoder(_Holder):
+class Encoder(Holder):
     def __init__(self, depths, dims, conv_mlp, v1: bool = False):
         super().__init__()
         self.stem_0 = nn.Identity()
-        self.stem_1 = _LN(dims[0])
+        self.stem_1 = LN(dims[0])
         prev = dims[0]
         for i, (d, c) in enumerate(zip(depths, dims)):
             setattr(self, f"stages_{i}", _Stage(prev, c, 2 if i > 0 else 1, d, conv_mlp, v1))
             prev = c
 
 
-class _Stem(_Holder):
+class Stem(Holder):
     def __init__(self, cin, cout3d, kernel):
         super().__init__()
-        self.conv = _Conv((cout3d, cin, *kernel))
+        self.conv = Conv((cout3d, cin, *kernel))
 
 
-class _UpStage(_Holder):
+class _UpStage(Holder):
     """``pre_conv``: MONAI SubpixelUpsample's Conv2d(cin, cin, 3, padding 1) in front of the pixel shuffle
     (``decoder_upsample_pre_conv=True``, blocks.py:138-146); MONAI's ``UpSample`` registers the shuffle block as
     ``pixelshuffle``, hence the key ``upsample.pixelshuffle.conv_block.{weight,bias}``."""
@@ -140,9 +140,9 @@ class _UpStage(_Holder):
     def __init__(self, cin, cskip, cout, depth, pre_conv=False):
         super().__init__()
         if pre_conv:
-            self.upsample = _Holder()
-            self.upsample.pixelshuffle = _Holder()
-            self.upsample.pixelshuffle.conv_block = _Conv((cin, cin, 3, 3))
+            self.upsample = Holder()
+            self.upsample.pixelshuffle = Holder()
+            self.upsample.pixelshuffle.conv_block = Conv((cin, cin, 3, 3))
         else:
             self.upsample = nn.Identity()
         self.conv = _Stage(cin // 4 + cskip, cout, 1, depth, conv_mlp=True)
@@ -152,7 +152,7 @@ class _UpStage(_Holder):
         return None if isinstance(self.upsample, nn.Identity) else self.upsample.pixelshuffle.conv_block
 
 
-class _Decoder(_Holder):
+class _Decoder(Holder):
     def __init__(self, chans, depth, pre_conv=False):
         super().__init__()
         self.decoder_stages = nn.ModuleList(
@@ -160,20 +160,20 @@ class _Decoder(_Holder):
         )
 
 
-class _ADN(_Holder):
+class _ADN(Holder):
     def __init__(self):
         super().__init__()
         self.A = nn.PReLU(num_parameters=1, init=0.25)
 
 
-class _HeadConv0(_Holder):
+class _HeadConv0(Holder):
     def __init__(self, cin, cout):
         super().__init__()
-        self.conv = _Conv((cout, cin, 3, 3, 3))
+        self.conv = Conv((cout, cin, 3, 3, 3))
         self.adn = _ADN()
 
 
-class _ShuffleHead(_Holder):
+class _ShuffleHead(Holder):
     """PixelToVoxelShuffleHead: parameter free (pixel shuffle + pad-pool + reshape)."""
 
     def __init__(self):
@@ -181,11 +181,11 @@ class _ShuffleHead(_Holder):
         self.upsample = nn.Identity()
 
 
-class _Head(_Holder):
+class _Head(Holder):
     def __init__(self, c3, cmid, co4):
         super().__init__()
         self.upsample = nn.Identity()
-        self.conv = nn.Sequential(_HeadConv0(c3, cmid), _Conv((co4, cmid, 1, 1, 1)))
+        self.conv = nn.Sequential(_HeadConv0(c3, cmid), Conv((co4, cmid, 1, 1, 1)))
         self.out = nn.Identity()
 
 
@@ -203,7 +203,7 @@ def _icnr_(weight: Tensor, scale: int) -> None:
 
 
 # ------------------------------------------------------------------------------------------------
-class _Core(NativeModule, nn.Module):
+class Core(NativeModule, nn.Module):
     """Shared machinery of the ConvNeXt-V2 U-Net family on this path (UNeXt2, the dense FCMAE U-Net): parameter tree in the
     engine's naming, flat-buffer engine, HIP-only forward."""
 
@@ -237,8 +237,8 @@ class _Core(NativeModule, nn.Module):
             stem_kernel=stem_kernel_size, ratio=ratio, decoder_conv_blocks=decoder_conv_blocks,
             head_pool=bool(head_pool), head_expansion_ratio=head_expansion_ratio, head=head,
         )
-        self.encoder_stages = _Encoder(depths, dims, conv_mlp)
-        self.stem = _Stem(in_channels, dims[0] // ratio, stem_kernel_size)
+        self.encoder_stages = Encoder(depths, dims, conv_mlp)
+        self.stem = Stem(in_channels, dims[0] // ratio, stem_kernel_size)
         dec = list(reversed(dims))
         if head == "conv":  # PixelToVoxelHead: (D + 2) * C * 2^2 * expansion channels feed the 3-D convolution
             dec[-1] = (out_stack_depth + 2) * head_channels_from * 4 * head_expansion_ratio
@@ -262,7 +262,7 @@ class _Core(NativeModule, nn.Module):
             nn.init.trunc_normal_(w, std=0.02)
 
         for name, mod in self.named_modules():
-            if isinstance(mod, _Conv) and (name.startswith("encoder_stages") or name.startswith("decoder")):
+            if isinstance(mod, Conv) and (name.startswith("encoder_stages") or name.startswith("decoder")):
                 tn(mod.weight)
                 nn.init.zeros_(mod.bias)
         w = self.stem.conv.weight  # torch Conv3d default: kaiming_uniform(a=sqrt(5))
@@ -310,7 +310,7 @@ class _Core(NativeModule, nn.Module):
         return unext2_apply(self, x, masks, bn_groups)
 
 
-class UNeXt2(_Core):
+class UNeXt2(Core):
     """MI355X-native UNeXt2 (see module docstring).  ``compute_dtype``: None → bf16 under
     ``torch.autocast(bfloat16)``, fp32 otherwise; or force ``torch.bfloat16`` / ``torch.float32``."""
 
