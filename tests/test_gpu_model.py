@@ -203,7 +203,9 @@ def test_mixed_loss_one_pass_forward_odd_sizes(shape, a2):
     """the training forward is one pass per scale (SSIM sums + gradient field + the next scale's pooling, data range and the
     L1 / L2 sums: vsx_ssim_scale_fwd_fused); the forward without gradient still pools in a pass of its own.  Both against the
     oracle on odd plane sizes (a leftover row / column at every scale, tiles whose last column owns up to 42 pixels), a
-    depth the kernel has no compile-time instance for, and a target that is an unaligned view."""
+    depth the kernel has no compile-time instance for, and a target that is an unaligned view.  Run with loss_fused = 1 and 0."""
+    from tests.ref_exact_gemm import Flags
+    from viscy_amd import _lib
     from viscy_amd.losses import MixedLoss
 
     gen = torch.Generator().manual_seed(11)
@@ -213,22 +215,29 @@ def test_mixed_loss_one_pass_forward_odd_sizes(shape, a2):
     flat[1:] = target.flatten().cuda()
     tdev = flat[1:].view(shape)  # 4-byte aligned only
     fn = MixedLoss(0.5, a2, 0.5)
-    p = pred.cuda().requires_grad_(True)
-    loss = fn(p, tdev)
-    with torch.no_grad():
-        loss_ng = fn(pred.cuda(), tdev)
     pr = pred.clone().requires_grad_(True)
     lr = loss_ref.mixed_loss(pr, target, 0.5, a2, 0.5)
-    assert abs(loss.item() - lr.item()) <= 1e-3 * abs(lr.item()), (loss.item(), lr.item())
-    assert abs(loss.item() - loss_ng.item()) <= 2e-6 * abs(lr.item()), (loss.item(), loss_ng.item())  # same math, other sum order
-    loss.backward()
     lr.backward()
-    g = p.grad.cpu()
-    d = (g - pr.grad).abs() / pr.grad.abs().max()
-    assert d.max().item() <= 1e-2, d.max().item()
-    assert (d > 5e-3).float().mean().item() <= 1e-3
-    cos = torch.nn.functional.cosine_similarity(g.flatten().double(), pr.grad.flatten().double(), dim=0).item()
-    assert cos > 0.99999, cos
+    flags = Flags(_lib.lib())
+    # loss_fused = 0: the two-pass training forward (vsx_loss_pool + vsx_ssim_scale_fwd_dmu); loss / loss_ng then compare two
+    # runs of the two-pass path
+    for fused in (1, 0):
+        with flags.scoped({"loss_fused": fused}):
+            assert flags.get("loss_fused") == fused
+            p = pred.cuda().requires_grad_(True)
+            loss = fn(p, tdev)
+            with torch.no_grad():
+                loss_ng = fn(pred.cuda(), tdev)
+            assert abs(loss.item() - lr.item()) <= 1e-3 * abs(lr.item()), (loss.item(), lr.item())
+            assert abs(loss.item() - loss_ng.item()) <= 2e-6 * abs(lr.item()), (loss.item(), loss_ng.item())  # same math, other sum order
+            loss.backward()
+        g = p.grad.cpu()
+        d = (g - pr.grad).abs() / pr.grad.abs().max()
+        assert d.max().item() <= 1e-2, d.max().item()
+        assert (d > 5e-3).float().mean().item() <= 1e-3
+        cos = torch.nn.functional.cosine_similarity(g.flatten().double(), pr.grad.flatten().double(), dim=0).item()
+        assert cos > 0.99999, cos
+    assert flags.get("loss_fused") == 1
 
 
 def test_mixed_loss_branches_and_errors():
