@@ -46,7 +46,8 @@ def cdiv(a: int, b: int) -> int:
 
 # ------------------------------------------------------------------------------------------------ dispatch arithmetic
 def conv_plan(B: int, H2: int, W2: int) -> dict:
-    """vsx_head_conv_fwd / vsx_head_conv_wgrad: tiles of 8 x 16 pixels, x fastest, then y, then the sample.  The persistent forward
+    """vsx_head_conv_fwd / vsx_head_conv_wgrad: tiles of 8 x 16 pixels (HF_TY x HF_TX, counted per sample by hc_tiles() of
+    csrc/headconv.hip), x fastest, then y, then the sample.  The persistent forward
     gives workgroup g the tiles [g tiles_per_wg, (g + 1) tiles_per_wg); the weight gradient's workgroup g takes g, g + grid, .."""
     tiles_x, tiles_y = W2 // 16, H2 // 8
     per, ntiles = tiles_x * tiles_y, B * tiles_x * tiles_y
@@ -59,7 +60,8 @@ def conv_plan(B: int, H2: int, W2: int) -> dict:
 
 def shuffle_plan(B: int, h: int, w: int, c3: int, D: int, dt, pool: bool, head_rows: int = 63, bwd: bool = False) -> dict:
     """vsx_head_shuffle_fwd / _bwd: column strips (bf16, pooled, C3 D = 56, 64 | w, bit 3 / 4 of head_rows), else LDS tiles
-    (C3 D <= 64), else one thread per 16-byte vector"""
+    (C3 D <= 64), else one thread per 16-byte vector (head_shuffle_launch of csrc/spatial.hip; rows_per_wg is its
+    hs_rows_per_wg)"""
     bit = ROWS_STRIP_BWD if bwd else ROWS_STRIP_FWD
     if dt == BF16 and pool and (head_rows & bit) and c3 * D == 56 and w % 64 == 0:
         strips = B * (w // 64)

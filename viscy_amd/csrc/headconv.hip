@@ -31,70 +31,86 @@ constexpr int HF_PS = HC_D7 * HC_C3 * 2;  // 112 B per halo pixel: 16 consecutiv
 // workgroups per CU by registers).
 constexpr int HF_TY = 8;                           // pixel rows per workgroup
 constexpr int HF_SR = HC_ZO * HC_CMID * 2 + 16;    // staging bytes per pixel (+16: the 16 lanes of a store group hit 16 bank pairs)
-__global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __restrict__ hin, const bf16_t* __restrict__ Wc,
-                                                            const float* __restrict__ bias, bf16_t* __restrict__ U,
-                                                            float* __restrict__ ssum, float* __restrict__ ssq, int H2, int W2,
-                                                            float* __restrict__ det_ws) {
-  __shared__ __attribute__((aligned(16))) char tile[(HF_TY + 2) * 18 * HF_PS];
-  __shared__ __attribute__((aligned(16))) char stage[4 * 16 * HF_SR];
-  __shared__ float red[4][64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p16 = lane & 15, kq = lane >> 4;
-  const int b = blockIdx.z, ty0 = blockIdx.y * HF_TY, tx0 = blockIdx.x * 16;
-  const size_t img = (size_t)b * H2 * W2;
-  {
-    // staging: every thread's loads first, then its LDS stores.  Written as `load; store` in one strided loop the compiler
-    // kept a real loop with `s_waitcnt vmcnt(0)` in front of each store — one memory round trip per iteration, 9–15 per tile
-    // (rocprofv3: the data-gradient kernel ran at 1.6 TB/s with its MFMAs idle 3/4 of the time)
-    constexpr int NPIX = (HF_TY + 2) * 18;
-    constexpr int NST = (NPIX * HC_D7 + 255) / 256;
-    uint4 sv[NST];
+constexpr int HF_TX = 16;                          // pixel columns per workgroup (one pixel fragment)
+
+// The (HF_TY + 2) x (HF_TX + 2) pixel halo tile of a channels-last tensor with NCH 16-byte chunks per pixel (hin: 7, dU: 20),
+// zero outside the image, to an LDS tile of PS bytes per pixel.  Every thread's loads first, then its LDS stores: written as
+// `load; store` in one strided loop the compiler kept a real loop with `s_waitcnt vmcnt(0)` in front of each store — one memory
+// round trip per iteration, 9–15 per tile (rocprofv3: the data-gradient kernel ran at 1.6 TB/s with its MFMAs idle 3/4 of the
+// time).  The two halves are separate calls so that the persistent forward can compute between them.
+constexpr int HC_HALO_PIX = (HF_TY + 2) * (HF_TX + 2);
+template <int NCH>
+struct HcHalo {
+  static constexpr int N = HC_HALO_PIX * NCH;  // chunks of a tile
+  static constexpr int NST = (N + 255) / 256;  // chunks per thread
+  uint4 sv[NST];
+};
+template <int NCH>
+__device__ __forceinline__ void hc_halo_issue(HcHalo<NCH>& hl, const bf16_t* __restrict__ src, size_t img, int ty0, int tx0, int H2,
+                                              int W2, int tid) {
 #pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int c = tid + it * 256;
-      const int pix = c / HC_D7, zc = c - pix * HC_D7;
-      const int py = pix / 18, px = pix - py * 18;
-      const int y = ty0 + py - 1, x = tx0 + px - 1;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (c < NPIX * HC_D7 && y >= 0 && y < H2 && x >= 0 && x < W2)
-        v = *reinterpret_cast<const uint4*>(hin + (img + (size_t)y * W2 + x) * (HC_D7 * HC_C3) + zc * HC_C3);
-      sv[it] = v;
-    }
+  for (int it = 0; it < HcHalo<NCH>::NST; ++it) {
+    const int c = tid + it * 256;
+    const int pix = c / NCH, ch = c - pix * NCH;
+    const int py = pix / (HF_TX + 2), px = pix - py * (HF_TX + 2);
+    const int y = ty0 + py - 1, x = tx0 + px - 1;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (c < HcHalo<NCH>::N && y >= 0 && y < H2 && x >= 0 && x < W2)
+      v = *reinterpret_cast<const uint4*>(src + (img + (size_t)y * W2 + x) * (NCH * 8) + ch * 8);
+    hl.sv[it] = v;
+  }
+}
+template <int NCH, int PS>
+__device__ __forceinline__ void hc_halo_store(const HcHalo<NCH>& hl, char* tile, int tid) {
 #pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int c = tid + it * 256;
-      if (c < NPIX * HC_D7) {
-        const int pix = c / HC_D7, zc = c - pix * HC_D7;
-        const uint4 v = sv[it];
-        *reinterpret_cast<uint4*>(tile + pix * HF_PS + zc * 16) = v;
-      }
+  for (int it = 0; it < HcHalo<NCH>::NST; ++it) {
+    const int c = tid + it * 256;
+    if (c < HcHalo<NCH>::N) {
+      const int pix = c / NCH, ch = c - pix * NCH;
+      const uint4 v = hl.sv[it];
+      *reinterpret_cast<uint4*>(tile + pix * PS + ch * 16) = v;
     }
   }
-  // weights: 2 channel fragments x 7 K-steps (4 taps each; tap 27 does not exist -> zero), resident in registers
+}
+
+// what a lane keeps for the whole launch: 2 channel fragments x 7 K-steps of weights (4 taps each; tap 27 does not exist ->
+// zero) with the halo-tile offsets of its taps, and the bias of its 2 x 4 channels
+struct HfWeights {
   mf_bf16x8 wf[2][7];
   int toff[7];
+  float bs[2][4];
+};
+__device__ __forceinline__ void hf_weights(HfWeights& w, const bf16_t* __restrict__ Wc, const float* __restrict__ bias, int p16, int kq) {
 #pragma unroll
   for (int kk = 0; kk < 7; ++kk) {
     const int t = kk * 4 + kq;
     const int tt = t < 27 ? t : 26;
     const int dyx = tt / 3, dz = tt - dyx * 3;
     const int dy = dyx / 3, dx = dyx - dy * 3;
-    toff[kk] = (dy * 18 + dx) * HF_PS + dz * 16;
+    w.toff[kk] = (dy * 18 + dx) * HF_PS + dz * 16;
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf)
-      wf[nf][kk] = t < 27 ? *reinterpret_cast<const mf_bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : mf_zero8();
+      w.wf[nf][kk] = t < 27 ? *reinterpret_cast<const mf_bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : mf_zero8();
   }
-  float bs[2][4], s1[2][4], s2[2][4];
+#pragma unroll
+  for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w.bs[nf][r] = bias ? bias[nf * 16 + kq * 4 + r] : 0.f;
+}
+
+// the two pixel rows of a wave out of the staged halo tile: MFMAs, bias, rounding, the wave-private staging row `st` and its
+// copy-out to U (tile origin (ty0, tx0) of image `img`); s1 / s2 = this lane's sums of the stored values and of their squares.
+// (The output row address is formed from U per row: handed in as a tile pointer, the one-tile kernel spilled 8 registers.)
+__device__ __forceinline__ void hf_wave_rows(const HfWeights& w, const char* tile, char* st, bf16_t* __restrict__ U, size_t img,
+                                             int ty0, int tx0, int W2, int wave, int lane, float (&s1)[2][4], float (&s2)[2][4]) {
+  const int p16 = lane & 15, kq = lane >> 4;
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      bs[nf][r] = bias ? bias[nf * 16 + kq * 4 + r] : 0.f;
       s1[nf][r] = 0.f;
       s2[nf][r] = 0.f;
     }
-  __syncthreads();
-  char* st = stage + wave * (16 * HF_SR);
 #pragma unroll 1
   for (int mf = 0; mf < 2; ++mf) {
     const int pbase = ((wave * 2 + mf) * 18 + p16) * HF_PS;
@@ -103,15 +119,15 @@ __global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __r
       mf_f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
       for (int kk = 0; kk < 7; ++kk) {
-        const mf_bf16x8 pf = *reinterpret_cast<const mf_bf16x8*>(tile + pbase + toff[kk] + z * 16);
+        const mf_bf16x8 pf = *reinterpret_cast<const mf_bf16x8*>(tile + pbase + w.toff[kk] + z * 16);
 #pragma unroll
-        for (int nf = 0; nf < 2; ++nf) acc[nf] = mfma16(wf[nf][kk], pf, acc[nf]);
+        for (int nf = 0; nf < 2; ++nf) acc[nf] = mfma16(w.wf[nf][kk], pf, acc[nf]);
       }
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf) {
         float c[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) c[r] = acc[nf][r] + bs[nf][r];
+        for (int r = 0; r < 4; ++r) c[r] = acc[nf][r] + w.bs[nf][r];
         uint2 o;
         o.x = f32x2_to_bf16x2_bits(c[0], c[1]);
         o.y = f32x2_to_bf16x2_bits(c[2], c[3]);
@@ -137,7 +153,16 @@ __global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __r
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
-  // lanes of one kq group (16 pixels) -> one partial per channel; waves -> LDS; one atomic per (sample, channel) per workgroup
+}
+
+// statistics exit of a tile: lanes of one kq group (16 pixels) -> one partial per channel; waves -> LDS; then either row `tile_id`
+// (= (b * tiles_img + ty * tiles_x + tx)) of the det_reduce workspace, added up in tile order by vsx_det_group_sum, or one atomic per
+// (sample, channel).  Its barrier also means: every wave is done reading the halo tile.
+__device__ __forceinline__ void hf_stats_exit(float (&red)[4][64], const float (&s1)[2][4], const float (&s2)[2][4], int tid, int b,
+                                              size_t tile_id, float* __restrict__ det_ws, float* __restrict__ ssum,
+                                              float* __restrict__ ssq) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int p16 = lane & 15, kq = lane >> 4;
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
@@ -151,12 +176,35 @@ __global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __r
   __syncthreads();
   if (tid < 64) {
     const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    if (det_ws) {  // det_reduce: one row of 64 partials per workgroup, added up in tile order by vsx_det_group_sum
-      det_ws[((size_t)b * gridDim.y * gridDim.x + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 64 + tid] = v;
+    if (det_ws) {
+      det_ws[tile_id * 64 + tid] = v;
     } else {
       atomicAdd((tid < 32 ? ssum : ssq) + (size_t)b * HC_CMID + (tid & 31), v);
     }
   }
+}
+
+__global__ __launch_bounds__(256, 3) void head_conv_fwd_kernel(const bf16_t* __restrict__ hin, const bf16_t* __restrict__ Wc,
+                                                            const float* __restrict__ bias, bf16_t* __restrict__ U,
+                                                            float* __restrict__ ssum, float* __restrict__ ssq, int H2, int W2,
+                                                            float* __restrict__ det_ws) {
+  __shared__ __attribute__((aligned(16))) char tile[HC_HALO_PIX * HF_PS];
+  __shared__ __attribute__((aligned(16))) char stage[4 * 16 * HF_SR];
+  __shared__ float red[4][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.z, ty0 = blockIdx.y * HF_TY, tx0 = blockIdx.x * HF_TX;
+  const size_t img = (size_t)b * H2 * W2;
+  {
+    HcHalo<HC_D7> hl;
+    hc_halo_issue(hl, hin, img, ty0, tx0, H2, W2, tid);
+    hc_halo_store<HC_D7, HF_PS>(hl, tile, tid);
+  }
+  HfWeights wt;
+  hf_weights(wt, Wc, bias, lane & 15, lane >> 4);
+  __syncthreads();
+  float s1[2][4], s2[2][4];
+  hf_wave_rows(wt, tile, stage + wave * (16 * HF_SR), U, img, ty0, tx0, W2, wave, lane, s1, s2);
+  hf_stats_exit(red, s1, s2, tid, b, (size_t)b * gridDim.y * gridDim.x + (size_t)blockIdx.y * gridDim.x + blockIdx.x, det_ws, ssum, ssq);
 }
 
 // Round 6: the same pass as a persistent kernel.  One tile per workgroup put the tile's phases in a row — 5 halo loads per thread,
@@ -174,141 +222,32 @@ __global__ __launch_bounds__(256, HCF_WPE) void head_conv_fwd_persist_kernel(con
                                                                     float* __restrict__ ssum, float* __restrict__ ssq, int H2,
                                                                     int W2, float* __restrict__ det_ws, int ntiles,
                                                                     int tiles_per_wg) {
-  __shared__ __attribute__((aligned(16))) char tile[(HF_TY + 2) * 18 * HF_PS];
+  __shared__ __attribute__((aligned(16))) char tile[HC_HALO_PIX * HF_PS];
   __shared__ __attribute__((aligned(16))) char stage[4 * 16 * HF_SR];
   __shared__ float red[4][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p16 = lane & 15, kq = lane >> 4;
-  const int tiles_x = W2 / 16, tiles_y = H2 / HF_TY, tiles_img = tiles_x * tiles_y;
-  constexpr int NPIX = (HF_TY + 2) * 18;
-  constexpr int NST = (NPIX * HC_D7 + 255) / 256;
-  // this thread's chunks of a halo tile never change: (pixel, plane) slots and their LDS addresses
-  int slot[NST];  // py | px << 8 | (plane + 1) << 16 (0: no chunk)
-#pragma unroll
-  for (int it = 0; it < NST; ++it) {
-    const int c = tid + it * 256;
-    const int pix = c / HC_D7;
-    const int py = pix / 18;
-    slot[it] = c < NPIX * HC_D7 ? (py | (pix - py * 18) << 8 | (c - pix * HC_D7 + 1) << 16) : 0;
-  }
-  auto issue = [&](int t, uint4 (&sv)[NST]) {
+  const int tiles_x = W2 / HF_TX, tiles_y = H2 / HF_TY, tiles_img = tiles_x * tiles_y;
+  HcHalo<HC_D7> hl;
+  auto issue = [&](int t) {
     const int b = t / tiles_img, r = t - b * tiles_img;
-    const int ty0 = (r / tiles_x) * HF_TY, tx0 = (r % tiles_x) * 16;
-    const size_t img = (size_t)b * H2 * W2;
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int y = ty0 + (slot[it] & 0xff) - 1, x = tx0 + ((slot[it] >> 8) & 0xff) - 1, zc = (slot[it] >> 16) - 1;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (zc >= 0 && y >= 0 && y < H2 && x >= 0 && x < W2)
-        v = *reinterpret_cast<const uint4*>(hin + (img + (size_t)y * W2 + x) * (HC_D7 * HC_C3) + zc * HC_C3);
-      sv[it] = v;
-    }
+    hc_halo_issue(hl, hin, (size_t)b * H2 * W2, (r / tiles_x) * HF_TY, (r % tiles_x) * HF_TX, H2, W2, tid);
   };
-  // weights: 2 channel fragments x 7 K-steps (4 taps each; tap 27 does not exist -> zero), resident in registers
-  mf_bf16x8 wf[2][7];
-  int toff[7];
-#pragma unroll
-  for (int kk = 0; kk < 7; ++kk) {
-    const int t = kk * 4 + kq;
-    const int tt = t < 27 ? t : 26;
-    const int dyx = tt / 3, dz = tt - dyx * 3;
-    const int dy = dyx / 3, dx = dyx - dy * 3;
-    toff[kk] = (dy * 18 + dx) * HF_PS + dz * 16;
-#pragma unroll
-    for (int nf = 0; nf < 2; ++nf)
-      wf[nf][kk] = t < 27 ? *reinterpret_cast<const mf_bf16x8*>(Wc + (size_t)(nf * 16 + p16) * HC_K + t * 8) : mf_zero8();
-  }
-  float bs[2][4];
-#pragma unroll
-  for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bs[nf][r] = bias ? bias[nf * 16 + kq * 4 + r] : 0.f;
+  HfWeights wt;
+  hf_weights(wt, Wc, bias, lane & 15, lane >> 4);
   const int t_begin = blockIdx.x * tiles_per_wg, t_end = min(ntiles, t_begin + tiles_per_wg);
   if (t_begin >= t_end) return;
-  uint4 sv[NST];
-  issue(t_begin, sv);
-  char* st = stage + wave * (16 * HF_SR);
+  issue(t_begin);
   for (int t = t_begin; t < t_end; ++t) {
     const int b = t / tiles_img, rr = t - b * tiles_img;
     const int tyi = rr / tiles_x, txi = rr - tyi * tiles_x;
-    const int ty0 = tyi * HF_TY, tx0 = txi * 16;
     const size_t img = (size_t)b * H2 * W2;
     // (every wave is done with the previous tile: it passed the statistics barrier at the end of the last step)
-#pragma unroll
-    for (int it = 0; it < NST; ++it)
-      if (slot[it]) *reinterpret_cast<uint4*>(tile + ((slot[it] & 0xff) * 18 + ((slot[it] >> 8) & 0xff)) * HF_PS + ((slot[it] >> 16) - 1) * 16) = sv[it];
+    hc_halo_store<HC_D7, HF_PS>(hl, tile, tid);
     __syncthreads();
-    if (t + 1 < t_end) issue(t + 1, sv);
+    if (t + 1 < t_end) issue(t + 1);
     float s1[2][4], s2[2][4];
-#pragma unroll
-    for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s1[nf][r] = 0.f;
-        s2[nf][r] = 0.f;
-      }
-#pragma unroll 1
-    for (int mf = 0; mf < 2; ++mf) {
-      const int pbase = ((wave * 2 + mf) * 18 + p16) * HF_PS;
-#pragma unroll
-      for (int z = 0; z < HC_ZO; ++z) {
-        mf_f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int kk = 0; kk < 7; ++kk) {
-          const mf_bf16x8 pf = *reinterpret_cast<const mf_bf16x8*>(tile + pbase + toff[kk] + z * 16);
-#pragma unroll
-          for (int nf = 0; nf < 2; ++nf) acc[nf] = mfma16(wf[nf][kk], pf, acc[nf]);
-        }
-#pragma unroll
-        for (int nf = 0; nf < 2; ++nf) {
-          float c[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) c[r] = acc[nf][r] + bs[nf][r];
-          uint2 o;
-          o.x = f32x2_to_bf16x2_bits(c[0], c[1]);
-          o.y = f32x2_to_bf16x2_bits(c[2], c[3]);
-          *reinterpret_cast<uint2*>(st + p16 * HF_SR + (z * HC_CMID + nf * 16 + kq * 4) * 2) = o;
-          // InstanceNorm statistics of the STORED (rounded) value, like VSX_EPI_BIAS_STATS
-          const float q0 = __uint_as_float(o.x << 16), q1 = __uint_as_float(o.x & 0xffff0000u);
-          const float q2 = __uint_as_float(o.y << 16), q3 = __uint_as_float(o.y & 0xffff0000u);
-          s1[nf][0] += q0; s1[nf][1] += q1; s1[nf][2] += q2; s1[nf][3] += q3;
-          s2[nf][0] += q0 * q0; s2[nf][1] += q1 * q1; s2[nf][2] += q2 * q2; s2[nf][3] += q3 * q3;
-        }
-      }
-      // the row of 16 pixels x 320 bytes is contiguous in U: 320 16-byte chunks, 64 per store instruction
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      char* dst = reinterpret_cast<char*>(U + (img + (size_t)(ty0 + wave * 2 + mf) * W2 + tx0) * (HC_ZO * HC_CMID));
-#pragma unroll
-      for (int it = 0; it < 5; ++it) {
-        const int c = lane + it * 64;
-        const int px = c / 20, ch = c - px * 20;
-        const uint4 v = *reinterpret_cast<const uint4*>(st + px * HF_SR + ch * 16);
-        *reinterpret_cast<uint4*>(dst + c * 16) = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-    // lanes of one kq group (16 pixels) -> one partial per channel; waves -> LDS; one atomic per (sample, channel) per tile
-#pragma unroll
-    for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float a = group_sum<16>(s1[nf][r]), q = group_sum<16>(s2[nf][r]);
-        if (p16 == 0) {
-          red[wave][nf * 16 + kq * 4 + r] = a;
-          red[wave][32 + nf * 16 + kq * 4 + r] = q;
-        }
-      }
-    __syncthreads();  // (also: every wave is done reading the halo tile)
-    if (tid < 64) {
-      const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-      if (det_ws) {  // det_reduce: one row of 64 partials per tile, added up in tile order by vsx_det_group_sum
-        det_ws[((size_t)b * tiles_img + (size_t)tyi * tiles_x + txi) * 64 + tid] = v;
-      } else {
-        atomicAdd((tid < 32 ? ssum : ssq) + (size_t)b * HC_CMID + (tid & 31), v);
-      }
-    }
+    hf_wave_rows(wt, tile, stage + wave * (16 * HF_SR), U, img, tyi * HF_TY, txi * HF_TX, W2, wave, lane, s1, s2);
+    hf_stats_exit(red, s1, s2, tid, b, (size_t)b * tiles_img + (size_t)tyi * tiles_x + txi, det_ws, ssum, ssq);
   }
 }
 
@@ -321,12 +260,12 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const bf16_t* __re
                                                               float* __restrict__ dW, float* __restrict__ db, int B, int H2,
                                                               int W2) {
   __shared__ __attribute__((aligned(16))) char du_t[128 * HW_DS];      // 40 KB
-  __shared__ __attribute__((aligned(16))) char hin_t[10 * 18 * HF_PS]; // 20 KB
+  __shared__ __attribute__((aligned(16))) char hin_t[HC_HALO_PIX * HF_PS];  // 20 KB
   __shared__ __attribute__((aligned(16))) unsigned short consts[8];    // [1, 0, 0, 0 | 0, 0, 0, 0] (bf16)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = lane & 15, kq = lane >> 4;
   if (tid < 8) consts[tid] = tid == 0 ? 0x3f80 : 0;
-  const int tiles_x = W2 / 16, tiles_y = H2 / 8;
+  const int tiles_x = W2 / HF_TX, tiles_y = H2 / HF_TY;
   const int ntiles = B * tiles_y * tiles_x;
   // this wave's column fragments jf = wave, wave + 4, wave + 8, wave + 12 (< 14)
   mf_f32x4 acc[2][4];
@@ -353,12 +292,13 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const bf16_t* __re
 #pragma unroll 1
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int b = t / (tiles_y * tiles_x), rem = t - b * tiles_y * tiles_x;
-    const int ty0 = (rem / tiles_x) * 8, tx0 = (rem % tiles_x) * 16;
+    const int ty0 = (rem / tiles_x) * HF_TY, tx0 = (rem % tiles_x) * HF_TX;
     const size_t img = (size_t)b * H2 * W2;
     __syncthreads();  // previous tile fully consumed
-    {  // all loads of the tile in flight together, then the LDS stores (see head_conv_fwd_kernel)
-      constexpr int NDU = 128 * 20 / 256, NHI = (180 * HC_D7 + 255) / 256;
-      uint4 dv[NDU], hv[NHI];
+    {  // all loads of the tile in flight together, then the LDS stores (see hc_halo_issue)
+      constexpr int NDU = 128 * 20 / 256;
+      uint4 dv[NDU];
+      HcHalo<HC_D7> hv;
 #pragma unroll
       for (int it = 0; it < NDU; ++it) {  // dU tile: 128 pixels x 20 chunks
         const int c = tid + it * 256;
@@ -366,17 +306,7 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const bf16_t* __re
         const int y = ty0 + (pix >> 4), x = tx0 + (pix & 15);
         dv[it] = *reinterpret_cast<const uint4*>(dU + (img + (size_t)y * W2 + x) * (HC_ZO * HC_CMID) + ch * 8);
       }
-#pragma unroll
-      for (int it = 0; it < NHI; ++it) {
-        const int c = tid + it * 256;
-        const int pix = c / HC_D7, zc = c - pix * HC_D7;
-        const int py = pix / 18, px = pix - py * 18;
-        const int y = ty0 + py - 1, x = tx0 + px - 1;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (c < 180 * HC_D7 && y >= 0 && y < H2 && x >= 0 && x < W2)
-          v = *reinterpret_cast<const uint4*>(hin + (img + (size_t)y * W2 + x) * (HC_D7 * HC_C3) + zc * HC_C3);
-        hv[it] = v;
-      }
+      hc_halo_issue(hv, hin, img, ty0, tx0, H2, W2, tid);
 #pragma unroll
       for (int it = 0; it < NDU; ++it) {
         const int c = tid + it * 256;
@@ -384,15 +314,7 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const bf16_t* __re
         const uint4 v = dv[it];
         *reinterpret_cast<uint4*>(du_t + pix * HW_DS + ch * 16) = v;
       }
-#pragma unroll
-      for (int it = 0; it < NHI; ++it) {
-        const int c = tid + it * 256;
-        if (c < 180 * HC_D7) {
-          const int pix = c / HC_D7, zc = c - pix * HC_D7;
-          const uint4 v = hv[it];
-          *reinterpret_cast<uint4*>(hin_t + pix * HF_PS + zc * 16) = v;
-        }
-      }
+      hc_halo_store<HC_D7, HF_PS>(hv, hin_t, tid);
     }
     __syncthreads();
 #pragma unroll 1
@@ -485,13 +407,13 @@ __global__ __launch_bounds__(256) void head_conv_dgrad_kernel(const bf16_t* __re
                                                               bf16_t* __restrict__ dhin, int H2, int W2) {
   // separate LDS objects: the compiler's alias scopes then let the halo / fragment reads proceed while the DMA into the OTHER
   // weight buffer is in flight (csrc/mlp.hip)
-  __shared__ __attribute__((aligned(16))) char halo[10 * 18 * HD_PS];  // 60 KB
+  __shared__ __attribute__((aligned(16))) char halo[HC_HALO_PIX * HD_PS];  // 60 KB
   __shared__ __attribute__((aligned(1024))) char wb0[10 * 1024];
   __shared__ __attribute__((aligned(1024))) char wb1[10 * 1024];
   const int tid = threadIdx.x;
   const MfLane ln = mf_lane(tid);  // the operand and C / D maps of lane (p16, kq): mfma16.h
   const int lane = ln.lane, wave = ln.wave, p16 = ln.p16, kq = ln.kq;
-  const int b = blockIdx.z, ty0 = blockIdx.y * 8, tx0 = blockIdx.x * 16;
+  const int b = blockIdx.z, ty0 = blockIdx.y * HF_TY, tx0 = blockIdx.x * HF_TX;
   const size_t img = (size_t)b * H2 * W2;
   // the 10 KiB of tap `tap` -> buffer: pieces wave, wave + 4, wave + 8 (1 KiB = one wave instruction)
   const char* wsrc = reinterpret_cast<const char*>(Wp) + lane * 16;
@@ -504,29 +426,10 @@ __global__ __launch_bounds__(256) void head_conv_dgrad_kernel(const bf16_t* __re
     }
   };
   wdma(0, wb0);
-  {  // all loads of the halo tile in flight together, then the LDS stores (see head_conv_fwd_kernel)
-    constexpr int NST = (180 * 20 + 255) / 256;
-    uint4 sv[NST];
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int c = tid + it * 256;
-      const int pix = c / 20, ch = c - pix * 20;
-      const int py = pix / 18, px = pix - py * 18;
-      const int y = ty0 + py - 1, x = tx0 + px - 1;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (c < 180 * 20 && y >= 0 && y < H2 && x >= 0 && x < W2)
-        v = *reinterpret_cast<const uint4*>(dU + (img + (size_t)y * W2 + x) * (HC_ZO * HC_CMID) + ch * 8);
-      sv[it] = v;
-    }
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-      const int c = tid + it * 256;
-      if (c < 180 * 20) {
-        const int pix = c / 20, ch = c - pix * 20;
-        const uint4 v = sv[it];
-        *reinterpret_cast<uint4*>(halo + pix * HD_PS + ch * 16) = v;
-      }
-    }
+  {  // the dU halo tile
+    HcHalo<HC_ZO * HC_CMID / 8> hl;
+    hc_halo_issue(hl, dU, img, ty0, tx0, H2, W2, tid);
+    hc_halo_store<HC_ZO * HC_CMID / 8, HD_PS>(hl, halo, tid);
   }
   mf_f32x4 acc[2][4];
   mfma_zero(acc);
@@ -565,20 +468,22 @@ __global__ __launch_bounds__(256) void head_conv_dgrad_kernel(const bf16_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
+// the shapes all three passes take (vsx.h): H2 and W2 in whole 16s, so every HF_TY x HF_TX tile is whole
+static bool hc_shape_ok(int B, int H2, int W2) { return B > 0 && H2 > 0 && W2 > 0 && H2 % 16 == 0 && W2 % 16 == 0; }
 static int hc_check(const char* who, int B, int H2, int W2, int c3, int cmid, int zo, int dtype) {
   VSX_CHECK(dtype == VSX_BF16, "%s: the direct head convolution is built for bf16 only (use vsx_gemm_nt / VSX_A_CONV3 for fp32)", who);
   VSX_CHECK(c3 == HC_C3 && cmid == HC_CMID && zo == HC_ZO, "%s: built for %d -> %d channels, %d output planes (got %d -> %d, %d)", who,
             HC_C3, HC_CMID, HC_ZO, c3, cmid, zo);
-  VSX_CHECK(B > 0 && H2 > 0 && W2 > 0 && H2 % 16 == 0 && W2 % 16 == 0, "%s: H2=%d, W2=%d must be positive multiples of 16", who, H2, W2);
+  VSX_CHECK(hc_shape_ok(B, H2, W2), "%s: H2=%d, W2=%d must be positive multiples of 16", who, H2, W2);
   return 0;
 }
 extern "C" int32_t vsx_head_conv_supported(int32_t H2, int32_t W2, int32_t c3, int32_t cmid, int32_t zo, int32_t dtype) {
-  return dtype == VSX_BF16 && c3 == HC_C3 && cmid == HC_CMID && zo == HC_ZO && H2 > 0 && W2 > 0 && H2 % 16 == 0 && W2 % 16 == 0;
+  return dtype == VSX_BF16 && c3 == HC_C3 && cmid == HC_CMID && zo == HC_ZO && hc_shape_ok(1, H2, W2);
 }
-static int hc_tiles(int H2, int W2) { return (W2 / 16) * (H2 / HF_TY); }  // workgroups (or tiles of the persistent kernel) per sample
+static int hc_tiles(int H2, int W2) { return (W2 / HF_TX) * (H2 / HF_TY); }  // workgroups (or tiles of the persistent kernel) per sample
 static long hc_det_need(int B, int H2, int W2) { return (long)B * hc_tiles(H2, W2) * 64; }
 extern "C" int64_t vsx_head_conv_det_floats(int32_t B, int32_t H2, int32_t W2) {
-  return B > 0 && H2 > 0 && W2 > 0 && H2 % 16 == 0 && W2 % 16 == 0 ? hc_det_need(B, H2, W2) : 0;
+  return hc_shape_ok(B, H2, W2) ? hc_det_need(B, H2, W2) : 0;
 }
 extern "C" int32_t vsx_head_conv_fwd(const void* hin, const void* Wc, const float* bias, void* U, float* ssum, float* ssq,
                                      int32_t B, int32_t H2, int32_t W2, int32_t c3, int32_t cmid, int32_t zo, int32_t dtype,
@@ -594,7 +499,7 @@ extern "C" int32_t vsx_head_conv_fwd(const void* hin, const void* Wc, const floa
     hipLaunchKernelGGL(head_conv_fwd_persist_kernel, dim3(vsx_cdiv(ntiles, (long)tpw)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)hin, (const bf16_t*)Wc, bias, (bf16_t*)U, ssum, ssq, H2, W2, det_ws, (int)ntiles, tpw);
   } else
-  hipLaunchKernelGGL(head_conv_fwd_kernel, dim3(W2 / 16, H2 / HF_TY, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)hin,
+  hipLaunchKernelGGL(head_conv_fwd_kernel, dim3(W2 / HF_TX, H2 / HF_TY, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)hin,
                      (const bf16_t*)Wc, bias, (bf16_t*)U, ssum, ssq, H2, W2, det_ws);
   VSX_LAUNCH_CHECK();
   if (det_ws) {
@@ -607,7 +512,7 @@ extern "C" int32_t vsx_head_conv_wgrad(const void* hin, const void* dU, float* d
                                        int32_t c3, int32_t cmid, int32_t zo, int32_t dtype, vsx_stream_t stream) {
   if (int e = hc_check("vsx_head_conv_wgrad", B, H2, W2, c3, cmid, zo, dtype)) return e;
   VSX_CHECK(hin && dU && dW, "vsx_head_conv_wgrad: null pointer");
-  int tiles = B * (H2 / 8) * (W2 / 16);
+  int tiles = B * hc_tiles(H2, W2);
   int grid = tiles < 512 ? tiles : 512;  // 2 workgroups per CU (60 KB LDS each); every workgroup ends with 32 x 217 atomics
   hipLaunchKernelGGL(head_conv_wgrad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)hin, (const bf16_t*)dU,
                      dW, db, B, H2, W2);
@@ -625,7 +530,7 @@ extern "C" int32_t vsx_head_conv_dgrad(const void* dU, const void* Wp, void* dhi
                                        int32_t cmid, int32_t zo, int32_t dtype, vsx_stream_t stream) {
   if (int e = hc_check("vsx_head_conv_dgrad", B, H2, W2, c3, cmid, zo, dtype)) return e;
   VSX_CHECK(dU && Wp && dhin, "vsx_head_conv_dgrad: null pointer");
-  hipLaunchKernelGGL(head_conv_dgrad_kernel, dim3(W2 / 16, H2 / 8, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dU,
+  hipLaunchKernelGGL(head_conv_dgrad_kernel, dim3(W2 / HF_TX, H2 / HF_TY, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dU,
                      (const bf16_t*)Wp, (bf16_t*)dhin, H2, W2);
   VSX_LAUNCH_CHECK();
   return 0;

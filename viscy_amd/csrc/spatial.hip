@@ -217,9 +217,11 @@ extern "C" int32_t vsx_col2im3x3(const void* dcol, void* dx, int32_t B, int32_t 
 
 // ------------------------------------------------------------------ pixel shuffle x2 + concat (K10)
 // out[b, Y, X, j] = j < c ? low[b, Y/2, X/2, 4j + 2(Y&1) + (X&1)] : skip[b, Y, X, j - c]
-template <typename T>
-__global__ __launch_bounds__(256) void ps_cat_fwd_kernel(const T* __restrict__ low, const T* __restrict__ skip,
-                                                         T* __restrict__ out, int B, int h, int w, int c, int cs) {
+// Element-wise form, one thread per vector of the concatenated tensor; the arguments are those of ps_cat_vec_kernel below.
+// Backward: low-part channels scatter to dlow (each element written once), skip-part channels go to dskip.
+template <typename T, bool BWD>
+__global__ __launch_bounds__(256) void ps_cat_elem_kernel(const T* __restrict__ a0, const T* __restrict__ a1, T* __restrict__ o0,
+                                                          T* __restrict__ o1, int B, int h, int w, int c, int cs) {
   constexpr int VN = VT<T>::N;
   const int ct = c + cs;
   const int nch = ct / VN;
@@ -234,61 +236,28 @@ __global__ __launch_bounds__(256) void ps_cat_fwd_kernel(const T* __restrict__ l
   const int Y = (int)(r % H2);
   const int b = (int)(r / H2);
   const int j0 = ch * VN;
-  T* dst = out + (size_t)pix * ct + j0;
-  if (j0 >= c && ((j0 - c) % VN == 0) && (cs % VN == 0)) {
-    stvec<T>(dst, ldvec<T>(skip + (size_t)pix * cs + (j0 - c)));
-    return;
-  }
-  const T* lp = low + (((size_t)b * h + (Y >> 1)) * w + (X >> 1)) * (4 * c) + 2 * (Y & 1) + (X & 1);
+  // (no whole-vector copy for skip channels: a vector that lies in the skip part aligned on both sides means c % VN == 0 and
+  // cs % VN == 0, and then the entry points launch ps_cat_vec_kernel)
+  const size_t lp = (((size_t)b * h + (Y >> 1)) * w + (X >> 1)) * (4 * c) + 2 * (Y & 1) + (X & 1);
   typename VT<T>::vec tv;
   T* tmp = reinterpret_cast<T*>(&tv);
+  if (BWD) tv = ldvec<T>(a0 + (size_t)pix * ct + j0);
 #pragma unroll
   for (int j = 0; j < VN; ++j) {
-    int jj = j0 + j;
-    tmp[j] = jj < c ? lp[4 * jj] : skip[(size_t)pix * cs + (jj - c)];
-  }
-  stvec<T>(dst, tv);
-}
-
-// backward: one thread per dcat vector; low-part channels scatter to dlow (each element written once),
-// skip-part channels go to dskip.
-template <typename T>
-__global__ __launch_bounds__(256) void ps_cat_bwd_kernel(const T* __restrict__ dcat, T* __restrict__ dlow,
-                                                         T* __restrict__ dskip, int B, int h, int w, int c, int cs) {
-  constexpr int VN = VT<T>::N;
-  const int ct = c + cs;
-  const int nch = ct / VN;
-  const int H2 = 2 * h, W2 = 2 * w;
-  const long total = (long)B * H2 * W2 * nch;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= total) return;
-  const int ch = (int)(gid % nch);
-  const long pix = gid / nch;
-  const int X = (int)(pix % W2);
-  const long r = pix / W2;
-  const int Y = (int)(r % H2);
-  const int b = (int)(r / H2);
-  const int j0 = ch * VN;
-  typename VT<T>::vec v = ldvec<T>(dcat + (size_t)pix * ct + j0);
-  if (j0 >= c && ((j0 - c) % VN == 0) && (cs % VN == 0)) {
-    stvec<T>(dskip + (size_t)pix * cs + (j0 - c), v);
-    return;
-  }
-  const T* tv = reinterpret_cast<const T*>(&v);
-  T* lp = dlow + (((size_t)b * h + (Y >> 1)) * w + (X >> 1)) * (4 * c) + 2 * (Y & 1) + (X & 1);
-#pragma unroll
-  for (int j = 0; j < VN; ++j) {
-    int jj = j0 + j;
-    if (jj < c)
-      lp[4 * jj] = tv[j];
+    const int jj = j0 + j;
+    if (!BWD)
+      tmp[j] = jj < c ? a0[lp + 4 * jj] : a1[(size_t)pix * cs + (jj - c)];
+    else if (jj < c)
+      o0[lp + 4 * jj] = tmp[j];
     else
-      dskip[(size_t)pix * cs + (jj - c)] = tv[j];
+      o1[(size_t)pix * cs + (jj - c)] = tmp[j];
   }
+  if (!BWD) stvec<T>(o0 + (size_t)pix * ct + j0, tv);
 }
 
-// Vector form of the two kernels above for c % VN == 0 and cs % VN == 0 (every configuration of the path): the 4 sub-pixels of a
+// Vector form of the kernel above for c % VN == 0 and cs % VN == 0 (every configuration of the path): the 4 sub-pixels of a
 // low-resolution pixel take their VN channels j0 .. j0 + VN - 1 from the 4 * VN CONTIGUOUS low channels 4 j0 .. 4 j0 + 4 VN - 1, so
-// one thread moves four whole vectors in and four out and (de)interleaves them in registers — the element-wise kernels issue
+// one thread moves four whole vectors in and four out and (de)interleaves them in registers — the element-wise kernel issues
 // VN two-byte accesses per vector (1.3 ms per step at 3.2 – 4.9 TB/s of 16-byte traffic's worth).
 // items: [0, na) = (low pixel, channel group) of the shuffled part, [na, na + nb) = (output pixel, vector) of the skip part
 template <typename T, bool BWD>
@@ -343,56 +312,30 @@ __global__ __launch_bounds__(256) void ps_cat_vec_kernel(const T* __restrict__ a
 
 /* K10: MONAI UpSample(mode="pixelshuffle", pre_conv=None) + torch.cat([up, skip], 1)
  * (viscy_models/components/blocks.py:138-146,170-171).  skip may be NULL (cs = 0). */
-extern "C" int32_t vsx_pixel_shuffle_cat_fwd(const void* low, const void* skip, void* out, int32_t B, int32_t h,
-                                             int32_t w, int32_t c, int32_t cs, int32_t dtype, vsx_stream_t stream) {
-  int vn = vsx_vec_elems(dtype);
-  VSX_CHECK(low && out && B > 0 && h > 0 && w > 0 && c > 0 && cs >= 0, "vsx_pixel_shuffle_cat_fwd: bad arguments");
-  VSX_CHECK((cs == 0) == (skip == nullptr), "vsx_pixel_shuffle_cat_fwd: skip pointer / cs mismatch");
-  VSX_CHECK((c + cs) % vn == 0, "vsx_pixel_shuffle_cat_fwd: c+cs=%d must be a multiple of %d", c + cs, vn);
-  hipStream_t s = (hipStream_t)stream;
-  if (c % vn == 0 && cs % vn == 0) {  // whole vectors on both sides: the register-(de)interleaving form
-    const long items = (long)B * h * w * (c / vn) + (long)B * 4 * h * w * (cs / vn);
-    vsx_by_dtype(dtype, [&](auto tag) {
-      using T = typename decltype(tag)::type;
-      hipLaunchKernelGGL((ps_cat_vec_kernel<T, false>), dim3(vsx_cdiv(items, 256)), dim3(256), 0, s, (const T*)low, (const T*)skip,
-                         (T*)out, (T*)nullptr, B, h, w, c, cs);
-    });
-    VSX_LAUNCH_CHECK();
-    return 0;
-  }
-  const long total = (long)B * 4 * h * w * ((c + cs) / vn);
+template <bool BWD>
+static int ps_cat_launch(const char* who, const void* a0, const void* a1, void* o0, void* o1, int32_t B, int32_t h, int32_t w, int32_t c,
+                         int32_t cs, int32_t dtype, vsx_stream_t stream) {
+  const int vn = vsx_vec_elems(dtype);
+  VSX_CHECK(a0 && o0 && B > 0 && h > 0 && w > 0 && c > 0 && cs >= 0, "%s: bad arguments", who);
+  VSX_CHECK((cs == 0) == ((BWD ? (const void*)o1 : a1) == nullptr), "%s: %s pointer / cs mismatch", who, BWD ? "dskip" : "skip");
+  VSX_CHECK((c + cs) % vn == 0, "%s: c+cs=%d must be a multiple of %d", who, c + cs, vn);
+  const bool vec = c % vn == 0 && cs % vn == 0;  // whole vectors on both sides: the register-(de)interleaving form
+  const long items = vec ? (long)B * h * w * (c / vn) + (long)B * 4 * h * w * (cs / vn) : (long)B * 4 * h * w * ((c + cs) / vn);
   vsx_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(ps_cat_fwd_kernel<T>, dim3(vsx_cdiv(total, 256)), dim3(256), 0, s, (const T*)low, (const T*)skip, (T*)out, B, h, w,
-                       c, cs);
+    hipLaunchKernelGGL((vec ? ps_cat_vec_kernel<T, BWD> : ps_cat_elem_kernel<T, BWD>), dim3(vsx_cdiv(items, 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)a0, (const T*)a1, (T*)o0, (T*)o1, B, h, w, c, cs);
   });
   VSX_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int32_t vsx_pixel_shuffle_cat_fwd(const void* low, const void* skip, void* out, int32_t B, int32_t h,
+                                             int32_t w, int32_t c, int32_t cs, int32_t dtype, vsx_stream_t stream) {
+  return ps_cat_launch<false>("vsx_pixel_shuffle_cat_fwd", low, skip, out, nullptr, B, h, w, c, cs, dtype, stream);
+}
 extern "C" int32_t vsx_pixel_shuffle_cat_bwd(const void* dcat, void* dlow, void* dskip, int32_t B, int32_t h, int32_t w,
                                              int32_t c, int32_t cs, int32_t dtype, vsx_stream_t stream) {
-  int vn = vsx_vec_elems(dtype);
-  VSX_CHECK(dcat && dlow && B > 0 && h > 0 && w > 0 && c > 0 && cs >= 0, "vsx_pixel_shuffle_cat_bwd: bad arguments");
-  VSX_CHECK((cs == 0) == (dskip == nullptr), "vsx_pixel_shuffle_cat_bwd: dskip pointer / cs mismatch");
-  VSX_CHECK((c + cs) % vn == 0, "vsx_pixel_shuffle_cat_bwd: c+cs=%d must be a multiple of %d", c + cs, vn);
-  hipStream_t s = (hipStream_t)stream;
-  if (c % vn == 0 && cs % vn == 0) {
-    const long items = (long)B * h * w * (c / vn) + (long)B * 4 * h * w * (cs / vn);
-    vsx_by_dtype(dtype, [&](auto tag) {
-      using T = typename decltype(tag)::type;
-      hipLaunchKernelGGL((ps_cat_vec_kernel<T, true>), dim3(vsx_cdiv(items, 256)), dim3(256), 0, s, (const T*)dcat, (const T*)nullptr,
-                         (T*)dlow, (T*)dskip, B, h, w, c, cs);
-    });
-    VSX_LAUNCH_CHECK();
-    return 0;
-  }
-  const long total = (long)B * 4 * h * w * ((c + cs) / vn);
-  vsx_by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(ps_cat_bwd_kernel<T>, dim3(vsx_cdiv(total, 256)), dim3(256), 0, s, (const T*)dcat, (T*)dlow, (T*)dskip, B, h, w, c, cs);
-  });
-  VSX_LAUNCH_CHECK();
-  return 0;
+  return ps_cat_launch<true>("vsx_pixel_shuffle_cat_bwd", dcat, nullptr, dlow, dskip, B, h, w, c, cs, dtype, stream);
 }
 
 // ------------------------------------------------------------------ head pixel shuffle (+ pad-pool) (K12)
@@ -586,6 +529,21 @@ __global__ __launch_bounds__(256) void head_shuffle_bwd_tiled_kernel(const T* __
 // 896 gathers) and leave as whole 112-byte pixels: two output rows x 128 pixels per walk step, contiguous in HBM.  The next
 // row's chunks are requested a step ahead.
 constexpr int HS_TX = 64;  // decoder columns per strip
+// the K chunks of a strip row that thread tid owns (chunk i = tid + 256 k of 64 pixels x 4 K chunks): decoder column xl, 16-byte
+// chunk q of that pixel = shuffle groups c' = 2q, 2q + 1, and cpo = the byte offsets of the two groups' output channels
+// (z C3 + c3) * 2, packed 16 | 16
+template <int K>
+__device__ __forceinline__ void hs_chunk_map(int tid, int C3, int D, int (&xl)[K], int (&q)[K], uint32_t (&cpo)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = tid + k * 256;
+    xl[k] = i / (4 * K);
+    q[k] = i - xl[k] * (4 * K);
+    const int c0 = 2 * q[k], c1 = c0 + 1;
+    const int o0 = ((c0 % D) * C3 + c0 / D) * 2, o1 = ((c1 % D) * C3 + c1 / D) * 2;
+    cpo[k] = (uint32_t)o0 | ((uint32_t)o1 << 16);
+  }
+}
 template <int K>           // chunks per thread and row = Cm / 8 (64 pixels x Cm / 2 chunks over 256 threads)
 __global__ __launch_bounds__(256) void head_shuffle_fwd_strip_kernel(const bf16_t* __restrict__ dec, bf16_t* __restrict__ hin, int h,
                                                                     int w, int C3, int D, int rows_per_wg) {
@@ -599,16 +557,8 @@ __global__ __launch_bounds__(256) void head_shuffle_fwd_strip_kernel(const bf16_
   const int b = blockIdx.z, x0 = blockIdx.x * HS_TX;
   const int y0 = blockIdx.y * rows_per_wg, y1 = min(h, y0 + rows_per_wg);
   int xl[K], q[K];
-  uint32_t cpo[K];  // byte offsets of the two groups' output channels (z C3 + c3) * 2, packed 16 | 16
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int i = tid + k * 256;
-    xl[k] = i / NQ;
-    q[k] = i - xl[k] * NQ;
-    const int c0 = 2 * q[k], c1 = c0 + 1;
-    const int o0 = ((c0 % D) * C3 + c0 / D) * 2, o1 = ((c1 % D) * C3 + c1 / D) * 2;
-    cpo[k] = (uint32_t)o0 | ((uint32_t)o1 << 16);
-  }
+  uint32_t cpo[K];
+  hs_chunk_map<K>(tid, C3, D, xl, q, cpo);
   const bool halo_thread = tid < NQ;  // also fetches chunk tid of column x0 - 1
   const size_t img = (size_t)b * h * w;
   auto request = [&](int y, vsx_u32x4 (&cur)[K], vsx_u32x4& hl) {
@@ -689,7 +639,6 @@ __global__ __launch_bounds__(256) void head_shuffle_fwd_strip_kernel(const bf16_
 template <int K>
 __global__ __launch_bounds__(256) void head_shuffle_bwd_strip_kernel(const bf16_t* __restrict__ dhin, bf16_t* __restrict__ ddec, int h,
                                                                     int w, int C3, int D, int rows_per_wg) {
-  constexpr int NQ = 4 * K;
   constexpr int Cm = 8 * K, C4 = 32 * K;
   constexpr int OB = Cm * 2;                      // bytes per output-resolution pixel
   constexpr int NPX = 2 * HS_TX + 1;              // staged pixels per output row (last = halo column 2 x0 + 128)
@@ -700,17 +649,9 @@ __global__ __launch_bounds__(256) void head_shuffle_bwd_strip_kernel(const bf16_
   const int b = blockIdx.z, x0 = blockIdx.x * HS_TX;
   const int y0 = blockIdx.y * rows_per_wg, y1 = min(h, y0 + rows_per_wg);
   const int H2 = 2 * h, W2 = 2 * w;
-  int xl[K];
+  int xl[K], q[K];  // (q: not used by this direction)
   uint32_t cpo[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int i = tid + k * 256;
-    xl[k] = i / NQ;
-    const int qq = i - xl[k] * NQ;
-    const int c0 = 2 * qq, c1 = c0 + 1;
-    const int o0 = ((c0 % D) * C3 + c0 / D) * 2, o1 = ((c1 % D) * C3 + c1 / D) * 2;
-    cpo[k] = (uint32_t)o0 | ((uint32_t)o1 << 16);
-  }
+  hs_chunk_map<K>(tid, C3, D, xl, q, cpo);
   constexpr int REM = CPR - KR * 256;             // leftover chunks of a row (threads tid < REM)
   constexpr int HC = OB / 16;                     // chunks of the halo pixel (threads tid < HC)
   // registers of one staged row pair: [row][KR + 1 (remainder) + 1 (halo)]
@@ -777,77 +718,54 @@ __global__ __launch_bounds__(256) void head_shuffle_bwd_strip_kernel(const bf16_
   }
 }
 
+// rows of the decoder map per workgroup of the strip kernels: two workgroups per CU in one round when the batch allows it
+static int hs_rows_per_wg(int B, int h, int w) {
+  const long strips = (long)B * (w / HS_TX);
+  const long rpw = (long)h * strips / 512;
+  return (int)(rpw < 8 ? 8 : (rpw > h ? h : rpw));
+}
 /* K12: PixelToVoxelHead.upsample + reshape (viscy_models/components/heads.py:607-615,632-637).
  * dec: [B, h, w, 4*C3*D] → hin: [B, 2h, 2w, D*C3] with the depth axis outermost inside a pixel
- * (channel = z*C3 + c3), so the 3x3x3 head convolution reads contiguous channel slices per z. */
-extern "C" int32_t vsx_head_shuffle_fwd(const void* dec, void* hin, int32_t B, int32_t h, int32_t w, int32_t C3,
-                                        int32_t D, int32_t pool, int32_t dtype, vsx_stream_t stream) {
-  int vn = vsx_vec_elems(dtype);
-  VSX_CHECK(dec && hin && B > 0 && h > 0 && w > 0 && C3 > 0 && D > 0, "vsx_head_shuffle_fwd: bad arguments");
-  VSX_CHECK((C3 * D) % vn == 0, "vsx_head_shuffle_fwd: C3*D=%d must be a multiple of %d", C3 * D, vn);
-  long total = (long)B * 4 * h * w * (C3 * D / vn);
-  dim3 grid(vsx_cdiv(total, 256));
+ * (channel = z*C3 + c3), so the 3x3x3 head convolution reads contiguous channel slices per z.
+ * Both directions (src -> dst = dec -> hin or dhin -> ddec); `strip_bit` = the direction's bit of head_rows. */
+template <bool BWD>
+static int head_shuffle_launch(const char* who, int strip_bit, const void* src, void* dst, int32_t B, int32_t h, int32_t w, int32_t C3,
+                               int32_t D, int32_t pool, int32_t dtype, vsx_stream_t stream) {
+  const int vn = vsx_vec_elems(dtype);
+  const int Cw = (BWD ? 4 : 1) * C3 * D;  // channels per pixel of the written tensor
+  VSX_CHECK(src && dst && B > 0 && h > 0 && w > 0 && C3 > 0 && D > 0, "%s: bad arguments", who);
+  VSX_CHECK(Cw % vn == 0, "%s: %s=%d must be a multiple of %d", who, BWD ? "4*C3*D" : "C3*D", Cw, vn);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSX_BF16 && pool && (g_vsx_head_rows & 8) && C3 * D == 56 && w % HS_TX == 0 && B <= 65535) {
-    // column strips (round 6); rows per workgroup: two workgroups per CU in one round when the batch allows it
-    const long strips = (long)B * (w / HS_TX);
-    long rpw = (long)h * strips / 512;
-    rpw = rpw < 8 ? 8 : (rpw > h ? h : rpw);
-    hipLaunchKernelGGL((head_shuffle_fwd_strip_kernel<7>), dim3(w / HS_TX, vsx_cdiv(h, rpw), B), dim3(256), 0, s,
-                       (const bf16_t*)dec, (bf16_t*)hin, h, w, C3, D, (int)rpw);
-    VSX_LAUNCH_CHECK();
-    return 0;
-  }
-  if (C3 * D <= 64 && B <= 65535) {  // LDS-tiled permutation
+  if (dtype == VSX_BF16 && pool && (g_vsx_head_rows & strip_bit) && C3 * D == 56 && w % HS_TX == 0 && B <= 65535) {
+    // column strips (round 6)
+    const int rpw = hs_rows_per_wg(B, h, w);
+    hipLaunchKernelGGL(BWD ? head_shuffle_bwd_strip_kernel<7> : head_shuffle_fwd_strip_kernel<7>, dim3(w / HS_TX, vsx_cdiv(h, rpw), B),
+                       dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)dst, h, w, C3, D, rpw);
+  } else if (C3 * D <= 64 && B <= 65535) {  // LDS-tiled permutation
     vsx_by_dtype(dtype, [&](auto tag) {
       using T = typename decltype(tag)::type;
       constexpr int TS = sizeof(T) == 2 ? 8 : 4;  // tile edge in decoder pixels
-      hipLaunchKernelGGL((head_shuffle_fwd_tiled_kernel<T, TS>), dim3(vsx_cdiv(w, TS), vsx_cdiv(h, TS), B), dim3(256), 0, s,
-                         (const T*)dec, (T*)hin, h, w, C3, D, pool);
+      hipLaunchKernelGGL((BWD ? head_shuffle_bwd_tiled_kernel<T, TS> : head_shuffle_fwd_tiled_kernel<T, TS>),
+                         dim3(vsx_cdiv(w, TS), vsx_cdiv(h, TS), B), dim3(256), 0, s, (const T*)src, (T*)dst, h, w, C3, D, pool);
     });
-    VSX_LAUNCH_CHECK();
-    return 0;
+  } else {  // one thread per vector of the written tensor
+    const long total = (long)B * (BWD ? 1 : 4) * h * w * (Cw / vn);
+    vsx_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(BWD ? head_shuffle_bwd_kernel<T> : head_shuffle_fwd_kernel<T>, dim3(vsx_cdiv(total, 256)), dim3(256), 0, s,
+                         (const T*)src, (T*)dst, B, h, w, C3, D, pool);
+    });
   }
-  vsx_by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(head_shuffle_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dec, (T*)hin, B, h, w, C3, D, pool);
-  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int32_t vsx_head_shuffle_fwd(const void* dec, void* hin, int32_t B, int32_t h, int32_t w, int32_t C3,
+                                        int32_t D, int32_t pool, int32_t dtype, vsx_stream_t stream) {
+  return head_shuffle_launch<false>("vsx_head_shuffle_fwd", 8, dec, hin, B, h, w, C3, D, pool, dtype, stream);
+}
 extern "C" int32_t vsx_head_shuffle_bwd(const void* dhin, void* ddec, int32_t B, int32_t h, int32_t w, int32_t C3,
                                         int32_t D, int32_t pool, int32_t dtype, vsx_stream_t stream) {
-  int vn = vsx_vec_elems(dtype);
-  VSX_CHECK(dhin && ddec && B > 0 && h > 0 && w > 0 && C3 > 0 && D > 0, "vsx_head_shuffle_bwd: bad arguments");
-  VSX_CHECK((4 * C3 * D) % vn == 0, "vsx_head_shuffle_bwd: 4*C3*D must be a multiple of %d", vn);
-  long total = (long)B * h * w * (4 * C3 * D / vn);
-  dim3 grid(vsx_cdiv(total, 256));
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSX_BF16 && pool && (g_vsx_head_rows & 16) && C3 * D == 56 && w % HS_TX == 0 && B <= 65535) {
-    const long strips = (long)B * (w / HS_TX);
-    long rpw = (long)h * strips / 512;
-    rpw = rpw < 8 ? 8 : (rpw > h ? h : rpw);
-    hipLaunchKernelGGL((head_shuffle_bwd_strip_kernel<7>), dim3(w / HS_TX, vsx_cdiv(h, rpw), B), dim3(256), 0, s,
-                       (const bf16_t*)dhin, (bf16_t*)ddec, h, w, C3, D, (int)rpw);
-    VSX_LAUNCH_CHECK();
-    return 0;
-  }
-  if (C3 * D <= 64 && B <= 65535) {  // LDS-tiled permutation
-    vsx_by_dtype(dtype, [&](auto tag) {
-      using T = typename decltype(tag)::type;
-      constexpr int TS = sizeof(T) == 2 ? 8 : 4;  // tile edge in decoder pixels
-      hipLaunchKernelGGL((head_shuffle_bwd_tiled_kernel<T, TS>), dim3(vsx_cdiv(w, TS), vsx_cdiv(h, TS), B), dim3(256), 0, s,
-                         (const T*)dhin, (T*)ddec, h, w, C3, D, pool);
-    });
-    VSX_LAUNCH_CHECK();
-    return 0;
-  }
-  vsx_by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(head_shuffle_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dhin, (T*)ddec, B, h, w, C3, D, pool);
-  });
-  VSX_LAUNCH_CHECK();
-  return 0;
+  return head_shuffle_launch<true>("vsx_head_shuffle_bwd", 16, dhin, ddec, B, h, w, C3, D, pool, dtype, stream);
 }
 
 // ------------------------------------------------------------------ PixelToVoxelShuffleHead (FCMAE head, heads.py:656-685)
@@ -917,14 +835,16 @@ __global__ __launch_bounds__(256) void voxel_shuffle_bwd_kernel(const float* __r
   }
 }
 
+static int voxel_shuffle_grid(long total) {  // grid-stride kernels: at most 65536 workgroups
+  const int g = vsx_cdiv(total, 256);
+  return g > 65536 ? 65536 : g;
+}
 /* FCMAE head: viscy_models.components.heads.PixelToVoxelShuffleHead (heads.py:656-685) = MONAI UpSample(pixelshuffle,
  * scale s, pre_conv None, apply_pad_pool) + reshape to (B, Cout, D, s*h, s*w).  feat [B*h*w, Cout*D*s*s] dtype -> out fp32. */
 extern "C" int32_t vsx_voxel_shuffle_fwd(const void* feat, float* out, int32_t B, int32_t h, int32_t w, int32_t Cout, int32_t D,
                                          int32_t s, int32_t pool, int32_t dtype, vsx_stream_t stream) {
   VSX_CHECK(feat && out && B > 0 && h > 0 && w > 0 && Cout > 0 && D > 0 && s > 0, "vsx_voxel_shuffle_fwd: bad arguments");
-  long total = (long)B * Cout * D * h * s * w * s;
-  int g = vsx_cdiv(total, 256);
-  if (g > 65536) g = 65536;
+  const int g = voxel_shuffle_grid((long)B * Cout * D * h * s * w * s);
   vsx_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL(voxel_shuffle_fwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)feat, out, B, h, w, Cout, D, s, pool);
@@ -937,9 +857,7 @@ extern "C" int32_t vsx_voxel_shuffle_bwd(const float* dout, void* dfeat, int32_t
   int vn = vsx_vec_elems(dtype);
   VSX_CHECK(dout && dfeat && B > 0 && h > 0 && w > 0 && Cout > 0 && D > 0 && s > 0, "vsx_voxel_shuffle_bwd: bad arguments");
   VSX_CHECK((Cout * D * s * s) % vn == 0, "vsx_voxel_shuffle_bwd: Cout*D*s*s=%d must be a multiple of %d", Cout * D * s * s, vn);
-  long total = (long)B * h * w * (Cout * D * s * s / vn);
-  int g = vsx_cdiv(total, 256);
-  if (g > 65536) g = 65536;
+  const int g = voxel_shuffle_grid((long)B * h * w * (Cout * D * s * s / vn));
   vsx_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL(voxel_shuffle_bwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, dout, (T*)dfeat, B, h, w, Cout, D, s, pool);
