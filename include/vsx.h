@@ -909,6 +909,47 @@ int64_t vsx_kde_gauss_ws_bytes(int64_t n, int64_t m);
 int32_t vsx_kde_gauss(const double* data, int64_t n, const double* grid, int64_t m, double a, double* out, void* ws, int64_t ws_bytes,
     vsx_stream_t stream);
 
+/* The device passes of the clustering evaluation (csrc/clustering.hip + f64_tile.h; viscy_utils/evaluation/clustering.py
+ * pairwise_distance_matrix, dbscan_clustering, knn_accuracy).  x [N, d] fp32 row-major, any 4-byte alignment (one 16-byte read per four
+ * features where d % 4 == 0 and x is 16-byte aligned, else scalar reads of the same features), 1 <= N <= 65535 * VSX_F64_TILE,
+ * 1 <= d <= 2^20.  The dots are float64 throughout, on v_mfma_f64_16x16x4_f64: a workgroup forms a VSX_F64_TILE x VSX_F64_TILE tile from
+ * chunks of VSX_F64_KC features converted to float64 where they are staged; a product of two fp32 values is exact in float64.  ONE
+ * summation order for every (row, column), tile position and entry point, written down in f64_tile.h: ascending chunks from +0.0, eight
+ * MFMA steps of four features per chunk.  No kernel waits on another workgroup, every loop has a bound known at launch, no atomics; every
+ * output buffer may hold any contents on entry and is a pure function of the inputs.  Every check runs before any launch; anything not
+ * served is refused with a non-zero status.
+ * row_sqnorm_f64: norms[i] = dot_ii, computed as the diagonal of a tile: the bits that any tile holds for the dot of row i with itself,
+ *   and, for two bit-identical rows i and j, for dot_ij.
+ * pdist_f64: out[(i - r0) ld + (j - c0)] float64 for r0 <= i < r1, c0 <= j < c1 (0 <= r0 < r1 <= N, likewise c; ld >= c1 - c0), norms from
+ *   row_sqnorm_f64.  i == j gives exactly 0.  Otherwise, every operation rounded once (no contraction):
+ *     VSX_PDIST_COSINE       1 - dot_ij * (inv_i * inv_j), inv = 1 / max(sqrt(n), 1e-12): F.normalize's rule, a zero row is at distance 1
+ *     VSX_PDIST_SQEUCLIDEAN  max((n_i + n_j) - 2 dot_ij, 0)
+ *     VSX_PDIST_EUCLIDEAN    the correctly rounded sqrt of that
+ *   d_ij == d_ji bit for bit; two bit-identical rows are at Euclidean distance exactly 0 (n_i + n_j = 2 dot_ij exactly); a block equals the
+ *   matching slice of the whole matrix bit for bit.
+ * eps_graph: adj uint64 [N][W], W = ceil(N / 64): bit b of word w of row i is 1 iff j = 64 w + b < N and (i == j or the SQEUCLIDEAN value
+ *   <= eps2); bits past N are 0; deg[i] = the popcount of row i.  The words are ballots written by ordinary vector stores.  eps2 finite, >= 0.
+ * cc_round: one round of connected components over the edges between core rows (core [N] uint8, 0 / 1): changed[0] = 0; then every core row
+ *   takes the smallest label among itself and its core neighbours; then labels[i] <- labels[labels[i]] up to 32 times.  changed[0] = 1
+ *   (plain stores) iff a label was lowered.  The caller starts with labels[i] = i and repeats until changed[0] == 0, at most N + 1 rounds
+ *   (a round settles every row one more edge away from its component's smallest core index).  Labels move in place by plain stores; the
+ *   fixed point, labels[i] = the smallest core index of the component of core row i, does not depend on scheduling.
+ * dbscan_finish: out[i] = cid[labels[i]] for a core row; for any other row the smallest cid[labels[j]] over its core neighbours j, or -1
+ *   where it has none.  cid [N] int32: the exclusive prefix count of the roots (core rows with labels[i] == i) in ascending index. */
+#define VSX_F64_TILE 64 /* rows of either operand per tile of the float64 engine */
+#define VSX_F64_KC 32   /* features per staged chunk of the float64 engine */
+#define VSX_PDIST_COSINE 0
+#define VSX_PDIST_EUCLIDEAN 1
+#define VSX_PDIST_SQEUCLIDEAN 2
+int32_t vsx_row_sqnorm_f64(const float* x, int32_t N, int32_t d, double* norms, vsx_stream_t stream);
+int32_t vsx_pdist_f64(const float* x, const double* norms, int32_t N, int32_t d, int32_t metric, int32_t r0, int32_t r1, int32_t c0,
+    int32_t c1, double* out, int64_t ld, vsx_stream_t stream);
+int32_t vsx_eps_graph(const float* x, const double* norms, int32_t N, int32_t d, double eps2, uint64_t* adj, int32_t* deg,
+    vsx_stream_t stream);
+int32_t vsx_cc_round(const uint64_t* adj, const uint8_t* core, int32_t* labels, int32_t N, int32_t* changed, vsx_stream_t stream);
+int32_t vsx_dbscan_finish(const uint64_t* adj, const uint8_t* core, const int32_t* labels, const int32_t* cid, int32_t N, int32_t* out,
+    vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

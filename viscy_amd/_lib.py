@@ -19,7 +19,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vsx.h")
 
 # the type words of the header, and what a pointer to one becomes: buffers are opaque addresses, a char pointer is a C string
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
-_POINTERS = dict.fromkeys(("void", "float", "double", "int32_t", "int64_t", "uint8_t"), C.c_void_p) | {"char": C.c_char_p}
+_POINTERS = dict.fromkeys(("void", "float", "double", "int32_t", "int64_t", "uint8_t", "uint64_t"), C.c_void_p) | {"char": C.c_char_p}
 
 
 def parse_header(text: str, structs: dict[str, type]) -> tuple[dict, dict, dict]:

@@ -1,4 +1,4 @@
-"""The host layer under the evaluation modules (``reduce``, ``linear_classifier``, ``mmd``, ``smoothness``, ``online_eval``): what an
+"""The host layer under the evaluation modules (``reduce``, ``linear_classifier``, ``mmd``, ``smoothness``, ``clustering``, ``online_eval``): what an
 entry point does with its arguments before a kernel sees them, and the rules of sklearn that more than one module restates.  Pure
 numpy / torch; nothing here loads the kernel library.
 

@@ -1500,3 +1500,99 @@ def kde_gauss(data: Tensor, grid: Tensor, a: float) -> Tensor:
     out = torch.empty(m, dtype=torch.float64, device=data.device)
     check(lib().vsx_kde_gauss(ptr(data), n, ptr(grid), m, float(a), ptr(out), ptr(ws), ws.nbytes, stream()), "kde_gauss")
     return out
+
+
+# ------------------------------------------------------------------ clustering evaluation (csrc/clustering.hip + f64_tile.h)
+F64_TILE, F64_KC = L.F64_TILE, L.F64_KC
+PDIST_METRICS = {"cosine": L.PDIST_COSINE, "euclidean": L.PDIST_EUCLIDEAN, "sqeuclidean": L.PDIST_SQEUCLIDEAN}
+F64_MAX_ROWS = 65535 * L.F64_TILE
+
+
+def _f64_rows(x: Tensor, what: str) -> tuple[int, int]:
+    n, d = _rows_f32(x, what)
+    if not 1 <= n <= F64_MAX_ROWS:  # the library takes N as int32: ctypes would wrap it silently
+        raise ValueError(f"{what}: x has {n} rows, the kernels serve 1 .. {F64_MAX_ROWS}")
+    return n, d
+
+
+def _typed(t: Tensor, dtype: torch.dtype, shape: tuple, what: str) -> Tensor:
+    ptr(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{what} must be a {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def row_sqnorm_f64(x: Tensor) -> Tensor:
+    """-> float64 (N,): the float64 engine's own dot of every row with itself, the bits a tile holds for dot_ii"""
+    n, d = _f64_rows(x, "row_sqnorm_f64")
+    norms = torch.empty(n, dtype=torch.float64, device=x.device)
+    check(lib().vsx_row_sqnorm_f64(ptr(x), n, d, ptr(norms), stream()), "row_sqnorm_f64")
+    return norms
+
+
+def pdist_f64(x: Tensor, norms: Tensor, metric: str = "cosine", rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+              out: Tensor | None = None) -> Tensor:
+    """-> float64 (r1 - r0, c1 - c0): the block ``rows`` x ``cols`` (the whole matrix by default) of the ``metric`` ("cosine" |
+    "euclidean" | "sqeuclidean") distance matrix of x float32 (N, d); ``norms`` from ``row_sqnorm_f64``.  Exactly 0 for i == j,
+    symmetric bit for bit, and a block equals the slice of the whole matrix.  ``out``: a contiguous float64 tensor of that shape"""
+    n, d = _f64_rows(x, "pdist_f64")
+    _f64_vec(norms, n, "pdist_f64: norms")
+    if metric not in PDIST_METRICS:
+        raise ValueError(f"pdist_f64: metric {metric!r} must be one of {sorted(PDIST_METRICS)}")
+    (r0, r1), (c0, c1) = rows or (0, n), cols or (0, n)
+    if not (0 <= r0 < r1 <= n and 0 <= c0 < c1 <= n):
+        raise ValueError(f"pdist_f64: the block [{r0}, {r1}) x [{c0}, {c1}) must lie in [0, {n})")
+    if out is None:
+        out = torch.empty((r1 - r0, c1 - c0), dtype=torch.float64, device=x.device)
+    _typed(out, torch.float64, (r1 - r0, c1 - c0), "pdist_f64: out")
+    check(lib().vsx_pdist_f64(ptr(x), ptr(norms), n, d, PDIST_METRICS[metric], r0, r1, c0, c1, ptr(out), c1 - c0, stream()), "pdist_f64")
+    return out
+
+
+def eps_graph_words(n: int) -> int:
+    """64-bit words per row of the bit matrix of ``eps_graph``"""
+    return -(-int(n) // 64)
+
+
+def eps_graph(x: Tensor, norms: Tensor, eps2: float, adj: Tensor | None = None, deg: Tensor | None = None) -> tuple[Tensor, Tensor]:
+    """-> (adj int64 (N, ceil(N / 64)) holding the uint64 words, deg int32 (N,)): bit b of word w of row i is set iff j = 64 w + b < N
+    and (i == j or the squared Euclidean distance <= eps2); deg = the popcount of the row.  ``adj`` / ``deg``: buffers to fill, any
+    contents"""
+    n, d = _f64_rows(x, "eps_graph")
+    _f64_vec(norms, n, "eps_graph: norms")
+    eps2 = float(eps2)
+    if not 0.0 <= eps2 < float("inf"):
+        raise ValueError(f"eps_graph: eps2={eps2} must be finite and >= 0")
+    w = eps_graph_words(n)
+    adj = torch.empty((n, w), dtype=torch.int64, device=x.device) if adj is None else _typed(adj, torch.int64, (n, w), "eps_graph: adj")
+    deg = torch.empty(n, dtype=torch.int32, device=x.device) if deg is None else _typed(deg, torch.int32, (n,), "eps_graph: deg")
+    check(lib().vsx_eps_graph(ptr(x), ptr(norms), n, d, eps2, ptr(adj), ptr(deg), stream()), "eps_graph")
+    return adj, deg
+
+
+def _graph(adj: Tensor, core: Tensor, labels: Tensor, what: str) -> int:
+    n = int(core.numel())
+    if not 1 <= n <= F64_MAX_ROWS:
+        raise ValueError(f"{what}: {n} rows, the kernels serve 1 .. {F64_MAX_ROWS}")
+    _typed(adj, torch.int64, (n, eps_graph_words(n)), f"{what}: adj")
+    _typed(core, torch.uint8, (n,), f"{what}: core")
+    _typed(labels, torch.int32, (n,), f"{what}: labels")
+    return n
+
+
+def cc_round(adj: Tensor, core: Tensor, labels: Tensor, changed: Tensor) -> None:
+    """one round of minimum-label hooking over core-core edges plus pointer jumping, in place on ``labels`` int32 (N,); ``changed``
+    int32 (1,) is 1 afterwards iff a label was lowered"""
+    n = _graph(adj, core, labels, "cc_round")
+    _typed(changed, torch.int32, (1,), "cc_round: changed")
+    check(lib().vsx_cc_round(ptr(adj), ptr(core), ptr(labels), n, ptr(changed), stream()), "cc_round")
+
+
+def dbscan_finish(adj: Tensor, core: Tensor, labels: Tensor, cid: Tensor, out: Tensor | None = None) -> Tensor:
+    """-> int32 (N,): ``cid[labels[i]]`` for a core row, the smallest ``cid[labels[j]]`` over the core neighbours j of any other row,
+    -1 where it has none"""
+    n = _graph(adj, core, labels, "dbscan_finish")
+    _typed(cid, torch.int32, (n,), "dbscan_finish: cid")
+    out = torch.empty(n, dtype=torch.int32, device=adj.device) if out is None else _typed(out, torch.int32, (n,), "dbscan_finish: out")
+    check(lib().vsx_dbscan_finish(ptr(adj), ptr(core), ptr(labels), ptr(cid), n, ptr(out), stream()), "dbscan_finish")
+    return out
