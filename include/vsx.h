@@ -696,6 +696,21 @@ int32_t vsx_percentile_scale(const float* x, float* y, const float* a_min, const
 int32_t vsx_crop_zreduce(const float* x, float* y, const int32_t* starts, const int32_t* mode, int32_t B, int32_t C, int32_t Z,
     int32_t Y, int32_t X, int32_t cz, int32_t cy, int32_t cx, vsx_stream_t stream);
 
+/* The DynaCLR data feed (viscy_data/triplet.py:224-253, read there patch by patch through tensorstore on the host): n patches
+ * cut out of frames resident in device memory, out[p, c, z, y, x] = (float) frame_p[c, z, y0_p + y, x0_p + x], fp32
+ * [n, C, Z, Yp, Xp].  desc: n rows of VSX_PG_DESC int64 on the device: {address of the frame's element [0, 0, 0, 0], element
+ * strides of c, z and y (x is contiguous), y0, x0}; a frame is a [C, Z, H, W] block of src_dtype, or a view into a larger one.
+ * Descriptors may repeat and may name different frames.  float32 sources are copied bit for bit, integer sources convert
+ * exactly.  No load leaves [x0, x0 + Xp) of its row.  The kernel trusts the table: the caller has checked 0 <= y0,
+ * y0 + Yp <= H, 0 <= x0, x0 + Xp <= W (viscy_amd.ops.patch_gather does).  out 16-byte aligned. */
+#define VSX_PG_F32 0
+#define VSX_PG_U16 1
+#define VSX_PG_I16 2
+#define VSX_PG_U8 3
+#define VSX_PG_DESC 6
+int32_t vsx_patch_gather(const int64_t* desc, float* out, int32_t n, int32_t C, int32_t Z, int32_t Yp, int32_t Xp,
+    int32_t src_dtype, vsx_stream_t stream);
+
 /* K18 kornia warp_affine3d as used by BatchedRandAffined (viscy_transforms/_affine.py:33-47,358-393): trilinear (or
  * nearest) resampling; Minv[B][3][4] maps output-voxel to input-voxel coordinates (x, y, z order).
  * The kernel applies Minv as given; the caller folds kornia's align_corners convention into it (with align_corners=False — kornia's

@@ -38,6 +38,8 @@ CLASS_MAP = {
     "viscy_data.combined.ConcatDataModule": "viscy_amd.data.combined.ConcatDataModule",
     "viscy_data.combined.BatchedConcatDataModule": "viscy_amd.data.combined.BatchedConcatDataModule",
     "viscy_data.BatchedConcatDataModule": "viscy_amd.data.combined.BatchedConcatDataModule",
+    "viscy_data.triplet.TripletDataModule": "viscy_amd.data.triplet.TripletDataModule",
+    "viscy_data.TripletDataModule": "viscy_amd.data.triplet.TripletDataModule",
     "viscy_utils.callbacks.prediction_writer.HCSPredictionWriter": "viscy_amd.prediction_writer.HCSPredictionWriter",
     "viscy_utils.callbacks.HCSPredictionWriter": "viscy_amd.prediction_writer.HCSPredictionWriter",
     "viscy_utils.callbacks.OnlineEvalCallback": "viscy_amd.online_eval.OnlineEvalCallback",

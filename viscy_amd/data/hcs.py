@@ -54,6 +54,9 @@ def _read_norm_meta(fov) -> dict | None:
     return out
 
 
+read_norm_meta = _read_norm_meta  # the public name, as the reference re-exports it (viscy_data.read_norm_meta): triplet.py reads through it
+
+
 class Compose:
     def __init__(self, transforms: Sequence[Callable]):
         self.transforms = list(transforms)

@@ -1596,3 +1596,58 @@ def dbscan_finish(adj: Tensor, core: Tensor, labels: Tensor, cid: Tensor, out: T
     out = torch.empty(n, dtype=torch.int32, device=adj.device) if out is None else _typed(out, torch.int32, (n,), "dbscan_finish: out")
     check(lib().vsx_dbscan_finish(ptr(adj), ptr(core), ptr(labels), ptr(cid), n, ptr(out), stream()), "dbscan_finish")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ patch gather (DynaCLR data feed)
+PATCH_GATHER_DTYPES = {torch.float32: L.PG_F32, torch.uint16: L.PG_U16, torch.int16: L.PG_I16, torch.uint8: L.PG_U8}
+
+
+def patch_descriptors(frames: Sequence[Tensor], origins: Sequence[Sequence[int]], size: Sequence[int]) -> Tensor:
+    """The descriptor table of ``vsx_patch_gather`` as an int64 (n, PG_DESC) host tensor, every row checked: frame ``i`` is a
+    (C, Z, H, W) tensor (any view whose last axis is contiguous), ``origins[i] = (y0, x0)``, ``size = (Yp, Xp)``.  A patch that
+    leaves its frame on any side raises ``ValueError``; a storage dtype the kernel does not read raises ``NotImplementedError``.
+    Host code: works on tensors of any device."""
+    yp, xp = (int(v) for v in size)
+    if len(frames) == 0 or len(frames) != len(origins):
+        raise ValueError(f"patch_gather: {len(frames)} frames for {len(origins)} origins")
+    if yp <= 0 or xp <= 0:
+        raise ValueError(f"patch_gather: patch size {(yp, xp)} must be positive")
+    f0 = frames[0]
+    if f0.dtype not in PATCH_GATHER_DTYPES:
+        raise NotImplementedError(f"patch_gather: frames stored as {f0.dtype} are not built (float32, uint16, int16, uint8 are)")
+    rows, seen = [], {}  # seen: a frame serves many patches of a batch and is inspected once
+    for i, (f, (y0, x0)) in enumerate(zip(frames, origins)):
+        info = seen.get(id(f))
+        if info is None:
+            if f.ndim != 4 or f.dtype != f0.dtype or f.device != f0.device or tuple(f.shape[:2]) != tuple(f0.shape[:2]):
+                raise ValueError(f"patch_gather: frame {i} is {tuple(f.shape)} {f.dtype} on {f.device}, frame 0 is {tuple(f0.shape)} "
+                                 f"{f0.dtype} on {f0.device}: one launch serves (C, Z, H, W) frames of one dtype, C and Z")
+            sc, sz, sy, sx = f.stride()
+            if (sx != 1 and f.shape[3] > 1) or min(sc, sz, sy) < 0:
+                raise ValueError(f"patch_gather: frame {i} has strides {f.stride()}: x must be contiguous, the others >= 0")
+            info = seen[id(f)] = (f.data_ptr(), sc, sz, sy, f.shape[2], f.shape[3])
+        y0, x0, H, W = int(y0), int(x0), info[4], info[5]
+        if y0 < 0 or y0 + yp > H:
+            raise ValueError(f"patch_gather: patch {i} rows [{y0}, {y0 + yp}) leave the frame's [0, {H})")
+        if x0 < 0 or x0 + xp > W:
+            raise ValueError(f"patch_gather: patch {i} columns [{x0}, {x0 + xp}) leave the frame's [0, {W})")
+        rows.append(info[:4] + (y0, x0))
+    return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), L.PG_DESC)
+
+
+def patch_gather(frames: Sequence[Tensor], origins: Sequence[Sequence[int]], size: Sequence[int], out: Tensor | None = None) -> Tensor:
+    """-> float32 (n, C, Z, Yp, Xp): ``out[i] = frames[i][:, :, y0:y0 + Yp, x0:x0 + Xp]`` converted exactly, ONE launch for all n.
+    The table is checked and uploaded here (one small pinned copy); the frames must stay alive until the launch has been issued
+    on the current stream, which the caller's references guarantee."""
+    table = patch_descriptors(frames, origins, size)
+    f0 = frames[0]
+    if not f0.is_cuda:
+        raise RuntimeError("viscy_amd: patch_gather runs on the HIP device only (host patches: viscy_amd.data.triplet.host_cut)")
+    n, (C, Z), (yp, xp) = len(frames), f0.shape[:2], (int(v) for v in size)
+    if n * C * Z * yp * xp >= 2 ** 62 or max(n, C, Z, yp, xp) >= 2 ** 31:
+        raise ValueError("patch_gather: sizes exceed the kernel's index range")
+    dev_table = table.pin_memory().to(f0.device, non_blocking=True)
+    shape = (n, C, Z, yp, xp)
+    out = torch.empty(shape, dtype=torch.float32, device=f0.device) if out is None else _typed(out, torch.float32, shape, "patch_gather: out")
+    check(lib().vsx_patch_gather(ptr(dev_table), ptr(out), n, C, Z, yp, xp, PATCH_GATHER_DTYPES[f0.dtype], stream()), "patch_gather")
+    return out

@@ -34,6 +34,7 @@ class Trainer:
         self.finished = False
         self.global_step = 0
         self.current_epoch, self.sanity_checking, self.global_rank, self.world_size = 0, False, 0, 1
+        self.predicting = False        # Lightning's trainer.predicting: True inside predict() (TripletDataModule._find_transform)
         self.graph_step = graph_step   # False: always the eager zero_grad / training_step / backward / step loop
         self.graph_steps = 0           # optimisation steps taken through the captured TrainStep (tests, logs)
         self._train_steps: dict = {}   # batch signature -> TrainStep
@@ -229,8 +230,11 @@ class Trainer:
         prediction-writer callbacks (``write_on_batch_end``) after every batch, ``on_predict_end``."""
         module.to(self.device).eval()
         self.datamodule = datamodule
+        datamodule.trainer = self
+        self.predicting = True
         datamodule.setup("predict")
-        module.on_predict_start()
+        if hasattr(module, "on_predict_start"):  # ContrastiveModule has none
+            module.on_predict_start()
         for cb in self.callbacks:
             if hasattr(cb, "on_predict_start"):
                 cb.on_predict_start(self, module)
@@ -251,6 +255,7 @@ class Trainer:
                         if hasattr(cb, "write_on_batch_end") and getattr(cb, "interval", "batch") in ("batch", "batch_and_epoch"):
                             cb.write_on_batch_end(self, module, pred, None, batch, j, 0)
         finally:
+            self.predicting = False
             # also on an exception / interrupt: a writer with a running device-side blend still holds predicted slices that the
             # reference would have on disk by now — on_predict_end flushes them and closes the store
             for cb in self.callbacks:
