@@ -5,7 +5,9 @@
     *reverse forward order* so gradient buckets become ready front-to-back during backward) and
     the matching flat gradient buffer;
   * ``prepare()``: per-step re-layout of master weights into GEMM operands (compute dtype);
-  * ``forward()`` / ``backward()``: the explicit launch sequences.
+  * ``forward()`` / ``backward_stages()``: the launch sequences, as loops over the stages.  Each layer is a pair of adjacent
+    methods (``_stem_*``, ``_down_*``, ``_preconv_*``, ``_up_*``, ``_block_*``, a row of ``_HEADS`` per head kind) joined by a
+    named record of what the forward keeps; a block's GRN-MLP runs by its ``_MlpPlan``.  Only ``backward_stages`` yields.
 
 ``ops`` is the kernel backend: ``viscy_amd.ops`` (HIP, the only backend the product ever uses).
 Tests may inject a reference implementation of the same call surface to validate the schedule
@@ -14,6 +16,7 @@ itself on CPU (tests/ref_ops.py); nothing in the package does.
 
 from __future__ import annotations
 
+import math
 import os
 from collections import namedtuple
 from typing import NamedTuple
@@ -83,17 +86,14 @@ def _plan_mlp(flag: int, supported, C: int, hw: int, M: int, B: int, dt: torch.d
 # order readers by position know: tests/test_gpu_model.py takes colsq as item 5.)
 _BlockSaved = namedtuple("_BlockSaved", "x xh rstd h gact colsq s rows dpm plan y mean")
 _NarrowSaved = namedtuple("_NarrowSaved", "x y colsq s")
-
-
-def _views(flat: Tensor, shapes):
-    out, off = [], 0
-    for shp in shapes:
-        n = 1
-        for s in shp:
-            n *= s
-        out.append(flat[off : off + n].view(shp))
-        off += n
-    return out
+# the other layers.  Stem: P = the patch matrix (kind "narrow": the input stack), f = the LayerNorm's input, kind = "patch" |
+# "narrow" | "blockdiag" (ratio > 1), conv = the module that ran.  Down / Up: x / cat -> LayerNorm -> xn (None: narrow projection)
+_StemSaved = namedtuple("_StemSaved", "P f mean rstd kind conv kern")
+_DownSaved = namedtuple("_DownSaved", "x xn mean rstd")
+_UpSaved = namedtuple("_UpSaved", "cat xn mean rstd c_up sc pre_in")
+_HeadConvSaved = namedtuple("_HeadConvSaved", "hin U stats fh fw")
+_HeadShuffleSaved = namedtuple("_HeadShuffleSaved", "fh fw")
+_EmbedSaved = namedtuple("_EmbedSaved", "pooled mean rstd emb z0 y1 sm1 sr1 z3 y4 sm4 sr4 training fh fw fc")
 
 
 class _ZeroArena:
@@ -112,9 +112,7 @@ class _ZeroArena:
         return self.ops.zeros(*shape, device=self.dev)  # vsx_fill_f32: the captured step holds no ATen fill
 
     def take(self, *shape) -> Tensor:
-        n = 1
-        for d in shape:
-            n *= int(d)
+        n = math.prod(int(d) for d in shape)
         n_al = (n + 63) // 64 * 64  # 256-byte granules: every view stays 16-byte aligned
         self.used += n_al
         if self.buf is not None and self.off + n_al <= self.buf.numel():
@@ -132,6 +130,7 @@ class Engine(FlatEngine):
         self._hip = ops is hip_ops  # the HIP backend: the only one that has the library's flags and fused GRN-MLP passes
         self._mlp_flag = 0          # `mlp_fused` as read by the forward in flight (0 on any other backend)
         self.cfg = model.cfg
+        self.head = self.cfg.get("head", "conv")  # "conv" | "shuffle" | "embed": a row of _HEADS
         self._zeros4c = {}       # C -> zeros(4C): the identity GRN of ConvNeXt-V1 blocks
         self._dp_inject = None   # tests: list of per-sample branch scales [B], consumed in forward block order
         self._za = None          # zero arena of the pass in flight
@@ -144,29 +143,19 @@ class Engine(FlatEngine):
     def _stage_params_rev(self, stage):
         ps = []
         for blk in reversed(list(stage.blocks)):
-            if hasattr(blk, "gamma"):  # ConvNeXt-V1 block: layer scale, no GRN
-                ps += [blk.gamma, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.norm.weight,
-                       blk.norm.bias, blk.conv_dw.weight, blk.conv_dw.bias]
-                continue
-            ps += [blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp.grn.weight, blk.mlp.grn.bias, blk.mlp.fc1.weight,
-                   blk.mlp.fc1.bias, blk.norm.weight, blk.norm.bias, blk.conv_dw.weight, blk.conv_dw.bias]
+            v1 = hasattr(blk, "gamma")  # ConvNeXt-V1 block: layer scale in front, no GRN
+            ps += ([blk.gamma] if v1 else []) + [blk.mlp.fc2.weight, blk.mlp.fc2.bias]
+            ps += ([] if v1 else [blk.mlp.grn.weight, blk.mlp.grn.bias]) + [blk.mlp.fc1.weight, blk.mlp.fc1.bias]
+            ps += [blk.norm.weight, blk.norm.bias, blk.conv_dw.weight, blk.conv_dw.bias]
         if not isinstance(stage.downsample, torch.nn.Identity):
-            ps += [stage.downsample[1].weight, stage.downsample[1].bias, stage.downsample[0].weight,
-                   stage.downsample[0].bias]
+            ps += [stage.downsample[1].weight, stage.downsample[1].bias, stage.downsample[0].weight, stage.downsample[0].bias]
         return ps
 
     def _param_order(self):
         m = self.model
-        ps = []
-        if self.cfg.get("head", "conv") == "conv":
-            ps = [m.head.conv[1].weight, m.head.conv[1].bias, m.head.conv[0].adn.A.weight, m.head.conv[0].conv.weight,
-                  m.head.conv[0].conv.bias]
+        ps = self._HEADS[self.head][0](self)
         self._bucket_marks = [0]
-        if self.cfg.get("head") == "embed":  # ContrastiveEncoder: pooled-embedding tail instead of decoder + head
-            t = m.tail
-            ps = [t.bn4.weight, t.bn4.bias, t.fc3.weight, t.fc3.bias, t.bn1.weight, t.bn1.bias, t.fc0.weight, t.fc0.bias,
-                  t.norm.weight, t.norm.bias]
-        else:
+        if self.head != "embed":  # ContrastiveEncoder: pooled-embedding tail instead of decoder + head
             for st in reversed(list(m.decoder.decoder_stages)):
                 ps += self._stage_params_rev(st.conv)
                 if getattr(st, "pre_conv", None) is not None:  # decoder_upsample_pre_conv: runs before the stage in the forward
@@ -242,9 +231,23 @@ class Engine(FlatEngine):
             w.W, w.WT = o.prep_weight(conv.weight, cout, cin, taps, dt, want=True, want_t=need_bwd)
         return w
 
+    def _prep_stem(self, conv, dt, narrow_stem):
+        """-> the [Cout, K] operand of a stem's patch GEMM; None: the narrow stem runs"""
+        o, K = self.ops, conv.weight[0].numel()
+        if narrow_stem and K % 8:
+            # 2x2 stem (K = Cin * kz * 4): the patch is not a whole number of 16-byte bf16 vectors — the narrow stem reads the
+            # fp32 stack and the master weight directly (csrc/narrow.hip), no patch matrix, no GEMM operand
+            return None
+        Wp, _ = o.prep_weight(conv.weight, conv.weight.shape[0], K, 1, dt)
+        if dt == torch.bfloat16 and K % 32:
+            o.flush()  # pad_cols reads what the task list has yet to write
+            # K = 80 (the 5x4x4 single-channel stem) is not a whole number of 32-deep MFMA slabs: the projection fell to
+            # the generic GEMM (2.9 ms at B = 512, 250 GB/s).  Zero-padded to 96 on both operands it runs on the lean one.
+            Wp = o.pad_cols(Wp, (K + 31) // 32 * 32)
+        return Wp
+
     def prepare(self, dt: torch.dtype, need_bwd: bool, mlp_flag: int = 0):
-        key = (dt, need_bwd)
-        m, cfg, o = self.model, self.cfg, self.ops
+        o = self.ops
         with o.batch():  # ~150 weight-space jobs -> a handful of task-list launches (ops.batch)
             W = self._prepare_ops(dt, need_bwd)
         if dt == torch.bfloat16 and mlp_flag:
@@ -260,31 +263,19 @@ class Engine(FlatEngine):
                             w.img = o.mlp_pack(w.W1f, w.W2, w.C)
                             if bwd_img:
                                 w.img2 = o.mlp_pack(w.W2T, w.W2, w.C)
-        self.W = W
-        self._prepared_for = key
+        self.W, self._prepared_for = W, (dt, need_bwd)
         return W
 
     def _prepare_ops(self, dt: torch.dtype, need_bwd: bool):
         m, cfg, o = self.model, self.cfg, self.ops
         W = {"dt": dt}
         # stem: [Cout3d, K] (block-diagonal expansion when the stem keeps D' > 1 depth slabs)
-        sw = m.stem.conv.weight
-        co3, K = sw.shape[0], sw[0].numel()
-        Dp = cfg["ratio"]
-        narrow_stem = cfg.get("head") == "shuffle" and tuple(cfg["stem_kernel"][1:]) == (2, 2)  # built only for the 2x2 FCMAE
-        if narrow_stem and K % 8 and Dp == 1:
-            # 2x2 stem (K = Cin * kz * 4): the patch is not a whole number of 16-byte bf16 vectors — the narrow stem reads the
-            # fp32 stack and the master weight directly (csrc/narrow.hip), no patch matrix, no GEMM operand
-            W["stem_W"], W["stem_b"] = None, m.stem.conv.bias
-        elif Dp == 1:
-            W["stem_W"], _ = o.prep_weight(sw, co3, K, 1, dt)
-            if dt == torch.bfloat16 and K % 32:
-                o.flush()  # pad_cols reads what the task list has yet to write
-                # K = 80 (the 5x4x4 single-channel stem) is not a whole number of 32-deep MFMA slabs: the projection fell to
-                # the generic GEMM (2.9 ms at B = 512, 250 GB/s).  Zero-padded to 96 on both operands it runs on the lean one.
-                W["stem_W"] = o.pad_cols(W["stem_W"], (K + 31) // 32 * 32)
-            W["stem_b"] = m.stem.conv.bias
+        sw, Dp = m.stem.conv.weight, cfg["ratio"]
+        narrow_stem = self.head == "shuffle" and tuple(cfg["stem_kernel"][1:]) == (2, 2)  # built only for the 2x2 FCMAE
+        if Dp == 1:
+            W["stem_W"], W["stem_b"] = self._prep_stem(m.stem.conv, dt, narrow_stem), m.stem.conv.bias
         else:  # rare configuration (Z = 15): tiny weight-space expansion done with tensor ops
+            co3, K = sw.shape[0], sw[0].numel()
             we = torch.zeros((co3, Dp, Dp, K), dtype=torch.float32, device=self.device)
             for d in range(Dp):
                 we[:, d, d, :] = sw.detach().reshape(co3, K)
@@ -292,14 +283,7 @@ class Engine(FlatEngine):
             W["stem_b"] = m.stem.conv.bias.detach().repeat_interleave(Dp).contiguous()
         s2 = getattr(m, "stem2d", None)
         if s2 is not None:  # FCMAE: Conv2d stem of Z == 1 inputs (fcmae.py:348-353,369-370) — the same patch GEMM with kz = 1
-            K2 = s2.weight[0].numel()
-            W["stem2d_W"] = None
-            if not (narrow_stem and K2 % 8):
-                W["stem2d_W"], _ = o.prep_weight(s2.weight, s2.weight.shape[0], K2, 1, dt)
-            if W["stem2d_W"] is not None and dt == torch.bfloat16 and K2 % 32:
-                o.flush()
-                W["stem2d_W"] = o.pad_cols(W["stem2d_W"], (K2 + 31) // 32 * 32)
-            W["stem2d_b"] = s2.bias
+            W["stem2d_W"], W["stem2d_b"] = self._prep_stem(s2, dt, narrow_stem), s2.bias
         enc = []
         for i in range(4):
             st = getattr(m.encoder_stages, f"stages_{i}")
@@ -315,13 +299,7 @@ class Engine(FlatEngine):
                 bw.dp = float(r)
         W["enc"] = enc
         dec = []
-        if cfg.get("head") == "embed":
-            t = m.tail
-            E, Cf = t.fc0.weight.shape
-            P = t.fc3.weight.shape[0]
-            W["fc0"], W["fc0T"] = o.prep_weight(t.fc0.weight, E, Cf, 1, torch.float32, want=True, want_t=need_bwd)
-            W["fc3"], W["fc3T"] = o.prep_weight(t.fc3.weight, P, E, 1, torch.float32, want=True, want_t=need_bwd)
-        else:
+        if self.head != "embed":
             for us in m.decoder.decoder_stages:
                 st = us.conv
                 proj = self._prep_proj(st.downsample[0], st.downsample[1], dt, need_bwd)
@@ -337,16 +315,7 @@ class Engine(FlatEngine):
                     pre.append((pc, *o.prep_weight(pc.weight, cpc, cpc, 9, dt, want=True, want_t=need_bwd)))
             W["dec_pre"] = pre
         W["dec"] = dec
-        if cfg.get("head", "conv") == "conv":
-            hc = m.head.conv[0].conv
-            cmid, c3 = hc.weight.shape[0], hc.weight.shape[1]
-            hdt = self._head_dtype(dt)
-            W["head_Wc"], _ = o.prep_weight(hc.weight, cmid, c3, 27, hdt, tapmode=1)
-            if need_bwd:
-                if hdt == torch.bfloat16 and c3 == 8 and cmid == 32 and cfg["out_stack_depth"] == 5:
-                    o.flush()  # reads head_Wc
-                    W["head_Wp"] = o.head_conv_dgrad_prep(W["head_Wc"])  # direct LDS-tiled dgrad (csrc/headconv.hip)
-                W["head_Wd"] = o.prep_head_dgrad(hc.weight, cmid, c3, cfg["out_stack_depth"], hdt)
+        self._HEADS[self.head][1](self, W, dt, need_bwd)
         return W
 
     def _head_dtype(self, dt: torch.dtype) -> torch.dtype:
@@ -480,53 +449,66 @@ class Engine(FlatEngine):
         t = o.grn_bwd_stats(colsq, PS[0], w.grn_w, g(blk.mlp.grn.weight), Sb=PS[1], dbeta=g(blk.mlp.grn.bias))
         dW1f, db1f = self._za.take(4 * C, C), self._za.take(4 * C)
         dy = o.narrow_block_bwd_b(dout, y, w.W1f, w.b1f, s, t, w.W2, dW1f, db1f, B, H, Wd, C)
-        o.unprep_grad(dW1f, g(blk.mlp.fc1.weight), 4 * C, C, 1, gamma=blk.norm.weight, W=blk.mlp.fc1.weight,
-                      dgamma=g(blk.norm.weight), u=db1f, beta=blk.norm.bias)
-        o.matvec_t_add(blk.mlp.fc1.weight, db1f, g(blk.norm.bias), 4 * C, C)
-        o.transpose_f32(db1f, g(blk.mlp.fc1.bias), 4 * C, 1, True)
+        self._fc1_unfold(blk, dW1f, db1f, C)
         ddw = self._za.take(49, C)
         dx = o.narrow_block_bwd_c(dy, x, dout, w.dw_w, ddw, g(blk.conv_dw.bias), B, H, Wd, C)
         o.transpose_f32(ddw, g(blk.conv_dw.weight), 49, C, True)
         return dx
 
+    def _fc1_unfold(self, blk, dW1f, db1f, C, rowsub=None):
+        # unfold the LayerNorm affine: dW1 = dW1f·diag(γ) + db1f ⊗ β, dγ = Σ_r dW1f ⊙ W1, dβ = W1ᵀ db1f, db1 = db1f
+        o, g = self.ops, self.g
+        o.unprep_grad(dW1f, g(blk.mlp.fc1.weight), 4 * C, C, 1, gamma=blk.norm.weight, W=blk.mlp.fc1.weight,
+                      dgamma=g(blk.norm.weight), u=db1f, beta=blk.norm.bias, rowsub=rowsub)
+        o.matvec_t_add(blk.mlp.fc1.weight, db1f, g(blk.norm.bias), 4 * C, C)
+        o.transpose_f32(db1f, g(blk.mlp.fc1.bias), 4 * C, 1, True)  # g(b1) += db1f (a [4C, 1] "transpose": no ATen launch in the step)
+
     def _block_bwd(self, dout, w, saved, B, H, Wd, dt):
+        # four phases on the schedule the forward planned (``saved.plan``), whatever `mlp_fused` says by now (a pass whose flag
+        # bit was cleared in between is refused by the library); dz and dx^ are released here, where they die, not by a phase
         if w.C < 16:
             return self._block_bwd_narrow(dout, w, saved, B, H, Wd)
-        o, g = self.ops, self.g
-        C, M = w.C, B * H * Wd
-        blk = w.p
-        x, xh, rstd, h, gact, colsq, s, rows, dpm, plan, y, mean = saved
-        dev = dout.device
-        hw = H * Wd
-        dfull = dout
-        if rows is not None:  # masked path: the MLP branch only sees the gradient of the kept tokens
-            idx, inv, keep, Lr = rows
-            M, hw = B * Lr, Lr
-            dout = o.rows_select(dfull, idx, M, C)
-        if dpm is not None:  # the branch saw dout * (0 | 1/keep) of its sample; the shortcut keeps the full gradient (dfull)
-            dout = o.scale_rows_samples(dout, dpm, M, C, hw)
+        o, C, sv = self.ops, w.C, saved
+        M, hw, dfull = B * H * Wd, H * Wd, dout
+        if sv.rows is not None:  # masked path: the MLP branch only sees the gradient of the kept tokens
+            M, hw = B * sv.rows[3], sv.rows[3]
+            dout = o.rows_select(dfull, sv.rows[0], M, C)
+        if sv.dpm is not None:  # the branch saw dout * (0 | 1/keep) of its sample; the shortcut keeps the full gradient (dfull)
+            dout = o.scale_rows_samples(dout, sv.dpm, M, C, hw)
+        PS, dgw, dgb = self._mlp_bwd_fc2(dout, w, sv, B, M, C, hw, dt)
+        dz, db1f, u1 = self._mlp_bwd_dh(dout, w, sv, PS, dgw, dgb, M, C, hw, dt)
+        dy, dxh, dW1f = self._mlp_bwd_fc1(dz, w, sv, M, C, dt)
+        del dz
+        self._fc1_unfold(w.p, dW1f, db1f, C, rowsub=u1)
+        if dy is None:
+            dy = o.ln_bwd(dxh, sv.xh, None, sv.rstd, None, None, None, None, M, C)
+        del dxh
+        if sv.rows is not None:
+            dy = o.rows_select(dy, sv.rows[1], B * H * Wd, C)  # adjoint of the gather: zero-filled scatter
+        return self._dw_bwd(dy, dfull, w, sv, B, H, Wd)
+
+    def _mlp_bwd_fc2(self, dout, w, sv, B, M, C, hw, dt):
+        """phase 1: fc2 weight / bias gradient, with the GRN statistics PS = {P_b, S_b} where they ride in it; -> PS, dgw, dgb"""
+        o, g, blk, plan, gact, s = self.ops, self.g, w.p, sv.plan, sv.gact, sv.s
         if w.v1:  # gradients of the folded (Ws, bs) and of the (constant, zero) GRN land in scratch
             dW2, db2 = self._za.take(C, 4 * C), self._za.take(C)
             dgw, dgb = self._za.take(4 * C), self._za.take(4 * C)
         else:
             dW2, db2 = g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias)
             dgw, dgb = g(blk.mlp.grn.weight), g(blk.mlp.grn.bias)
-        # the schedule is the one the forward planned, whatever `mlp_fused` says by now (a pass whose flag bit was cleared in
-        # between is refused by the library)
-        fused_bwd, stats_in_tn = plan.bwd, plan.tn_stats
         PS = self._za.take(2, B, 4 * C)
-        if fused_bwd == 1:
+        if plan.bwd == 1:
             # dz = dout·W2 is LINEAR in dout, so everything the backward needs from "Σ over the sample of dz·(something)" comes
             # out of the per-sample products Q_b = dout_bᵀ·g_b that the weight gradient computes anyway:
             #   P_b = Σ_hw dz·g = Σ_c W2[c,:]·Q_b[c,:],  S_b = Σ_hw dz = Σ_c W2[c,:]·cs_b[c],  dW2 = Σ_b s_b·Q_b + cs⊗β
             # — one TN GEMM without operand prologue (30 % faster than the prologue form) and a tiny reduction replace the
             # fc2 weight-gradient GEMM AND the statistics pass over the 4C-wide tensors; dz is never formed for them
-            Qb = torch.empty((B, C, 4 * C), dtype=torch.float32, device=dev)
-            csb = torch.empty((B, C), dtype=torch.float32, device=dev)
+            Qb = torch.empty((B, C, 4 * C), dtype=torch.float32, device=dout.device)
+            csb = torch.empty((B, C), dtype=torch.float32, device=dout.device)
             o.gemm("tn", gact, dout, Qb, M, C, 4 * C, 4 * C, C, 4 * C, dtype=dt, hw=hw, colsum=csb, b_bstride=C * 4 * C)
             o.grn_q_reduce(Qb, csb, w.W2, s, w.grn_b, PS[0], PS[1], dW2, db2)
             del Qb
-        elif stats_in_tn:
+        elif plan.tn_stats:
             # round 5: the products are too large to store (C = 384 at B = 512), but each per-sample TILE of Q_b passes through the
             # accumulators of the fc2 weight-gradient GEMM anyway — that launch scales it by s_b into dW2 and contracts it with its
             # W2 tile into P_b on the way (csrc/gemm.hip, gemm_tn_fast_kernel PRO == 2).  The statistics pass that recomputed dz for
@@ -548,231 +530,197 @@ class Engine(FlatEngine):
         if w.v1:
             o.layer_scale_unfold(dW2, db2, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma, g(blk.mlp.fc2.weight),
                                  g(blk.mlp.fc2.bias), g(blk.gamma))
-        ln_re = not plan.keep_xh  # the forward stored no normalised rows: y and the row means instead (MODE 7)
-        u1 = None
-        if ln_re:
-            cs2 = self._za.take(2, 4 * C)  # {column sums of dh, u = sum_r dh' * mean}
-            db1f, u1 = cs2[0], cs2[1]
-        else:
-            db1f = self._za.take(4 * C)
-        if fused_bwd:
+        return PS, dgw, dgb
+
+    def _mlp_bwd_dh(self, dout, w, sv, PS, dgw, dgb, M, C, hw, dt):
+        """phase 2: -> (dz holding dh, its column sums db1f, u1 = Σ_r dh' · mean where the forward kept y instead of x^)"""
+        o, plan, s = self.ops, sv.plan, sv.s
+        # not keep_xh: the forward stored y and the row means, no normalised rows (MODE 7); cs2 = {column sums of dh, u = sum_r dh' * mean}
+        cs2 = None if plan.keep_xh else self._za.take(2, 4 * C)
+        db1f, u1 = (self._za.take(4 * C), None) if cs2 is None else (cs2[0], cs2[1])
+        if plan.bwd:
             # the 4C-wide dz is never written: the statistics came from the per-sample products above; this pass recomputes
             # dz = dout·W2 tile by tile (K = C is short) and writes dh directly (csrc/mlp.hip MODE 4) — one 4C-wide write
             # where the unfused pair (dz GEMM, then GRN / GELU backward over it) has two
             img2 = w.img2
             assert img2 is not None  # plan.bwd != 0 needs bit 3 and MODE 4 at the forward: prepare() packed it then
-            if fused_bwd == 2 and not stats_in_tn:  # statistics by recomputing dz tile by tile (P = Σ dz·g, S = Σ dz), nothing stored
-                o.mlp_bwd_stats(dout, img2, gact, PS[0], PS[1], M, C, hw)
-            if stats_in_tn:
-                t = o.grn_bwd_stats(colsq, PS[0], w.grn_w, dgw)
+            if plan.bwd == 2 and not plan.tn_stats:  # statistics by recomputing dz tile by tile (P = Σ dz·g, S = Σ dz), nothing stored
+                o.mlp_bwd_stats(dout, img2, sv.gact, PS[0], PS[1], M, C, hw)
+            if plan.tn_stats:
+                t = o.grn_bwd_stats(sv.colsq, PS[0], w.grn_w, dgw)
             else:
-                t = o.grn_bwd_stats(colsq, PS[0], w.grn_w, dgw, Sb=PS[1], dbeta=dgb)
-            if ln_re:  # h recomputed from y re-normalised on chip; dz holds dh * rstd (MODE 7)
-                dz = o.mlp_bwd_dh_ln(dout, y, mean, rstd, img2, w.img, w.b1f, s, t, cs2, M, C, hw)
+                t = o.grn_bwd_stats(sv.colsq, PS[0], w.grn_w, dgw, Sb=PS[1], dbeta=dgb)
+            if not plan.keep_xh:  # h recomputed from y re-normalised on chip; dz holds dh * rstd (MODE 7)
+                dz = o.mlp_bwd_dh_ln(dout, sv.y, sv.mean, sv.rstd, img2, w.img, w.b1f, s, t, cs2, M, C, hw)
             elif not plan.keep_h:  # h recomputed on chip from the normalised rows (MODE 5)
-                dz = o.mlp_bwd_dh_re(dout, xh, img2, w.img, w.b1f, s, t, db1f, M, C, hw)
+                dz = o.mlp_bwd_dh_re(dout, sv.xh, img2, w.img, w.b1f, s, t, db1f, M, C, hw)
             else:
-                dz = o.mlp_bwd_dh(dout, img2, h, s, t, db1f, M, C, hw)  # (named dz below: it holds dH)
+                dz = o.mlp_bwd_dh(dout, img2, sv.h, s, t, db1f, M, C, hw)  # (named dz: it holds dH)
         else:
             # fc2 data gradient dZ, with Σ dZ·gelu(h) (GRN statistics path) and Σ dZ (GRN beta gradient)
-            dz = torch.empty((M, 4 * C), dtype=dt, device=dev)
-            o.gemm("nt", dout, w.W2T, dz, M, 4 * C, C, C, C, 4 * C, dtype=dt, epi=L.EPI_DZ, aux=gact, ldx=4 * C, red0=PS[0],
+            dz = torch.empty((M, 4 * C), dtype=dt, device=dout.device)
+            o.gemm("nt", dout, w.W2T, dz, M, 4 * C, C, C, C, 4 * C, dtype=dt, epi=L.EPI_DZ, aux=sv.gact, ldx=4 * C, red0=PS[0],
                    red1=PS[1], hw=hw)
-            t = o.grn_bwd_stats(colsq, PS[0], w.grn_w, dgw, Sb=PS[1], dbeta=dgb)
-            o.grn_gelu_bwd(dz, h, s, t, db1f, M, 4 * C, hw)  # dz now holds dH
-        # fc1 data gradient; where one column tile spans the row (C <= 256) the block LayerNorm's backward rides in the GEMM's
-        # epilogue (VSX_EPI_LN_BWD): dx^ is never written, the LayerNorm-backward launch and two C-wide passes go
-        if ln_re:
+            t = o.grn_bwd_stats(sv.colsq, PS[0], w.grn_w, dgw, Sb=PS[1], dbeta=dgb)
+            o.grn_gelu_bwd(dz, sv.h, s, t, db1f, M, 4 * C, hw)  # dz now holds dH
+        return dz, db1f, u1
+
+    def _mlp_bwd_fc1(self, dz, w, sv, M, C, dt):
+        """phase 3, the two GEMMs over dz: fc1 data gradient and folded weight gradient; -> (dy | None, dx^ | None, dW1f)"""
+        o, xh = self.ops, sv.xh
+        if not sv.plan.keep_xh:
             # dz = dh * rstd: the accumulator is rstd * dx^ already, x^ is re-formed from y in the epilogue; the weight gradient
-            # contracts dz with y itself, dh^T x^ = dz^T y - u (x) 1 — the rank-1 term goes in the unfold below
-            xh = y
+            # contracts dz with y itself, dh^T x^ = dz^T y - u (x) 1 — the rank-1 term goes in the unfold (`rowsub`)
+            xh = sv.y
+        # where one column tile spans the row (C <= 256) the block LayerNorm's backward rides in the data-gradient GEMM's epilogue
+        # (VSX_EPI_LN_BWD): dx^ is never written, the LayerNorm-backward launch and two C-wide passes go
         # (a HIP kernel only; None: the shape is not served)
-        dy = o.dgrad_ln_bwd(dz, w.W1fT, xh, rstd, M, C, 4 * C, mean=mean) if self._hip else None
-        assert dy is not None or not ln_re  # the plan drops x^ only where this epilogue serves the shape
+        dy = o.dgrad_ln_bwd(dz, w.W1fT, xh, sv.rstd, M, C, 4 * C, mean=sv.mean) if self._hip else None
+        assert dy is not None or sv.plan.keep_xh  # the plan drops x^ only where this epilogue serves the shape
         dxh = None
         if dy is None:
-            dxh = torch.empty((M, C), dtype=dt, device=dev)
+            dxh = torch.empty((M, C), dtype=dt, device=dz.device)
             o.gemm("nt", dz, w.W1fT, dxh, M, C, 4 * C, 4 * C, 4 * C, C, dtype=dt)
         dW1f = self._za.take(4 * C, C)
         o.gemm("tn", xh, dz, dW1f, M, 4 * C, C, C, 4 * C, C, dtype=dt)
-        del dz
-        # unfold the LayerNorm affine: dW1 = dW1f·diag(γ) + db1f ⊗ β, dγ = Σ_r dW1f ⊙ W1, dβ = W1ᵀ db1f, db1 = db1f
-        o.unprep_grad(dW1f, g(blk.mlp.fc1.weight), 4 * C, C, 1, gamma=blk.norm.weight, W=blk.mlp.fc1.weight,
-                      dgamma=g(blk.norm.weight), u=db1f, beta=blk.norm.bias, rowsub=u1)
-        o.matvec_t_add(blk.mlp.fc1.weight, db1f, g(blk.norm.bias), 4 * C, C)
-        o.transpose_f32(db1f, g(blk.mlp.fc1.bias), 4 * C, 1, True)  # g(b1) += db1f (a [4C, 1] "transpose": no ATen launch in the step)
-        if dy is None:
-            dy = o.ln_bwd(dxh, xh, None, rstd, None, None, None, None, M, C)
-        del dxh
-        if rows is not None:
-            dy = o.rows_select(dy, inv, B * H * Wd, C)  # adjoint of the gather: zero-filled scatter
+        return dy, dxh, dW1f
+
+    def _dw_bwd(self, dy, dfull, w, sv, B, H, Wd):
+        """phase 4: depthwise 7x7 data gradient + the shortcut's gradient ``dfull``, and the 7x7 weight / bias gradient"""
+        o, g, C, blk = self.ops, self.g, w.C, w.p
         dx = o.dwconv7_bwd_data(dy, w.dw_w, dfull, B, H, Wd, C)
         ddw = self._za.take(49, C)
-        o.dwconv7_bwd_weight(dy, x, ddw, g(blk.conv_dw.bias), B, H, Wd, C)
+        o.dwconv7_bwd_weight(dy, sv.x, ddw, g(blk.conv_dw.bias), B, H, Wd, C)
         o.transpose_f32(ddw, g(blk.conv_dw.weight), 49, C, True)
-        if rows is not None:
-            dx = o.rows_select(dx, keep, B * H * Wd, C)  # adjoint of `x *= unmasked` (shortcut and dwconv input alike)
+        if sv.rows is not None:
+            dx = o.rows_select(dx, sv.rows[2], B * H * Wd, C)  # adjoint of `x *= unmasked` (shortcut and dwconv input alike)
         return dx
 
-    # ------------------------------------------------------------------ forward
-    def forward(self, x: Tensor, dt: torch.dtype, need_bwd: bool, masks=None, bn_groups: int = 1):
-        """A forward WITHOUT a backward behind it (predict / validation / `InferStep` captures) forms the per-sample GRN and
-        InstanceNorm sums in a fixed order (`ops.det_scope`: what the `det_reduce` flag does, for this thread only), as the
-        reference's CPU path is deterministic: with fp32 atomics the bf16 forward at 2048^2 differs by 7e-3 of the output maximum
-        from run to run, the fixed order costs 0.3 % of a pass (profiles/r05_det_reduce.txt; VERDICT r5).  Training forwards
-        keep the atomics unless the `det_reduce` flag is set by hand;
-        ``VSX_DET_INFER=0`` in the environment switches the automatic setting off."""
-        auto = (not need_bwd) and self._hip and os.environ.get("VSX_DET_INFER", "1") != "0"
-        with hip_ops.det_scope(auto):  # per thread: the process-wide flag is left alone
-            return self._forward(x, dt, need_bwd, masks, bn_groups)
+    # ------------------------------------------------------------------ one dense layer's backward
+    def _dense_bwd(self, x, d, WT, dW, db, M, N, K, dt, patch2=None):
+        """out[M, N] = x[M, K]·Wᵀ + b: dW += dᵀx by a TN GEMM with the column sums of d into db, then dx = d·W by an NT GEMM
+        through the prepared transpose WT.  patch2 = (gh, gw): x is the 2x2-patch gather (A_PATCH2) of a [4M, K / 4] map, to
+        which dx is scattered back; the weight gradient is staged in the arena and unfolded into dW tap by tap"""
+        o, ldx, ka, kc = self.ops, K, {}, {}
+        if patch2 is not None:
+            ldx = K // 4
+            ka = dict(a_mode=L.A_PATCH2, gh=patch2[0], gw=patch2[1], cs=ldx)
+            kc = dict(c_mode=L.A_PATCH2, c_cs=ldx, gh=patch2[0], gw=patch2[1])
+        stage = dW if patch2 is None else self._za.take(N, K)
+        o.gemm("tn", x, d, stage, M, N, K, ldx, N, K, dtype=dt, colsum=db, **ka)
+        if patch2 is not None:
+            o.unprep_grad(stage, dW, N, ldx, 4)
+        dx = torch.empty((M * K // ldx, ldx), dtype=dt, device=d.device)
+        o.gemm("nt", d, WT, dx, M, K, N, N, N, ldx, dtype=dt, **kc)
+        return dx
 
-    def _forward(self, x: Tensor, dt: torch.dtype, need_bwd: bool, masks=None, bn_groups: int = 1):
-        """``masks``: None (dense) or, per encoder stage, ``(idx, inv, keep, L)`` int32 row maps of the FCMAE mask at that
-        stage's resolution (see ``viscy_amd.fcmae.stage_row_maps``)."""
+    # ------------------------------------------------------------------ layers: forward, backward and the record between them
+    def _stem_fwd(self, x, W, flat_stem, dt, sv):
+        """patch gather + projection GEMM (or the narrow stem), then the encoder's stem_1 LayerNorm2d; -> [B*h*w, C0]"""
         o, cfg, m = self.ops, self.cfg, self.model
-        # read once: prepare() packs the weight images and every block of this forward plans its schedule from this value
-        self._mlp_flag = L.lib().vsx_get_flag(b"mlp_fused") if self._hip else 0
-        W = self.prepare(dt, need_bwd, self._mlp_flag)
-        B, Cin, Z, H, Wd = x.shape
-        za_key = ("fwd", B, H, Wd, masks is not None)
-        self._za = za = _ZeroArena(x.device, self._za_need.get(za_key, 0), o)
-        # FCMAE 2-D branch (fcmae.py:369-370): the reference runs conv2d whenever x.shape[2] == 1, whatever in_stack_depth is —
-        # a 2-D FCMAE (in_stack_depth = 1) trains and loads its conv2d weights, never the conv3d ones (ADVICE r2)
-        flat_stem = Z == 1 and "stem2d_W" in W
-        if Cin != cfg["in_channels"] or (Z != cfg["in_stack_depth"] and not flat_stem):
-            raise ValueError(f"expected input (B,{cfg['in_channels']},{cfg['in_stack_depth']},Y,X), got {tuple(x.shape)}")
-        kz, ky, kx = cfg["stem_kernel"]
-        if H % (8 * ky) or Wd % (8 * kx):
-            raise ValueError(f"Y and X must be divisible by {8 * ky} (got {H}x{Wd}); VSUNet pads to a multiple of 64")
-        h, w = H // ky, Wd // kx
-        dims = cfg["dims"]
-        C0 = dims[0]
-        # the prepared operands travel with the forward that used them: a later (no_grad / other dtype) forward re-prepares
-        # self.W, and the backward of THIS forward must still see its own transposed weights (ADVICE r1)
-        sv = {"shape": (B, H, Wd), "dt": dt, "masked": masks is not None, "W": W} if need_bwd else None
-        if need_bwd:
-            self._count_forward()
-        # ---- stem: patch gather + projection GEMM, then encoder stem_1 LayerNorm2d
-        stem_W, stem_b = (W["stem2d_W"], W["stem2d_b"]) if flat_stem else (W["stem_W"], W["stem_b"])
-        skern = (1 if flat_stem else kz, ky, kx)
-        M0 = B * h * w
+        stem_W, stem_b, conv = (W["stem2d_W"], W["stem2d_b"], m.stem2d) if flat_stem else (W["stem_W"], W["stem_b"], m.stem.conv)
+        kern = (1 if flat_stem else cfg["stem_kernel"][0], *cfg["stem_kernel"][1:])
         if stem_W is None:  # narrow stem (K not a multiple of 8): no patch matrix; the backward re-reads the stack
-            P = x.contiguous()
-            f = o.narrow_stem_fwd(P, m.stem2d.weight if flat_stem else m.stem.conv.weight, stem_b, skern, dt)
+            P, kind = x.contiguous(), "narrow"
+            f = o.narrow_stem_fwd(P, conv.weight, stem_b, kern, dt)
         else:
-            P = o.stem_im2col(x.contiguous(), skern, dt, ld=stem_W.shape[1])
-            K0 = P.shape[1]
+            P, kind = o.stem_im2col(x.contiguous(), kern, dt, ld=stem_W.shape[1]), "patch"
+            if cfg["ratio"] > 1 and not flat_stem:
+                kind = "blockdiag"  # stem_W is the block-diagonal expansion over the ratio depth slabs (_prepare_ops)
+            M0, C0, K0 = P.shape[0], cfg["dims"][0], P.shape[1]
             f = torch.empty((M0, C0), dtype=dt, device=x.device)
             o.gemm("nt", P, stem_W, f, M0, C0, K0, K0, K0, C0, dtype=dt, epi=L.EPI_BIAS, bias=stem_b)
         ln1 = m.encoder_stages.stem_1
-        cur, mean, rstd = o.ln_fwd(f, ln1.weight, ln1.bias, M0, C0)
-        if need_bwd:
-            sv["stem"] = (P, f, mean, rstd)
-            sv["flat_stem"] = flat_stem
-            sv["stem_narrow"] = skern if stem_W is None else None
+        cur, mean, rstd = o.ln_fwd(f, ln1.weight, ln1.bias, f.shape[0], f.shape[1])
+        if sv is not None:
+            sv["stem"] = _StemSaved(P, f, mean, rstd, kind, conv, kern)
+        return cur
+
+    def _stem_bwd(self, d, s, dt):
+        o, g, Dp, ln1 = self.ops, self.g, self.cfg["ratio"], self.model.encoder_stages.stem_1
+        P, f, conv, (M0, C0), K0 = s.P, s.f, s.conv, s.f.shape, s.P.shape[1]
+        df = o.ln_bwd(d, f, s.mean, s.rstd, ln1.weight, None, g(ln1.weight), g(ln1.bias), M0, C0)
+        if s.kind == "narrow":  # patches recomputed from the stored stack (P is x here)
+            o.narrow_stem_wgrad(P, df, g(conv.weight), g(conv.bias), s.kern)
+        elif s.kind == "patch":
+            Kw = conv.weight[0].numel()  # the patch matrix may carry zero-padded tail columns (lda = K0 >= Kw)
+            o.gemm("tn", P, df, g(conv.weight), M0, C0, Kw, K0, C0, Kw, dtype=dt, colsum=g(conv.bias))
+        else:  # block-diagonal expansion (ratio > 1): the gradient of the expanded weight, folded back onto its diagonal blocks
+            co3, K = C0 // Dp, K0 // Dp
+            dWe, dbe = self._za.take(C0, K0), self._za.take(C0)
+            o.gemm("tn", P, df, dWe, M0, C0, K0, K0, C0, K0, dtype=dt, colsum=dbe)
+            dWe = dWe.view(co3, Dp, Dp, K)
+            g(conv.weight).add_(torch.stack([dWe[:, dd, dd] for dd in range(Dp)], 0).sum(0).view_as(conv.weight))
+            g(conv.bias).add_(dbe.view(co3, Dp).sum(1))
+
+    def _down_fwd(self, cur, proj, B, ch, cw, dt, st_sv):
+        """encoder downsampling onto the ch x cw grid: LayerNorm2d, then the 2x2 stride-2 convolution as a patch-gather GEMM"""
+        o, cc = self.ops, proj.cin
+        xn, mean, rstd = o.ln_fwd(cur, proj.ln.weight, proj.ln.bias, B * 4 * ch * cw, cc)
+        nxt = torch.empty((B * ch * cw, proj.cout), dtype=dt, device=cur.device)
+        o.gemm("nt", xn, proj.W, nxt, B * ch * cw, proj.cout, 4 * cc, cc, 4 * cc, proj.cout, dtype=dt,
+               a_mode=L.A_PATCH2, gh=ch, gw=cw, cs=cc, epi=L.EPI_BIAS, bias=proj.conv.bias)
+        st_sv["proj"] = _DownSaved(cur, xn, mean, rstd)
+        return nxt
+
+    def _down_bwd(self, d, proj, s, dskip, B, ch, cw, dt):
+        """... and the gradient ``dskip`` that the decoder sent to this layer's input (the skip) rides in the LayerNorm backward"""
+        o, g, cin = self.ops, self.g, proj.cin
+        dxn = self._dense_bwd(s.xn, d, proj.WT, g(proj.conv.weight), g(proj.conv.bias), B * ch * cw, proj.cout, 4 * cin, dt, (ch, cw))
+        return o.ln_bwd(dxn, s.x, s.mean, s.rstd, proj.ln.weight, dskip, g(proj.ln.weight), g(proj.ln.bias), B * 4 * ch * cw, cin)
+
+    def _preconv_fwd(self, feat, pre, B, fh, fw, fc, dt):
+        """decoder_upsample_pre_conv (MONAI SubpixelUpsample conv_block): dense 3x3 convolution at the low resolution"""
+        o, (pc, Wp, _) = self.ops, pre
+        col = o.im2col3x3(feat, B, fh, fw, fc)
+        out = torch.empty((B * fh * fw, fc), dtype=dt, device=feat.device)
+        o.gemm("nt", col, Wp, out, B * fh * fw, fc, 9 * fc, 9 * fc, 9 * fc, fc, dtype=dt, epi=L.EPI_BIAS, bias=pc.bias)
+        return out
+
+    def _preconv_bwd(self, d, pre, pre_in, B, lh, lw, dt):
+        """weight gradient from the re-gathered patch matrix, data gradient through its transpose"""
+        o, g, (pc, _, WpT) = self.ops, self.g, pre
+        cpc, Ml = pc.weight.shape[0], B * lh * lw
+        col = o.im2col3x3(pre_in, B, lh, lw, cpc)
+        dWp = self._za.take(cpc, 9 * cpc)
+        o.gemm("tn", col, d, dWp, Ml, cpc, 9 * cpc, 9 * cpc, cpc, 9 * cpc, dtype=dt, colsum=g(pc.bias))
+        o.unprep_grad(dWp, g(pc.weight), cpc, cpc, 9)
+        del col
+        dcol = torch.empty((Ml, 9 * cpc), dtype=dt, device=d.device)
+        o.gemm("nt", d, WpT, dcol, Ml, 9 * cpc, cpc, cpc, cpc, 9 * cpc, dtype=dt)
+        return o.col2im3x3(dcol, B, lh, lw, cpc)
+
+    def _up_fwd(self, feat, skip, pre, proj, B, fh, fw, fc, dt, st_sv):
+        """decoder stage entry: (pre-convolution,) pixel shuffle x2 concatenated with the skip, LayerNorm2d, 1x1 projection"""
+        o, (skip, sh, sw_, sc) = self.ops, skip
+        assert sh == 2 * fh and sw_ == 2 * fw
+        c_up = fc // 4
+        low = feat if pre is None else self._preconv_fwd(feat, pre, B, fh, fw, fc, dt)
+        cat = o.pixel_shuffle_cat_fwd(low, skip, B, fh, fw, c_up, sc)
+        Mk, ccat = B * sh * sw_, c_up + sc
+        if proj.cout < 16:  # narrow stage (2x2 stem: C = 4 or 8): LayerNorm + 1x1 projection in one pass, xn not stored
+            cur, mean, rstd = o.narrow_proj_fwd(cat, proj.ln.weight, proj.ln.bias, proj.conv.weight, proj.conv.bias, Mk, ccat,
+                                                proj.cout)
+            xn = None
         else:
-            del P, f
-        # ---- encoder
-        feats, enc_sv = [], []
-        ch, cw, cc = h, w, C0
-        for i, (proj, blocks) in enumerate(W["enc"]):
-            st_sv = {"blocks": []}
-            if proj is not None:
-                M_in = B * ch * cw
-                xn, mean, rstd = o.ln_fwd(cur, proj.ln.weight, proj.ln.bias, M_in, cc)
-                ch, cw = ch // 2, cw // 2
-                nxt = torch.empty((B * ch * cw, proj.cout), dtype=dt, device=x.device)
-                o.gemm("nt", xn, proj.W, nxt, B * ch * cw, proj.cout, 4 * cc, cc, 4 * cc, proj.cout, dtype=dt,
-                       a_mode=L.A_PATCH2, gh=ch, gw=cw, cs=cc, epi=L.EPI_BIAS, bias=proj.conv.bias)
-                st_sv["proj"] = (cur, xn, mean, rstd)
-                cur, cc = nxt, proj.cout
-            rows = None
-            if masks is not None:
-                rows = masks[i]
-                # first block of the stage: `x *= unmasked` (fcmae.py:216-217); later blocks receive masked maps already
-                cur = o.rows_select(cur, rows[2], B * ch * cw, cc)
-            for bw in blocks:
-                cur = self._block_fwd(cur, bw, B, ch, cw, dt, st_sv["blocks"] if need_bwd else None, rows)
-            feats.append((cur, ch, cw, cc))
-            enc_sv.append(st_sv)
-        if cfg.get("head") == "embed":
-            out = self._embed_tail_fwd(feats[3], B, sv, bn_groups)
-            if need_bwd:
-                sv["enc"] = enc_sv
-                sv["feat_dims"] = [(a, b_, c) for (_, a, b_, c) in feats]
-            self._za_need[za_key] = za.used
-            return out, sv
-        # ---- decoder
-        dec_sv = []
-        feat, fh, fw, fc = feats[3]
-        for k, (proj, blocks) in enumerate(W["dec"]):
-            skip, sh, sw_, sc = feats[2 - k]
-            assert sh == 2 * fh and sw_ == 2 * fw
-            c_up = fc // 4
-            pre = W["dec_pre"][k]
-            low_in = None
-            if pre is not None:  # MONAI SubpixelUpsample conv_block: dense 3x3 convolution at the low resolution
-                pc, Wp, _ = pre
-                col = o.im2col3x3(feat, B, fh, fw, fc)
-                low_in = feat
-                feat = torch.empty((B * fh * fw, fc), dtype=dt, device=x.device)
-                o.gemm("nt", col, Wp, feat, B * fh * fw, fc, 9 * fc, 9 * fc, 9 * fc, fc, dtype=dt, epi=L.EPI_BIAS, bias=pc.bias)
-                del col
-            cat = o.pixel_shuffle_cat_fwd(feat, skip, B, fh, fw, c_up, sc)
-            fh, fw = sh, sw_
-            Mk, ccat = B * fh * fw, c_up + sc
-            if proj.cout < 16:  # narrow stage (2x2 stem: C = 4 or 8): LayerNorm + 1x1 projection in one pass, xn not stored
-                cur, mean, rstd = o.narrow_proj_fwd(cat, proj.ln.weight, proj.ln.bias, proj.conv.weight, proj.conv.bias, Mk, ccat,
-                                                    proj.cout)
-                xn = None
-            else:
-                xn, mean, rstd = o.ln_fwd(cat, proj.ln.weight, proj.ln.bias, Mk, ccat)
-                cur = torch.empty((Mk, proj.cout), dtype=dt, device=x.device)
-                o.gemm("nt", xn, proj.W, cur, Mk, proj.cout, ccat, ccat, ccat, proj.cout, dtype=dt, epi=L.EPI_BIAS,
-                       bias=proj.conv.bias)
-            st_sv = {"proj": (cat, xn, mean, rstd, c_up, sc), "blocks": [], "pre_in": low_in}
-            for bw in blocks:
-                cur = self._block_fwd(cur, bw, B, fh, fw, dt, st_sv["blocks"] if need_bwd else None)
-            feat, fc = cur, proj.cout
-            dec_sv.append(st_sv)
-        # ---- head
-        if cfg.get("head", "conv") == "shuffle":
-            # PixelToVoxelShuffleHead (heads.py:656-685): pixel shuffle x s + pad-pool + reshape, parameter free
-            sxy = cfg["stem_kernel"][-1]
-            out = o.voxel_shuffle_fwd(feat, B, fh, fw, cfg["out_channels"], cfg["out_stack_depth"], sxy, True)
-            if need_bwd:
-                sv["enc"], sv["dec"] = enc_sv, dec_sv
-                sv["feat_dims"] = [(a, b_, c) for (_, a, b_, c) in feats]
-                sv["head"] = (fh, fw)
-            self._za_need[za_key] = za.used
-            return out, sv
-        Zo, D7 = cfg["out_stack_depth"], cfg["out_stack_depth"] + 2
-        hc = m.head.conv[0].conv
-        cmid, c3 = hc.weight.shape[0], hc.weight.shape[1]
-        cout = cfg["out_channels"]
-        hdt = self._head_dtype(dt)
-        hin = o.head_shuffle_fwd(feat if hdt == dt else feat.float(), B, fh, fw, c3, D7, cfg["head_pool"])
-        H2, W2 = 2 * fh, 2 * fw
-        Mh = B * H2 * W2
-        stats = self._za.take(2, B, cmid)
-        direct = o.head_conv_supported(H2, W2, c3, cmid, Zo, hdt)
-        if direct:
-            U = o.head_conv_fwd(hin, W["head_Wc"], hc.bias, stats[0], stats[1], B, H2, W2, c3, cmid, Zo)
+            xn, mean, rstd = o.ln_fwd(cat, proj.ln.weight, proj.ln.bias, Mk, ccat)
+            cur = torch.empty((Mk, proj.cout), dtype=dt, device=feat.device)
+            o.gemm("nt", xn, proj.W, cur, Mk, proj.cout, ccat, ccat, ccat, proj.cout, dtype=dt, epi=L.EPI_BIAS,
+                   bias=proj.conv.bias)
+        st_sv["proj"] = _UpSaved(cat, xn, mean, rstd, c_up, sc, None if pre is None else feat)
+        return cur
+
+    def _up_bwd(self, d, proj, s, B, sh, sw_, dt):
+        """-> (gradient of the low map in front of the shuffle, gradient of the skip)"""
+        o, g, Mk, ccat = self.ops, self.g, B * sh * sw_, s.c_up + s.sc
+        if proj.cout < 16:
+            dxn = o.narrow_proj_bwd(d, s.cat, s.mean, s.rstd, proj.ln.weight, proj.ln.bias, proj.conv.weight, g(proj.conv.weight),
+                                    g(proj.conv.bias), Mk, ccat, proj.cout)
         else:
-            U = torch.empty((Mh, Zo * cmid), dtype=hdt, device=x.device)
-            o.gemm_z("nt", hin, W["head_Wc"], U, Mh, cmid, 27 * c3, D7 * c3, 27 * c3, Zo * cmid, dtype=hdt,
-                     a_mode=L.A_CONV3, gh=H2, gw=W2, cs=3 * c3, nz=Zo, a_coff=[z * c3 for z in range(Zo)],
-                     b_off=[0] * Zo, c_coff=[z * cmid for z in range(Zo)], epi=L.EPI_BIAS_STATS, bias=hc.bias,
-                     red0=stats[0], red1=stats[1], hw=H2 * W2)
-        w2 = m.head.conv[1].weight.view(4 * cout, cmid)
-        out = o.head_out_fwd(U, stats[0], stats[1], w2, m.head.conv[1].bias, m.head.conv[0].adn.A.weight, B, H2, W2, Zo,
-                             cmid, cout)
-        if need_bwd:
-            sv["enc"], sv["dec"] = enc_sv, dec_sv
-            sv["feat_dims"] = [(a, b_, c) for (_, a, b_, c) in feats]
-            sv["head"] = (hin, U, stats, fh, fw)
-        self._za_need[za_key] = za.used
-        return out, sv
+            dxn = self._dense_bwd(s.xn, d, proj.WT, g(proj.conv.weight), g(proj.conv.bias), Mk, proj.cout, ccat, dt)
+        dcat = o.ln_bwd(dxn, s.cat, s.mean, s.rstd, proj.ln.weight, None, g(proj.ln.weight), g(proj.ln.bias), Mk, ccat)
+        del dxn
+        return o.pixel_shuffle_cat_bwd(dcat, B, sh // 2, sw_ // 2, s.c_up, s.sc)
 
     # ------------------------------------------------------------------ ContrastiveEncoder tail (contrastive/encoder.py:93-154)
     def _bn_groups_fwd(self, z, bn, training, relu, groups):
@@ -794,15 +742,25 @@ class Engine(FlatEngine):
                          g(bn.weight), g(bn.bias), training, relu) for gi in range(groups)]
         return dx[0] if groups == 1 else torch.cat(dx)
 
-    def _embed_tail_fwd(self, feat3, B, sv, bn_groups: int = 1):
+    def _embed_tail_params(self):
+        t = self.model.tail
+        return [t.bn4.weight, t.bn4.bias, t.fc3.weight, t.fc3.bias, t.bn1.weight, t.bn1.bias, t.fc0.weight, t.fc0.bias,
+                t.norm.weight, t.norm.bias]
+
+    def _embed_tail_prep(self, W, dt, need_bwd):
+        o, t = self.ops, self.model.tail
+        (E, Cf), P = t.fc0.weight.shape, t.fc3.weight.shape[0]
+        W["fc0"], W["fc0T"] = o.prep_weight(t.fc0.weight, E, Cf, 1, torch.float32, want=True, want_t=need_bwd)
+        W["fc3"], W["fc3T"] = o.prep_weight(t.fc3.weight, P, E, 1, torch.float32, want=True, want_t=need_bwd)
+
+    def _embed_tail_fwd(self, feat3, B, dt, sv, bn_groups: int = 1):
         """global average pool -> LayerNorm (timm head.norm) = embedding; Linear -> BN -> ReLU -> Linear -> BN = projection.
         fp32 throughout ([B, 768]-sized tensors); BatchNorm statistics are those of THIS call's batch (the reference runs
         anchor and positive through separate forwards, dynaclr/engine.py:265-266); ``bn_groups = 2`` gives a concatenated
         [anchor; positive] batch exactly those per-call statistics while the trunk runs once."""
         o, m, W = self.ops, self.model, self.W
         feat, fh, fw, fc = feat3
-        t = m.tail
-        training = bool(m.training)
+        t, training = m.tail, bool(m.training)
         pooled = o.avgpool_rows_fwd(feat, B, fh * fw, fc)
         emb, mean, rstd = o.ln_fwd(pooled, t.norm.weight, t.norm.bias, B, fc)
         E, P = t.fc0.weight.shape[0], t.fc3.weight.shape[0]
@@ -818,44 +776,73 @@ class Engine(FlatEngine):
             t.bn1.num_batches_tracked += bn_groups
             t.bn4.num_batches_tracked += bn_groups
         if sv is not None:
-            sv["tail"] = (pooled, mean, rstd, emb, z0, y1, sm1, sr1, z3, y4, sm4, sr4, training, fh, fw, fc)
+            sv["head"] = _EmbedSaved(pooled, mean, rstd, emb, z0, y1, sm1, sr1, z3, y4, sm4, sr4, training, fh, fw, fc)
         return emb, y4
 
-    def _embed_tail_bwd(self, sv, demb, dproj, dt, B):
-        o, m, W, g = self.ops, self.model, sv["W"], self.g
-        pooled, mean, rstd, emb, z0, y1, sm1, sr1, z3, y4, sm4, sr4, training, fh, fw, fc = sv["tail"]
-        t = m.tail
-        E, P = t.fc0.weight.shape[0], t.fc3.weight.shape[0]
-        dev = emb.device
+    def _embed_tail_bwd(self, sv, dout, dt, B):
+        o, t, W, g, s = self.ops, self.model.tail, sv["W"], self.g, sv["head"]
+        E, P, fc, f32 = t.fc0.weight.shape[0], t.fc3.weight.shape[0], s.fc, torch.float32
+        demb, dproj = dout
         d_emb = demb.contiguous().float() if demb is not None else None
         if dproj is not None:
-            dz3 = self._bn_groups_bwd(dproj.contiguous().float(), z3, y4, t.bn4, sm4, sr4, training, False)
-            o.gemm("tn", y1, dz3, g(t.fc3.weight), B, P, E, E, P, E, dtype=torch.float32, colsum=g(t.fc3.bias))
-            dy1 = torch.empty((B, E), dtype=torch.float32, device=dev)
-            o.gemm("nt", dz3, W["fc3T"], dy1, B, E, P, P, P, E, dtype=torch.float32)
-            dz0 = self._bn_groups_bwd(dy1, z0, y1, t.bn1, sm1, sr1, training, True)
-            o.gemm("tn", emb, dz0, g(t.fc0.weight), B, E, fc, fc, E, fc, dtype=torch.float32, colsum=g(t.fc0.bias))
-            de = torch.empty((B, fc), dtype=torch.float32, device=dev)
-            o.gemm("nt", dz0, W["fc0T"], de, B, fc, E, E, E, fc, dtype=torch.float32)
+            dz3 = self._bn_groups_bwd(dproj.contiguous().float(), s.z3, s.y4, t.bn4, s.sm4, s.sr4, s.training, False)
+            dy1 = self._dense_bwd(s.y1, dz3, W["fc3T"], g(t.fc3.weight), g(t.fc3.bias), B, P, E, f32)
+            dz0 = self._bn_groups_bwd(dy1, s.z0, s.y1, t.bn1, s.sm1, s.sr1, s.training, True)
+            de = self._dense_bwd(s.emb, dz0, W["fc0T"], g(t.fc0.weight), g(t.fc0.bias), B, E, fc, f32)
             d_emb = de if d_emb is None else d_emb + de
         if d_emb is None:
-            d_emb = torch.zeros((B, fc), dtype=torch.float32, device=dev)
-        dpooled = o.ln_bwd(d_emb, pooled, mean, rstd, t.norm.weight, None, g(t.norm.weight), g(t.norm.bias), B, fc)
-        return o.avgpool_rows_bwd(dpooled, B, fh * fw, fc, dt)
+            d_emb = torch.zeros((B, fc), dtype=f32, device=s.emb.device)
+        dpooled = o.ln_bwd(d_emb, s.pooled, s.mean, s.rstd, t.norm.weight, None, g(t.norm.weight), g(t.norm.bias), B, fc)
+        return o.avgpool_rows_bwd(dpooled, B, s.fh * s.fw, fc, dt)
 
-    def _head_conv_bwd(self, sv, dout, dt, B, dev):
+    # ------------------------------------------------------------------ PixelToVoxelHead ("conv") and the shuffle head
+    def _head_conv_dims(self):
+        cfg, hc = self.cfg, self.model.head.conv[0].conv
+        return hc, hc.weight.shape[0], hc.weight.shape[1], cfg["out_channels"], cfg["out_stack_depth"], cfg["out_stack_depth"] + 2
+
+    def _head_conv_params(self):
+        hd = self.model.head.conv
+        return [hd[1].weight, hd[1].bias, hd[0].adn.A.weight, hd[0].conv.weight, hd[0].conv.bias]
+
+    def _head_conv_prep(self, W, dt, need_bwd):
+        o, hdt, (hc, cmid, c3, _, Zo, _) = self.ops, self._head_dtype(dt), self._head_conv_dims()
+        W["head_Wc"], _ = o.prep_weight(hc.weight, cmid, c3, 27, hdt, tapmode=1)
+        if need_bwd:
+            if hdt == torch.bfloat16 and c3 == 8 and cmid == 32 and Zo == 5:
+                o.flush()  # reads head_Wc
+                W["head_Wp"] = o.head_conv_dgrad_prep(W["head_Wc"])  # direct LDS-tiled dgrad (csrc/headconv.hip)
+            W["head_Wd"] = o.prep_head_dgrad(hc.weight, cmid, c3, Zo, hdt)
+
+    def _head_conv_fwd(self, feat3, B, dt, sv, bn_groups=1):
+        o, m, W, hdt, (feat, fh, fw, _) = self.ops, self.model, self.W, self._head_dtype(dt), feat3
+        hc, cmid, c3, cout, Zo, D7 = self._head_conv_dims()
+        hin = o.head_shuffle_fwd(feat if hdt == dt else feat.float(), B, fh, fw, c3, D7, self.cfg["head_pool"])
+        H2, W2, Mh = 2 * fh, 2 * fw, B * 4 * fh * fw
+        stats = self._za.take(2, B, cmid)
+        if o.head_conv_supported(H2, W2, c3, cmid, Zo, hdt):
+            U = o.head_conv_fwd(hin, W["head_Wc"], hc.bias, stats[0], stats[1], B, H2, W2, c3, cmid, Zo)
+        else:
+            U = torch.empty((Mh, Zo * cmid), dtype=hdt, device=feat.device)
+            o.gemm_z("nt", hin, W["head_Wc"], U, Mh, cmid, 27 * c3, D7 * c3, 27 * c3, Zo * cmid, dtype=hdt,
+                     a_mode=L.A_CONV3, gh=H2, gw=W2, cs=3 * c3, nz=Zo, a_coff=[z * c3 for z in range(Zo)],
+                     b_off=[0] * Zo, c_coff=[z * cmid for z in range(Zo)], epi=L.EPI_BIAS_STATS, bias=hc.bias,
+                     red0=stats[0], red1=stats[1], hw=H2 * W2)
+        w2 = m.head.conv[1].weight.view(4 * cout, cmid)
+        out = o.head_out_fwd(U, stats[0], stats[1], w2, m.head.conv[1].bias, m.head.conv[0].adn.A.weight, B, H2, W2, Zo,
+                             cmid, cout)
+        if sv is not None:
+            sv["head"] = _HeadConvSaved(hin, U, stats, fh, fw)
+        return out
+
+    def _head_conv_bwd(self, sv, dout, dt, B):
         """PixelToVoxelHead backward; returns the gradient of the decoder feature map."""
         o, cfg, m, g, W = self.ops, self.cfg, self.model, self.g, sv["W"]
-        Zo, D7 = cfg["out_stack_depth"], cfg["out_stack_depth"] + 2
-        hc = m.head.conv[0].conv
-        cmid, c3 = hc.weight.shape[0], hc.weight.shape[1]
-        cout = cfg["out_channels"]
+        hc, cmid, c3, cout, Zo, D7 = self._head_conv_dims()
+        trunk_dt, dt, dev = dt, self._head_dtype(dt), self.device
         hin, U, stats, fh, fw = sv["head"]
-        H2, W2 = 2 * fh, 2 * fw
-        Mh = B * H2 * W2
+        H2, W2, Mh = 2 * fh, 2 * fw, B * 4 * fh * fw
         alpha = m.head.conv[0].adn.A.weight
         w2 = m.head.conv[1].weight.view(4 * cout, cmid)
-        # ---- head
         S = self._za.take(2, B, cmid)
         if dt == torch.bfloat16 and (cmid, cout) in ((32, 2), (64, 4)):
             # pass 1 with the 1x1x1 weight gradient folded in (voxel contraction on MFMA inside the kernel): the
@@ -890,7 +877,96 @@ class Engine(FlatEngine):
         del dU
         d = o.head_shuffle_bwd(dhin, B, fh, fw, c3, D7, cfg["head_pool"])
         del dhin
-        return d
+        return d if dt == trunk_dt else d.to(trunk_dt)
+
+    def _head_shuffle_fwd(self, feat3, B, dt, sv, bn_groups=1):
+        """PixelToVoxelShuffleHead (heads.py:656-685): pixel shuffle x s + pad-pool + reshape, parameter free"""
+        cfg, (feat, fh, fw, _) = self.cfg, feat3
+        out = self.ops.voxel_shuffle_fwd(feat, B, fh, fw, cfg["out_channels"], cfg["out_stack_depth"], cfg["stem_kernel"][-1], True)
+        if sv is not None:
+            sv["head"] = _HeadShuffleSaved(fh, fw)
+        return out
+
+    def _head_shuffle_bwd(self, sv, dout, dt, B):
+        o, cfg, s, sxy = self.ops, self.cfg, sv["head"], self.cfg["stem_kernel"][-1]
+        vs = o.voxel_shuffle_bwd
+        if (cfg["out_channels"] * cfg["out_stack_depth"] * sxy * sxy) % (8 if dt == torch.bfloat16 else 4):
+            vs = o.narrow_voxel_shuffle_bwd  # fewer channels than a 16-byte vector (2x2 pre-training head: 4)
+        return vs(dout.contiguous().float(), B, s.fh, s.fw, cfg["out_channels"], cfg["out_stack_depth"], sxy, True, dt)
+
+    # head kind -> (parameters in backward order, prepare(W, dt, need_bwd), forward(feat3, B, dt, sv, bn_groups), backward)
+    _HEADS = {"conv": (_head_conv_params, _head_conv_prep, _head_conv_fwd, _head_conv_bwd),
+              "shuffle": (lambda self: [], lambda self, W, dt, need_bwd: None, _head_shuffle_fwd, _head_shuffle_bwd),
+              "embed": (_embed_tail_params, _embed_tail_prep, _embed_tail_fwd, _embed_tail_bwd)}
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, x: Tensor, dt: torch.dtype, need_bwd: bool, masks=None, bn_groups: int = 1):
+        """A forward WITHOUT a backward behind it (predict / validation / `InferStep` captures) forms the per-sample GRN and
+        InstanceNorm sums in a fixed order (`ops.det_scope`: what the `det_reduce` flag does, for this thread only), as the
+        reference's CPU path is deterministic: with fp32 atomics the bf16 forward at 2048^2 differs by 7e-3 of the output maximum
+        from run to run, the fixed order costs 0.3 % of a pass (profiles/r05_det_reduce.txt; VERDICT r5).  Training forwards
+        keep the atomics unless the `det_reduce` flag is set by hand;
+        ``VSX_DET_INFER=0`` in the environment switches the automatic setting off."""
+        auto = (not need_bwd) and self._hip and os.environ.get("VSX_DET_INFER", "1") != "0"
+        with hip_ops.det_scope(auto):  # per thread: the process-wide flag is left alone
+            return self._forward(x, dt, need_bwd, masks, bn_groups)
+
+    def _forward(self, x: Tensor, dt: torch.dtype, need_bwd: bool, masks=None, bn_groups: int = 1):
+        """``masks``: None (dense) or, per encoder stage, ``(idx, inv, keep, L)`` int32 row maps of the FCMAE mask at that
+        stage's resolution (see ``viscy_amd.fcmae.stage_row_maps``)."""
+        o, cfg = self.ops, self.cfg
+        # read once: prepare() packs the weight images and every block of this forward plans its schedule from this value
+        self._mlp_flag = L.lib().vsx_get_flag(b"mlp_fused") if self._hip else 0
+        W = self.prepare(dt, need_bwd, self._mlp_flag)
+        B, Cin, Z, H, Wd = x.shape
+        za_key = ("fwd", B, H, Wd, masks is not None)
+        self._za = za = _ZeroArena(x.device, self._za_need.get(za_key, 0), o)
+        # FCMAE 2-D branch (fcmae.py:369-370): the reference runs conv2d whenever x.shape[2] == 1, whatever in_stack_depth is —
+        # a 2-D FCMAE (in_stack_depth = 1) trains and loads its conv2d weights, never the conv3d ones (ADVICE r2)
+        flat_stem = Z == 1 and "stem2d_W" in W
+        if Cin != cfg["in_channels"] or (Z != cfg["in_stack_depth"] and not flat_stem):
+            raise ValueError(f"expected input (B,{cfg['in_channels']},{cfg['in_stack_depth']},Y,X), got {tuple(x.shape)}")
+        _, ky, kx = cfg["stem_kernel"]
+        if H % (8 * ky) or Wd % (8 * kx):
+            raise ValueError(f"Y and X must be divisible by {8 * ky} (got {H}x{Wd}); VSUNet pads to a multiple of 64")
+        # the prepared operands travel with the forward that used them: a later (no_grad / other dtype) forward re-prepares
+        # self.W, and the backward of THIS forward must still see its own transposed weights (ADVICE r1)
+        sv = {"shape": (B, H, Wd), "dt": dt, "masked": masks is not None, "W": W} if need_bwd else None
+        if need_bwd:
+            self._count_forward()
+        cur = self._stem_fwd(x, W, flat_stem, dt, sv)
+        # ---- encoder
+        feats, enc_sv, dec_sv = [], [], []
+        ch, cw = H // ky, Wd // kx
+        for i, (proj, blocks) in enumerate(W["enc"]):
+            st_sv = {"blocks": []}
+            if proj is not None:
+                ch, cw = ch // 2, cw // 2
+                cur = self._down_fwd(cur, proj, B, ch, cw, dt, st_sv)
+            rows = None
+            if masks is not None:
+                rows = masks[i]
+                # first block of the stage: `x *= unmasked` (fcmae.py:216-217); later blocks receive masked maps already
+                cur = o.rows_select(cur, rows[2], B * ch * cw, cur.shape[1])
+            for bw in blocks:
+                cur = self._block_fwd(cur, bw, B, ch, cw, dt, st_sv["blocks"] if need_bwd else None, rows)
+            feats.append((cur, ch, cw, cur.shape[1]))
+            enc_sv.append(st_sv)
+        # ---- decoder (none in front of the embedding tail), then the head
+        feat, fh, fw, fc = feats[3]
+        for k, (proj, blocks) in enumerate(W["dec"]):
+            st_sv = {"blocks": []}
+            cur = self._up_fwd(feat, feats[2 - k], W["dec_pre"][k], proj, B, fh, fw, fc, dt, st_sv)
+            fh, fw = 2 * fh, 2 * fw
+            for bw in blocks:
+                cur = self._block_fwd(cur, bw, B, fh, fw, dt, st_sv["blocks"] if need_bwd else None)
+            feat, fc = cur, proj.cout
+            dec_sv.append(st_sv)
+        out = self._HEADS[self.head][2](self, (feat, fh, fw, fc), B, dt, sv, bn_groups)
+        if need_bwd:
+            sv.update(enc=enc_sv, dec=dec_sv, feat_dims=[(a, b_, c) for (_, a, b_, c) in feats])
+        self._za_need[za_key] = za.used
+        return out, sv
 
     # ------------------------------------------------------------------ backward
     def backward_stages(self, sv, dout: Tensor):
@@ -902,62 +978,20 @@ class Engine(FlatEngine):
         # that only touch weight-sized data) are collected and launched as task lists when the segment ends (ops.batch_open)
         self.ops.batch_open()
         try:
-            o, cfg, m, g, W = self.ops, self.cfg, self.model, self.g, sv["W"]
-            dt = sv["dt"]
-            B, H, Wd = sv["shape"]
-            dev = self.device
+            W, dt, (B, H, Wd) = sv["W"], sv["dt"], sv["shape"]
             za_key = ("bwd", B, H, Wd, sv["masked"])
-            self._za = za = _ZeroArena(dev, self._za_need.get(za_key, 0), self.ops)
-            if cfg.get("head") == "embed":
-                d = self._embed_tail_bwd(sv, dout[0], dout[1], dt, B)
-            elif cfg.get("head", "conv") == "shuffle":
-                fh, fw = sv["head"]
-                sxy = cfg["stem_kernel"][-1]
-                vs = o.voxel_shuffle_bwd
-                if (cfg["out_channels"] * cfg["out_stack_depth"] * sxy * sxy) % (8 if dt == torch.bfloat16 else 4):
-                    vs = o.narrow_voxel_shuffle_bwd  # fewer channels than a 16-byte vector (2x2 pre-training head: 4)
-                d = vs(dout.contiguous().float(), B, fh, fw, cfg["out_channels"], cfg["out_stack_depth"], sxy, True, dt)
-            else:
-                hdt = self._head_dtype(dt)
-                d = self._head_conv_bwd(sv, dout, hdt, B, dev)
-                if hdt != dt:
-                    d = d.to(dt)
+            self._za = za = _ZeroArena(self.device, self._za_need.get(za_key, 0), self.ops)
+            d = self._HEADS[self.head][3](self, sv, dout, dt, B)
             # ---- decoder (reverse)
             dskips = {}
-            for k in (2, 1, 0) if cfg.get("head") != "embed" else ():
-                proj, blocks = W["dec"][k]
-                st_sv = sv["dec"][k]
-                cat, xn, mean, rstd, c_up, sc = st_sv["proj"]
-                _, sh, sw_, _ = (None, *sv["feat_dims"][2 - k])
-                Mk, ccat = B * sh * sw_, c_up + sc
+            for k in reversed(range(len(W["dec"]))):
+                (proj, blocks), st_sv, pre = W["dec"][k], sv["dec"][k], W["dec_pre"][k]
+                sh, sw_, _ = sv["feat_dims"][2 - k]
                 for bw, bsv in zip(reversed(blocks), reversed(st_sv["blocks"])):
                     d = self._block_bwd(d, bw, bsv, B, sh, sw_, dt)
-                if proj.cout < 16:
-                    dxn = o.narrow_proj_bwd(d, cat, mean, rstd, proj.ln.weight, proj.ln.bias, proj.conv.weight, g(proj.conv.weight),
-                                            g(proj.conv.bias), Mk, ccat, proj.cout)
-                else:
-                    o.gemm("tn", xn, d, g(proj.conv.weight), Mk, proj.cout, ccat, ccat, proj.cout, ccat, dtype=dt,
-                           colsum=g(proj.conv.bias))
-                    dxn = torch.empty((Mk, ccat), dtype=dt, device=dev)
-                    o.gemm("nt", d, proj.WT, dxn, Mk, ccat, proj.cout, proj.cout, proj.cout, ccat, dtype=dt)
-                dcat = o.ln_bwd(dxn, cat, mean, rstd, proj.ln.weight, None, g(proj.ln.weight), g(proj.ln.bias), Mk, ccat)
-                del dxn
-                d, dskips[2 - k] = o.pixel_shuffle_cat_bwd(dcat, B, sh // 2, sw_ // 2, c_up, sc)
-                del dcat
-                pre = W["dec_pre"][k]
-                if pre is not None:  # pre-convolution: weight gradient from the re-gathered patch matrix, data gradient through its transpose
-                    pc, _, WpT = pre
-                    lh, lw, cpc = sh // 2, sw_ // 2, 4 * c_up
-                    Ml = B * lh * lw
-                    col = o.im2col3x3(st_sv["pre_in"], B, lh, lw, cpc)
-                    dWp = self._za.take(cpc, 9 * cpc)
-                    o.gemm("tn", col, d, dWp, Ml, cpc, 9 * cpc, 9 * cpc, cpc, 9 * cpc, dtype=dt, colsum=g(pc.bias))
-                    o.unprep_grad(dWp, g(pc.weight), cpc, cpc, 9)
-                    del col
-                    dcol = torch.empty((Ml, 9 * cpc), dtype=dt, device=dev)
-                    o.gemm("nt", d, WpT, dcol, Ml, 9 * cpc, cpc, cpc, cpc, 9 * cpc, dtype=dt)
-                    d = o.col2im3x3(dcol, B, lh, lw, cpc)
-                    del dcol
+                d, dskips[2 - k] = self._up_bwd(d, proj, st_sv["proj"], B, sh, sw_, dt)
+                if pre is not None:
+                    d = self._preconv_bwd(d, pre, st_sv["proj"].pre_in, B, sh // 2, sw_ // 2, dt)
             yield from self._segment_end(0)
             if self.encoder_frozen():  # nothing below the decoder needs a gradient: skip ~40 % of the backward
                 self._za_need[za_key] = za.used
@@ -966,51 +1000,15 @@ class Engine(FlatEngine):
                 return
             # ---- encoder (reverse); d = gradient w.r.t. feats[3]
             for i in (3, 2, 1, 0):
-                proj, blocks = W["enc"][i]
-                st_sv = sv["enc"][i]
-                ch, cw, cc = sv["feat_dims"][i]
+                (proj, blocks), st_sv = W["enc"][i], sv["enc"][i]
+                ch, cw, _ = sv["feat_dims"][i]
                 for bw, bsv in zip(reversed(blocks), reversed(st_sv["blocks"])):
                     d = self._block_bwd(d, bw, bsv, B, ch, cw, dt)
                 if proj is not None:
-                    prev, xn, mean, rstd = st_sv["proj"]
-                    cin = proj.cin
-                    Mo = B * ch * cw
-                    dWg = self._za.take(proj.cout, 4 * cin)
-                    o.gemm("tn", xn, d, dWg, Mo, proj.cout, 4 * cin, cin, proj.cout, 4 * cin, dtype=dt, a_mode=L.A_PATCH2,
-                           gh=ch, gw=cw, cs=cin, colsum=g(proj.conv.bias))
-                    o.unprep_grad(dWg, g(proj.conv.weight), proj.cout, cin, 4)
-                    dxn = torch.empty((B * 4 * ch * cw, cin), dtype=dt, device=dev)
-                    o.gemm("nt", d, proj.WT, dxn, Mo, 4 * cin, proj.cout, proj.cout, proj.cout, cin, dtype=dt,
-                           c_mode=L.A_PATCH2, c_cs=cin, gh=ch, gw=cw)
-                    d = o.ln_bwd(dxn, prev, mean, rstd, proj.ln.weight, dskips.get(i - 1), g(proj.ln.weight), g(proj.ln.bias),
-                                 B * 4 * ch * cw, cin)
-                    del dxn
+                    d = self._down_bwd(d, proj, st_sv["proj"], dskips.get(i - 1), B, ch, cw, dt)
                 if i == 2:
                     yield from self._segment_end(1)
-            # ---- stem_1 LayerNorm + stem projection
-            P, f, mean, rstd = sv["stem"]
-            ln1 = m.encoder_stages.stem_1
-            M0, C0, K0 = f.shape[0], f.shape[1], P.shape[1]
-            df = o.ln_bwd(d, f, mean, rstd, ln1.weight, None, g(ln1.weight), g(ln1.bias), M0, C0)
-            Dp = cfg["ratio"]
-            if sv.get("stem_narrow") is not None:  # patches recomputed from the stored stack (P is x here)
-                sc = m.stem2d if sv.get("flat_stem") else m.stem.conv
-                o.narrow_stem_wgrad(P, df, g(sc.weight), g(sc.bias), sv["stem_narrow"])
-            elif sv.get("flat_stem"):
-                Kw = m.stem2d.weight[0].numel()
-                o.gemm("tn", P, df, g(m.stem2d.weight), M0, C0, Kw, K0, C0, Kw, dtype=dt, colsum=g(m.stem2d.bias))
-            elif Dp == 1:
-                Kw = m.stem.conv.weight[0].numel()  # the patch matrix may carry zero-padded tail columns (lda = K0 >= Kw)
-                o.gemm("tn", P, df, g(m.stem.conv.weight), M0, C0, Kw, K0, C0, Kw, dtype=dt, colsum=g(m.stem.conv.bias))
-            else:
-                co3 = C0 // Dp
-                K = K0 // Dp
-                dWe = self._za.take(C0, K0)
-                dbe = self._za.take(C0)
-                o.gemm("tn", P, df, dWe, M0, C0, K0, K0, C0, K0, dtype=dt, colsum=dbe)
-                dWe = dWe.view(co3, Dp, Dp, K)
-                g(m.stem.conv.weight).add_(torch.stack([dWe[:, dd, dd] for dd in range(Dp)], 0).sum(0).view_as(m.stem.conv.weight))
-                g(m.stem.conv.bias).add_(dbe.view(co3, Dp).sum(1))
+            self._stem_bwd(d, sv["stem"], dt)  # stem_1 LayerNorm + stem projection
             self._za_need[za_key] = za.used
             yield from self._segment_end(2)
         finally:
