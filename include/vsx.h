@@ -965,6 +965,38 @@ int32_t vsx_cc_round(const uint64_t* adj, const uint8_t* core, int32_t* labels, 
 int32_t vsx_dbscan_finish(const uint64_t* adj, const uint8_t* core, const int32_t* labels, const int32_t* cid, int32_t N, int32_t* out,
     vsx_stream_t stream);
 
+/* Test stage (cytoland/engine.py:334-392, csrc/test_metrics.hip): the sums behind the regression metrics of VSUNet.test_step in one
+ * read of an image pair, and SSIM over the windows that lie inside the image.
+ * P, T: `planes` fp32 images of H rows x W columns each, element (pl, y, x) at pl * plane_stride + y * row_stride + x (strides in
+ *   elements, row_stride >= W is not required of the caller: any non-negative strides that stay inside the buffer), 4-byte aligned.
+ * pair_sums: out [VSX_PAIR_SUMS] float64 = { sum p, sum t, sum p^2, sum t^2, sum p t, sum |p - t|, sum (p - t)^2, min p, max p,
+ *   min t, max t, sum over rows of cos(row), rows }; a row is one line along X of one plane and
+ *   cos = p.t / (max(|p|, 1e-8) max(|t|, 1e-8)) (F.cosine_similarity(dim=-1)).  Every accumulator is float64.  A wave owns whole
+ *   rows (VSX_PAIR_SUMS_WAVES waves per workgroup, VSX_PAIR_SUMS_VEC elements per lane and load where both rows are 16-byte
+ *   aligned); at most VSX_PAIR_SUMS_MAX_WGS workgroups, a function of planes * H alone, write one partial each to ws
+ *   (vsx_pair_sums_ws_bytes) and one launch folds them in workgroup order.  No atomics: the same bits in every run.
+ * ssim_window: separable weights wy [Ky], wx [Kx] (device fp32; odd sizes in [3, VSX_SSIM_MAX_K], H >= Ky, W >= Kx), c = {c1, c2} and
+ *   shift = {s_p, s_t} device floats.  With x = p - s_p, y = t - s_t formed where a tile is staged and E the weighted window mean:
+ *     mx = E[x], my = E[y], vxx = max(E[x^2] - mx^2, 0), vyy = max(E[y^2] - my^2, 0), vxy = E[xy] - mx my, mp = mx + s_p, mt = my + s_t
+ *     ssim = ((2 mp mt + c1) (2 vxy + c2)) / ((mp^2 + mt^2 + c1) (vxx + vyy + c2))                                 (fp32)
+ *   for each of the (H - Ky + 1) x (W - Kx + 1) windows inside a plane: what torchmetrics' structural_similarity_index_measure
+ *   averages after it has cropped its reflect padding.  sums [planes] float64 = the sum of each plane's map (one partial per
+ *   VSX_SSIM_TILE x VSX_SSIM_TILE tile of outputs in ws, vsx_ssim_window_ws_bytes, folded in a fixed order, no atomics);
+ *   map: NULL, or [planes][H - Ky + 1][W - Kx + 1] fp32. */
+#define VSX_PAIR_SUMS 13
+#define VSX_PAIR_SUMS_WAVES 4
+#define VSX_PAIR_SUMS_VEC 4
+#define VSX_PAIR_SUMS_MAX_WGS 2048
+#define VSX_SSIM_MAX_K 33
+#define VSX_SSIM_TILE 32
+int64_t vsx_pair_sums_ws_bytes(int64_t planes, int32_t H);
+int32_t vsx_pair_sums(const float* P, int64_t p_plane_stride, int64_t p_row_stride, const float* T, int64_t t_plane_stride,
+    int64_t t_row_stride, int64_t planes, int32_t H, int32_t W, double* out, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int64_t vsx_ssim_window_ws_bytes(int64_t planes, int32_t H, int32_t W, int32_t Ky, int32_t Kx);
+int32_t vsx_ssim_window(const float* P, int64_t p_plane_stride, int64_t p_row_stride, const float* T, int64_t t_plane_stride,
+    int64_t t_row_stride, int64_t planes, int32_t H, int32_t W, const float* wy, int32_t Ky, const float* wx, int32_t Kx,
+    const float* c, const float* shift, double* sums, float* map, void* ws, int64_t ws_bytes, vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 
     python -m viscy_amd fit     --config finetune.yml [--config override.yml]
     python -m viscy_amd predict --config predict.yml
+    python -m viscy_amd test    --config test.yml          # prints the epoch means of the test metrics as one JSON line
 
 * ``load_composed_config`` — ``viscy_utils.compose.load_composed_config``
   (/root/reference/packages/viscy-utils/src/viscy_utils/compose.py:46-140): ``base:`` lists resolved recursively relative to
@@ -176,13 +177,17 @@ def build(cfg: dict):
     return module, datamodule, trainer, skipped
 
 
-def main(argv=None) -> int:
+def parser():
     import argparse
 
     ap = argparse.ArgumentParser(prog="python -m viscy_amd", description="run a cytoland / dynaclr YAML recipe on the MI355X classes")
-    ap.add_argument("subcommand", choices=["fit", "predict"])
+    ap.add_argument("subcommand", choices=["fit", "predict", "test"])
     ap.add_argument("--config", "-c", action="append", required=True, help="YAML file(s); later ones override earlier ones")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    args = parser().parse_args(argv)
     cfg: dict = {}
     for c in args.config:
         cfg = deep_merge(cfg, load_composed_config(c))
@@ -191,6 +196,10 @@ def main(argv=None) -> int:
         print(f"[viscy_amd] not instantiated (no counterpart in this build): {s}", file=sys.stderr)
     if args.subcommand == "fit":
         trainer.fit(module, datamodule)
+    elif args.subcommand == "test":
+        import json
+
+        print(json.dumps(trainer.test(module, datamodule)[0]), flush=True)
     else:
         trainer.predict(module, datamodule)
     return 0

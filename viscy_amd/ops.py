@@ -916,6 +916,41 @@ def voxel_shuffle_bwd(dout: Tensor, B: int, h: int, w: int, Cout: int, D: int, s
     return dfeat
 
 
+# ------------------------------------------------------------------ test stage (csrc/test_metrics.hip)
+def _planes_ws(dev, nbytes: int) -> Tensor:
+    """float64 per-workgroup partials of a test-stage launch, sized by the library, from the reduction scratch"""
+    if nbytes <= 0:
+        raise ValueError(f"test-stage workspace query answered {nbytes}: the shape is refused")
+    return _workspace(dev, (int(nbytes) + 3) // 4)
+
+
+def pair_sums(P: Tensor, p_strides: tuple[int, int], T: Tensor, t_strides: tuple[int, int], planes: int, H: int, W: int) -> Tensor:
+    """vsx_pair_sums on two runs of ``planes`` fp32 images starting at the tensors' first elements, (plane, row) strides in
+    elements -> [VSX_PAIR_SUMS] float64.  The tensors may be views: only their first address is taken."""
+    if not (P.is_cuda and T.is_cuda and P.dtype == T.dtype == torch.float32):
+        raise RuntimeError("viscy_amd.pair_sums takes float32 tensors on the HIP device (no CPU fallback)")
+    out = torch.empty(L.PAIR_SUMS, dtype=torch.float64, device=P.device)
+    ws = _planes_ws(P.device, lib().vsx_pair_sums_ws_bytes(planes, H))
+    check(lib().vsx_pair_sums(P.data_ptr(), p_strides[0], p_strides[1], T.data_ptr(), t_strides[0], t_strides[1], planes, H, W, ptr(out),
+                              ptr(ws), ws.numel() * 4, stream()), "pair_sums")
+    return out
+
+
+def ssim_window(P: Tensor, p_strides: tuple[int, int], T: Tensor, t_strides: tuple[int, int], planes: int, H: int, W: int, wy: Tensor,
+                wx: Tensor, c: Tensor, shift: Tensor, full: bool = False) -> tuple[Tensor, Tensor | None]:
+    """vsx_ssim_window -> (sums [planes] float64, the map [planes, H - Ky + 1, W - Kx + 1] fp32 or None); wy / wx / c / shift are
+    fp32 device tensors (taps, {c1, c2}, {s_p, s_t})"""
+    if not (P.is_cuda and T.is_cuda and P.dtype == T.dtype == torch.float32):
+        raise RuntimeError("viscy_amd.ssim_window takes float32 tensors on the HIP device (no CPU fallback)")
+    ky, kx = int(wy.numel()), int(wx.numel())
+    sums = torch.empty(planes, dtype=torch.float64, device=P.device)
+    fmap = torch.empty((planes, H - ky + 1, W - kx + 1), dtype=torch.float32, device=P.device) if full else None
+    ws = _planes_ws(P.device, lib().vsx_ssim_window_ws_bytes(planes, H, W, ky, kx))
+    check(lib().vsx_ssim_window(P.data_ptr(), p_strides[0], p_strides[1], T.data_ptr(), t_strides[0], t_strides[1], planes, H, W, ptr(wy), ky,
+                                ptr(wx), kx, ptr(c), ptr(shift), ptr(sums), ptr(fmap), ptr(ws), ws.numel() * 4, stream()), "ssim_window")
+    return sums, fmap
+
+
 # ------------------------------------------------------------------ narrow-channel family (csrc/narrow.hip): the 2x2-stem FCMAE
 def _narrow_ws(dev, op: int, B: int, n: int, C: int, K: int = 0) -> Tensor:
     """per-workgroup partials of a narrow launch, sized by the library"""

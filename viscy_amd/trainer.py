@@ -35,6 +35,7 @@ class Trainer:
         self.global_step = 0
         self.current_epoch, self.sanity_checking, self.global_rank, self.world_size = 0, False, 0, 1
         self.predicting = False        # Lightning's trainer.predicting: True inside predict() (TripletDataModule._find_transform)
+        self.testing = False           # Lightning's trainer.testing: True inside test()
         self.graph_step = graph_step   # False: always the eager zero_grad / training_step / backward / step loop
         self.graph_steps = 0           # optimisation steps taken through the captured TrainStep (tests, logs)
         self._train_steps: dict = {}   # batch signature -> TrainStep
@@ -224,6 +225,84 @@ class Trainer:
         sd = {k: v.detach().cpu().clone() for k, v in module.state_dict().items()}
         torch.save({"state_dict": sd, "epoch": self.max_epochs, "global_step": self.global_step}, path)
         return path
+
+    def _call_stage_hook(self, name: str, module) -> None:
+        """a hook of the test loop: on every callback that has it, then on the module (Lightning's order)"""
+        self._call_hook(name, module)
+        fn = getattr(module, name, None)
+        if fn is not None:
+            fn()
+
+    def test(self, module, datamodule) -> list[dict[str, float]]:
+        """Lightning's test loop as the reference uses it (``python -m cytoland test``): ``setup("test")``, ``eval`` under
+        ``no_grad``, ``on_test_start`` / ``on_test_epoch_start``, per batch ``on_after_batch_transfer`` and ``test_step``
+        (``on_test_batch_end`` on callbacks), ``on_test_epoch_end`` / ``on_test_end``.  Returns one dict (one test dataloader):
+        for every key the module logged with ``on_epoch=True`` (Lightning's default in a test step) the mean over the batches,
+        weighted by batch size; ``on_epoch=False`` keys (``position`` / ``time`` / ``slice``) stay in ``module.logged`` only.
+        The module's contract is the logging shim of ``VSUNet``: ``logged[key]`` grows by one value per ``log`` call and
+        ``logged_kw[key]`` holds the call's keywords.  The sums are kept on the device; the one host read is at the end."""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("Trainer.test runs in one process: the epoch means are not reduced across ranks "
+                                      f"(world size {dist.get_world_size()})")
+        module.to(self.device).eval()
+        module.trainer = self
+        self.datamodule = datamodule
+        datamodule.trainer = self
+        datamodule.setup("test")
+        use_bf16 = self.precision.startswith("bf16") and self.device.type == "cuda"
+        if not hasattr(module, "logged"):
+            module.logged = {}
+        logged = module.logged
+        totals: dict[str, list] = {}
+        self.testing = True
+        try:
+            # a forward without a backward forms its sums in a fixed order (Engine.forward) and so do the metric kernels: in the
+            # production precision (bf16) the same checkpoint on the same data gives the same numbers, bit for bit
+            with torch.no_grad():
+                self._call_stage_hook("on_test_start", module)
+                self._call_stage_hook("on_test_epoch_start", module)
+                for j, batch in enumerate(datamodule.test_dataloader()):
+                    batch = self._to_device(batch)
+                    if hasattr(datamodule, "on_after_batch_transfer"):
+                        was = getattr(datamodule, "training", False)
+                        datamodule.training = False
+                        batch = datamodule.on_after_batch_transfer(batch, 0)
+                        datamodule.training = was
+                    seen = {k: len(v) for k, v in logged.items()}
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_bf16):
+                        out = module.test_step(batch, j)
+                    size = self._batch_size(batch)
+                    kws = getattr(module, "logged_kw", {})
+                    for key, vals in logged.items():
+                        kw = kws.get(key, {})
+                        if not kw.get("on_epoch", True):
+                            continue
+                        weight = int(kw.get("batch_size") or size or 1)
+                        for v in vals[seen.get(key, 0):]:
+                            v = torch.as_tensor(v).detach().to(torch.float64)
+                            tot = totals.setdefault(key, [torch.zeros((), dtype=torch.float64, device=v.device), 0])
+                            tot[0] = tot[0] + v * weight
+                            tot[1] += weight
+                    self._call_hook("on_test_batch_end", module, out, batch, j, 0)
+                self._call_stage_hook("on_test_epoch_end", module)
+                self._call_stage_hook("on_test_end", module)
+        finally:
+            self.testing = False
+        return [{key: float(tot / max(n, 1)) for key, (tot, n) in totals.items()}]
+
+    @staticmethod
+    def _batch_size(batch) -> int:
+        """Lightning's extract_batch_size, as far as these batches need it: the leading extent of the first tensor found"""
+        if torch.is_tensor(batch):
+            return int(batch.shape[0]) if batch.ndim else 1
+        if isinstance(batch, dict):
+            batch = list(batch.values())
+        if isinstance(batch, (list, tuple)):
+            for v in batch:
+                n = Trainer._batch_size(v)
+                if n:
+                    return n
+        return 0
 
     def predict(self, module, datamodule) -> list[torch.Tensor]:
         """Lightning's predict loop as the reference uses it: ``on_predict_start`` hooks, ``predict_step`` per batch,

@@ -163,6 +163,7 @@ class VSUNet(_Base):
         self.predict_graph = False  # True: hipGraph-captured forward per window shape in predict (viscy_amd.step.InferStep)
         self._infer_step = None
         self.logged: dict[str, list[float]] = {}
+        self.logged_kw: dict[str, dict] = {}
         if ckpt_path is not None:
             self.load_state_dict(torch.load(ckpt_path, weights_only=True, map_location="cpu")["state_dict"])
 
@@ -178,6 +179,7 @@ class VSUNet(_Base):
                 torch.distributed.all_reduce(value, op=torch.distributed.ReduceOp.SUM)  # Lightning sync_dist: mean over ranks
                 value = value / torch.distributed.get_world_size()
             self.logged.setdefault(key, []).append(value)
+            self.logged_kw[key] = kw  # on_step / on_epoch / batch_size of the call: what Trainer.test forms its epoch means by
 
     def forward(self, x: Tensor) -> Tensor:
         return self.model(x)
@@ -212,24 +214,33 @@ class VSUNet(_Base):
         self._log(f"loss/val/{dataloader_idx}", loss, sync_dist=True, batch_size=batch["source"].shape[0])
 
     def test_step(self, batch, batch_idx: int):
-        """Test stage of the reference (engine.py:334-372): the centre Z slice of the first channel of prediction and target
-        is scored with MAE, MSE, cosine similarity (along X, averaged), Pearson r and R² over all pixels, logged per batch
-        as ``test_metrics/<name>`` together with ``position`` / ``time`` / ``slice`` of the first sample.  Not built: the
-        torchmetrics SSIM entry and the Cellpose segmentation metrics (third-party models, outside the hot path).  The
-        metric arithmetic is plain tensor code on the forward result (no kernel of the path)."""
+        """Test stage of the reference (engine.py:334-392): the centre Z slice of the first channel of prediction and target
+        is scored with MAE, MSE, cosine similarity (along X, averaged), Pearson r and R² over all pixels and with SSIM (uniform
+        21 x 21 window, data range from the pair), logged per batch as ``test_metrics/<name>`` together with ``position`` /
+        ``time`` / ``slice`` of the first sample.  On the HIP device the two centre-slice views are read in place by
+        ``viscy_amd.metrics``: one ``vsx_pair_sums`` launch gives the float64 sums behind the five regression metrics, the data
+        range and the two means that the ``vsx_ssim_window`` launch after it centres by; nothing in between waits for the host.
+        On a CPU tensor (the "2D" plumbing model) the five regression metrics are plain tensor arithmetic and no SSIM is
+        logged.  Not built: the Cellpose segmentation metrics (a third-party model, outside the hot path)."""
         target = batch["target"]
         zc = target.shape[-3] // 2
         t = target[:, 0, zc:zc + 1].float()
         p = self.forward(batch["source"])[:, 0, zc:zc + 1].float()
-        pf, tf = p.flatten(), t.flatten()
-        pc, tc = pf - pf.mean(), tf - tf.mean()
-        mets = {
-            "test_metrics/MAE": (pf - tf).abs().mean(),
-            "test_metrics/MSE": ((pf - tf) ** 2).mean(),
-            "test_metrics/cosine": torch.nn.functional.cosine_similarity(p, t, dim=-1).mean(),
-            "test_metrics/pearson": (pc * tc).sum() / (pc.norm() * tc.norm()).clamp_min(1e-20),
-            "test_metrics/r2": 1 - ((pf - tf) ** 2).sum() / (tc ** 2).sum().clamp_min(1e-20),
-        }
+        if p.is_cuda:
+            from . import metrics as M
+
+            mets = {f"test_metrics/{k}": v for k, v in M.regression_metrics(p, t).items()}
+            mets["test_metrics/SSIM"] = M.structural_similarity_index_measure(p, t, gaussian_kernel=False, kernel_size=21)
+        else:
+            pf, tf = p.flatten(), t.flatten()
+            pc, tc = pf - pf.mean(), tf - tf.mean()
+            mets = {
+                "test_metrics/MAE": (pf - tf).abs().mean(),
+                "test_metrics/MSE": ((pf - tf) ** 2).mean(),
+                "test_metrics/cosine": torch.nn.functional.cosine_similarity(p, t, dim=-1).mean(),
+                "test_metrics/pearson": (pc * tc).sum() / (pc.norm() * tc.norm()).clamp_min(1e-20),
+                "test_metrics/r2": 1 - ((pf - tf) ** 2).sum() / (tc ** 2).sum().clamp_min(1e-20),
+            }
         for k, v in mets.items():
             self._log(k, v, on_step=True, on_epoch=True)
         if "index" in batch:
