@@ -997,6 +997,49 @@ int32_t vsx_ssim_window(const float* P, int64_t p_plane_stride, int64_t p_row_st
     int64_t t_row_stride, int64_t planes, int32_t H, int32_t W, const float* wy, int32_t Ky, const float* wx, int32_t Kx,
     const float* c, const float* shift, double* sums, float* map, void* ws, int64_t ws_bytes, vsx_stream_t stream);
 
+/* The device passes of `viscy preprocess` (csrc/preprocess.hip; viscy_utils/meta_utils.py generate_normalization_metadata /
+ * generate_fg_masks, viscy_utils/mp_utils.py get_val_stats; host layer viscy_amd/preprocess.py).  A source plane set is [Z, H, W] of
+ * src_dtype (VSX_PG_F32 / U16 / I16 / U8) with ELEMENT strides z_stride >= 0 and y_stride >= W, x contiguous; it may be a view into a
+ * [T, C, Z, H, W] block, and the kernels trust the strides.  Integer sources convert to fp32 exactly, float32 is copied bit for bit.
+ * No floating-point atomics, no allocation, synchronisation or device-to-host copy; every output is a pure function of the inputs
+ * (and, for the moments, of x's 16-byte alignment), bit-identical from run to run.  Every check runs before any launch; anything
+ * not served is refused with a non-zero status.
+ * grid_sample: out [Z][ceil(H / g)][ceil(W / g)] fp32, out[z, i, j] = src[z, i g, j g]: numpy's `[:, ::g, ::g]`.  g >= 1; g > H gives one row.
+ * median3x3: the 3 x 3 median of every plane with scipy.ndimage's default mode="reflect" (d c b a | a b c d): what
+ *   median_filter(size=(1, 1, 3, 3)) and size=(1, 3, 3) compute; planes never mix; H or W of 1 and 2 repeat the rows there are.
+ *   Exactly one of out / mask is given: out [Z][H][W] fp32 (the source must be VSX_PG_F32), or mask [Z][H][W] uint8 = median >= thr ? 1 : 0
+ *   from a source of any dtype.  A wave walks down a strip of VSX_MEDIAN_COLS columns, VSX_MEDIAN_ROWS rows with three rows in
+ *   registers.  The input is ASSUMED NaN-free (scipy's result with a NaN is unspecified as well); of -0.0 / +0.0 either may come back.
+ * nan_moments: x [n] fp32, 4-byte aligned, 1 <= n <= 2^31 - 1; ws: vsx_nan_moments_ws_bytes(n) bytes, 8-byte aligned, no
+ *   initialisation needed (one partial of VSX_MOMENTS_PART_BYTES per chunk of VSX_MOMENTS_CHUNK values, plain stores, then ONE
+ *   fixed-order fold); out [4] float64 on the device.
+ *     pass 1: out = {count of non-NaN values, their min, max, sum}; no such value: {0, +inf, -inf, 0}.  integral = 1 (the values are
+ *             integers with |x| <= 65535: uint8 / uint16 / int16 stores): isums [2] int64 = {sum x, sum x^2}, exact, since
+ *             65535^2 (2^31 - 1) < 2^63.
+ *     pass 2: out = {sum (x - mean)^2, sum (x - mean), 0, 0} over the non-NaN values, x - mean formed in float64.
+ * hist_int: x [n] fp32 holding integers; counts [nbins] uint64, counts[v - lo] = how many x equal v; 1 <= nbins <= 65536.  A value
+ *   outside [lo, lo + nbins) (a NaN included) is not counted.  counts is zeroed by the call.  uint64 counts set no limit on n; private
+ *   32-bit LDS counters serve nbins <= VSX_HIST_LDS_BINS (a workgroup sees fewer than 2^32 values), global integer atomics beyond.
+ * hist_edges: edges [nbins + 1] ascending float64 on the device, 2 <= nbins <= VSX_HIST_EDGES_MAX_BINS; counts [nbins] uint64, zeroed by
+ *   the call: bin i counts edges[i] <= x < edges[i + 1], the last bin is closed on the right, anything else (a NaN included) is
+ *   dropped: np.histogram's rule.  A value is placed by an arithmetic guess and then walked to the bin the table defines, so the
+ *   counts are those of the edges whatever the guess rounds to. */
+#define VSX_MEDIAN_COLS 62
+#define VSX_MEDIAN_ROWS 32
+#define VSX_MOMENTS_CHUNK 8192
+#define VSX_MOMENTS_PART_BYTES 48
+#define VSX_HIST_LDS_BINS 8192
+#define VSX_HIST_EDGES_MAX_BINS 1024
+int32_t vsx_grid_sample(const void* src, int32_t src_dtype, int64_t z_stride, int64_t y_stride, int32_t Z, int32_t H, int32_t W,
+    int32_t g, float* out, vsx_stream_t stream);
+int32_t vsx_median3x3(const void* src, int32_t src_dtype, int64_t z_stride, int64_t y_stride, int32_t Z, int32_t H, int32_t W,
+    float* out, uint8_t* mask, float thr, vsx_stream_t stream);
+int64_t vsx_nan_moments_ws_bytes(int64_t n);
+int32_t vsx_nan_moments(const float* x, int64_t n, int32_t pass, int32_t integral, double mean, double* out, int64_t* isums,
+    void* ws, int64_t ws_bytes, vsx_stream_t stream);
+int32_t vsx_hist_int(const float* x, int64_t n, int32_t lo, int32_t nbins, uint64_t* counts, vsx_stream_t stream);
+int32_t vsx_hist_edges(const float* x, int64_t n, const double* edges, int32_t nbins, uint64_t* counts, vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
     python -m viscy_amd fit     --config finetune.yml [--config override.yml]
     python -m viscy_amd predict --config predict.yml
     python -m viscy_amd test    --config test.yml          # prints the epoch means of the test metrics as one JSON line
+    python -m viscy_amd preprocess --data_path plate.zarr [--channel_names ...] [--compute_otsu] [--compute_fg_masks]   # no recipe
 
 * ``load_composed_config`` — ``viscy_utils.compose.load_composed_config``
   (/root/reference/packages/viscy-utils/src/viscy_utils/compose.py:46-140): ``base:`` lists resolved recursively relative to
@@ -186,7 +187,42 @@ def parser():
     return ap
 
 
+def _flag(v: str) -> bool:
+    if v.lower() in ("true", "1", "yes"):
+        return True
+    if v.lower() in ("false", "0", "no"):
+        return False
+    raise ValueError(f"not a boolean: {v!r}")
+
+
+def preprocess_parser():
+    """``python -m viscy_amd preprocess``: the arguments of ``Trainer.preprocess`` (``viscy preprocess``), no recipe needed"""
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="python -m viscy_amd preprocess",
+                                 description="normalisation statistics, Otsu thresholds and foreground masks of an HCS OME-Zarr store")
+    ap.add_argument("--data_path", required=True)
+    ap.add_argument("--channel_names", nargs="+", default=["-1"], help="channel names; -1 (default): all")
+    ap.add_argument("--num_workers", type=int, default=1)
+    ap.add_argument("--block_size", type=int, default=32)
+    ap.add_argument("--compute_otsu", nargs="?", const=True, default=False, type=_flag)
+    ap.add_argument("--otsu_grid_spacing", type=int, default=8)
+    ap.add_argument("--compute_fg_masks", nargs="?", const=True, default=False, type=_flag)
+    ap.add_argument("--fg_mask_channels", nargs="+", default=None)
+    ap.add_argument("--fg_mask_key", default="fg_mask")
+    return ap
+
+
 def main(argv=None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if argv[:1] == ["preprocess"]:  # takes its arguments from the command line: fit / predict / test keep requiring --config
+        from .trainer import Trainer
+
+        kw = vars(preprocess_parser().parse_args(argv[1:]))
+        if kw["channel_names"] == ["-1"]:
+            kw["channel_names"] = -1
+        Trainer(seed=None).preprocess(**kw)
+        return 0
     args = parser().parse_args(argv)
     cfg: dict = {}
     for c in args.config:

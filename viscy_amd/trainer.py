@@ -304,6 +304,30 @@ class Trainer:
                     return n
         return 0
 
+    def preprocess(self, data_path, channel_names=-1, num_workers: int = 1, block_size: int = 32, compute_otsu: bool = False,
+                   otsu_grid_spacing: int = 8, compute_fg_masks: bool = False, fg_mask_channels=None, fg_mask_key: str = "fg_mask",
+                   model=None) -> None:
+        """``VisCyTrainer.preprocess`` (``viscy preprocess``): normalisation statistics of ``channel_names`` (-1: all) sampled every
+        ``block_size`` pixels, written into the store's ``.zattrs``; with ``compute_otsu`` the per-FOV Otsu thresholds, and with
+        ``compute_fg_masks`` the ``fg_mask_key`` arrays of ``fg_mask_channels`` (default: the channels above).  ``model`` is ignored.
+        ``compute_fg_masks`` without ``compute_otsu`` is refused before anything is computed (the reference computes the statistics
+        first and raises the same error after them)."""
+        from .data.ome_zarr import open_ome_zarr
+        from .preprocess import generate_fg_masks, generate_normalization_metadata
+
+        if model is not None:
+            print("[viscy_amd] Ignoring model configuration during preprocessing.")
+        if compute_fg_masks and not compute_otsu:
+            raise ValueError("compute_fg_masks requires compute_otsu=True")
+        names = open_ome_zarr(data_path, layout="hcs", mode="r").channel_names
+        channel_indices = [names.index(c) for c in channel_names] if channel_names != -1 else channel_names
+        resolved = [names[i] for i in channel_indices] if channel_names != -1 else list(names)
+        generate_normalization_metadata(zarr_dir=data_path, num_workers=num_workers, channel_ids=channel_indices, grid_spacing=block_size,
+                                        compute_otsu=compute_otsu, otsu_grid_spacing=otsu_grid_spacing)
+        if compute_fg_masks:
+            generate_fg_masks(zarr_dir=data_path, channel_names=fg_mask_channels if fg_mask_channels is not None else resolved,
+                              fg_mask_key=fg_mask_key)
+
     def predict(self, module, datamodule) -> list[torch.Tensor]:
         """Lightning's predict loop as the reference uses it: ``on_predict_start`` hooks, ``predict_step`` per batch,
         prediction-writer callbacks (``write_on_batch_end``) after every batch, ``on_predict_end``."""
