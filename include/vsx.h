@@ -711,6 +711,24 @@ int32_t vsx_crop_zreduce(const float* x, float* y, const int32_t* starts, const 
 int32_t vsx_patch_gather(const int64_t* desc, float* out, int32_t n, int32_t C, int32_t Z, int32_t Yp, int32_t Xp,
     int32_t src_dtype, vsx_stream_t stream);
 
+/* The multi-experiment DynaCLR feed (dynaclr/data/dataset.py `_slice_patch`: one tensorstore read and one host
+ * F.interpolate(mode="nearest-exact") per patch there): per-patch channel lists, per-patch native boxes and the resampling to
+ * one target size in one launch, out[p, c, z, y, x] = (float) frame_p[chan_p[c], zi_p[z], yi_p[y], xi_p[x]], fp32
+ * [n, C, Zt, Yt, Xt].  desc: n rows of VSX_PGS_DESC int64 on the device: {address of the frame's element [0, 0, 0, 0], element
+ * strides of c, z and y (x is contiguous), offsets (in ints) into idx of the patch's channel table (C entries), z table (Zt), y
+ * table (Yt) and x table (Xt)}.  idx: int32 on the device.  Table entries are ABSOLUTE positions in the patch's frame (the host
+ * has added the box origin); patches may share tables by naming the same offset, and may name different frames of different
+ * shapes.  A frame is a [Cf, Zf, H, W] block of src_dtype (a VSX_PG_* code), or a view into a larger one.  float32 sources are
+ * copied bit for bit, integer sources convert exactly.  Every load reads an element the tables name.  The kernel trusts the
+ * tables: the caller has checked every entry against the frame's shape (viscy_amd.ops.patch_gather_scaled does).  With arange
+ * tables the result is vsx_patch_gather's.  out 16-byte aligned; Xt <= VSX_PGS_MAX_XT (the x table is held in LDS).  The grid is
+ * capped at eight workgroups per compute unit; a workgroup's row groups take VSX_PGS_ROWS_PER_GROUP rows each per work unit. */
+#define VSX_PGS_DESC 8
+#define VSX_PGS_MAX_XT 16384
+#define VSX_PGS_ROWS_PER_GROUP 4
+int32_t vsx_patch_gather_scaled(const int64_t* desc, const int32_t* idx, float* out, int32_t n, int32_t C, int32_t Zt,
+    int32_t Yt, int32_t Xt, int32_t src_dtype, vsx_stream_t stream);
+
 /* K18 kornia warp_affine3d as used by BatchedRandAffined (viscy_transforms/_affine.py:33-47,358-393): trilinear (or
  * nearest) resampling; Minv[B][3][4] maps output-voxel to input-voxel coordinates (x, y, z order).
  * The kernel applies Minv as given; the caller folds kornia's align_corners convention into it (with align_corners=False — kornia's

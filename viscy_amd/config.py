@@ -42,6 +42,7 @@ CLASS_MAP = {
     "viscy_data.BatchedConcatDataModule": "viscy_amd.data.combined.BatchedConcatDataModule",
     "viscy_data.triplet.TripletDataModule": "viscy_amd.data.triplet.TripletDataModule",
     "viscy_data.TripletDataModule": "viscy_amd.data.triplet.TripletDataModule",
+    "dynaclr.data.datamodule.MultiExperimentDataModule": "viscy_amd.data.multi_experiment.MultiExperimentDataModule",
     "viscy_utils.callbacks.prediction_writer.HCSPredictionWriter": "viscy_amd.prediction_writer.HCSPredictionWriter",
     "viscy_utils.callbacks.HCSPredictionWriter": "viscy_amd.prediction_writer.HCSPredictionWriter",
     "viscy_utils.callbacks.OnlineEvalCallback": "viscy_amd.online_eval.OnlineEvalCallback",

@@ -11,8 +11,8 @@ Without a HIP device everything is cut on the host (``host_cut``), which is what
 Host table work (filtering, anchors, positives, negative draws) is pandas, call for call in the reference's order, so that a
 seeded run (``numpy.random.seed``) draws the same cells.
 
-Beyond the reference: ``device_cache_bytes``.  Not built here: ``MultiExperimentDataModule``, fusing
-``NormalizeSampled`` into the gather.
+Beyond the reference: ``device_cache_bytes``.  Not built here: fusing ``NormalizeSampled`` into the gather.
+``MultiExperimentDataModule`` sits on ``FrameCache`` in ``multi_experiment.py``.
 """
 
 from __future__ import annotations

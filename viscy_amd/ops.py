@@ -12,6 +12,7 @@ import os
 import threading
 from typing import Sequence
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -1685,4 +1686,91 @@ def patch_gather(frames: Sequence[Tensor], origins: Sequence[Sequence[int]], siz
     shape = (n, C, Z, yp, xp)
     out = torch.empty(shape, dtype=torch.float32, device=f0.device) if out is None else _typed(out, torch.float32, shape, "patch_gather: out")
     check(lib().vsx_patch_gather(ptr(dev_table), ptr(out), n, C, Z, yp, xp, PATCH_GATHER_DTYPES[f0.dtype], stream()), "patch_gather")
+    return out
+
+
+PGS_AXES = ("channel", "z", "y", "x")
+
+
+def patch_tables(frames: Sequence[Tensor], channels: Sequence, zs: Sequence, ys: Sequence, xs: Sequence) -> tuple[Tensor, Tensor, tuple]:
+    """The descriptor rows and the index tables of ``vsx_patch_gather_scaled`` as host tensors: int64 (n, PGS_DESC) and int32 (T,),
+    plus the output shape (n, C, Zt, Yt, Xt).  Frame ``i`` is a (Cf, Zf, H, W) tensor (any view whose last axis is contiguous;
+    frames of one launch share the dtype and the device, not the shape); ``channels[i]``, ``zs[i]``, ``ys[i]``, ``xs[i]`` are its
+    1-D integer tables of ABSOLUTE positions in that frame (arrays, rows of a 2-D array, tensors, lists).  A table OBJECT named
+    by several patches is stored once; objects are told apart by identity and held until the call returns.  Every
+    entry is checked against its frame: one outside raises ``ValueError`` naming the patch and the axis.  Host code."""
+    n = len(frames)
+    if n == 0 or not (len(channels) == len(zs) == len(ys) == len(xs) == n):
+        raise ValueError(f"patch_gather_scaled: {n} frames for {len(channels)} / {len(zs)} / {len(ys)} / {len(xs)} tables")
+    f0 = frames[0]
+    if f0.dtype not in PATCH_GATHER_DTYPES:
+        raise NotImplementedError(f"patch_gather_scaled: frames stored as {f0.dtype} are not built (float32, uint16, int16, uint8 are)")
+    segs, seg_of, seg = [], {}, np.empty((n, 4), dtype=np.int64)  # distinct tables, id -> position in segs, per patch and axis
+    held = []  # every object whose id() is a key: a temporary (a row of a 2-D array) must not hand its address to the next one
+    rows, dims, seen = np.empty((n, 4), dtype=np.int64), np.empty((n, 4), dtype=np.int64), {}
+    for i, f in enumerate(frames):
+        info = seen.get(id(f))
+        if info is None:
+            if f.ndim != 4 or f.dtype != f0.dtype or f.device != f0.device:
+                raise ValueError(f"patch_gather_scaled: frame {i} is {tuple(f.shape)} {f.dtype} on {f.device}, frame 0 is "
+                                 f"{f0.dtype} on {f0.device}: one launch serves (C, Z, H, W) frames of one dtype and device")
+            sc, sz, sy, sx = f.stride()
+            if (sx != 1 and f.shape[3] > 1) or min(sc, sz, sy) < 0:
+                raise ValueError(f"patch_gather_scaled: frame {i} has strides {f.stride()}: x must be contiguous, the others >= 0")
+            info = seen[id(f)] = ((f.data_ptr(), sc, sz, sy), tuple(f.shape))
+            held.append(f)
+        rows[i], dims[i] = info
+        for a, t in enumerate((channels[i], zs[i], ys[i], xs[i])):
+            k = seg_of.get(id(t))
+            if k is None:
+                arr = np.asarray(t)
+                if arr.ndim != 1 or arr.size == 0 or arr.dtype.kind not in "iu":
+                    raise ValueError(f"patch_gather_scaled: patch {i} {PGS_AXES[a]} table must be a non-empty 1-D integer array")
+                k = seg_of[id(t)] = len(segs)
+                held.append(t)
+                segs.append(arr.astype(np.int64, copy=False))
+            seg[i, a] = k
+    lengths = np.array([s.size for s in segs], dtype=np.int64)
+    starts = np.concatenate(([0], np.cumsum(lengths)[:-1]))
+    flat = np.concatenate(segs)
+    lo, hi = np.minimum.reduceat(flat, starts), np.maximum.reduceat(flat, starts)
+    size = lengths[seg]  # (n, 4): C, Zt, Yt, Xt of every patch
+    if (size != size[0]).any():
+        i, a = (int(v[0]) for v in np.nonzero(size != size[0]))
+        raise ValueError(f"patch_gather_scaled: patch {i} {PGS_AXES[a]} table has {int(size[i, a])} entries, patch 0 has "
+                         f"{int(size[0, a])}: one launch writes one (C, Zt, Yt, Xt)")
+    bad = (lo[seg] < 0) | (hi[seg] >= dims)
+    if bad.any():
+        i, a = (int(v[0]) for v in np.nonzero(bad))
+        raise ValueError(f"patch_gather_scaled: patch {i} {PGS_AXES[a]} table spans [{int(lo[seg[i, a]])}, {int(hi[seg[i, a]])}], "
+                         f"which leaves the frame's [0, {int(dims[i, a])})")
+    desc = torch.from_numpy(np.concatenate((rows, starts[seg]), axis=1))
+    return desc, torch.from_numpy(flat.astype(np.int32)), (n, *(int(v) for v in size[0]))
+
+
+def patch_gather_scaled(frames: Sequence[Tensor], channels: Sequence, zs: Sequence, ys: Sequence, xs: Sequence,
+                        out: Tensor | None = None) -> Tensor:
+    """-> float32 (n, C, Zt, Yt, Xt): ``out[i] = frames[i][channels[i]][:, zs[i]][:, :, ys[i]][:, :, :, xs[i]]`` converted exactly, ONE
+    launch for all n: per-patch channel lists, per-patch boxes in frames of different shapes, and the resampling that the tables
+    spell out (``viscy_amd.data.multi_experiment.nearest_exact_index``).  Tables and descriptors are checked on the host
+    (``patch_tables``) and travel in one pinned copy; nothing is launched when a check fails.  The frames must stay alive until
+    the launch has been issued on the current stream, which the caller's references guarantee."""
+    desc, idx, shape = patch_tables(frames, channels, zs, ys, xs)
+    f0 = frames[0]
+    if not f0.is_cuda:
+        raise RuntimeError("viscy_amd: patch_gather_scaled runs on the HIP device only (host patches: "
+                           "viscy_amd.data.multi_experiment.host_gather)")
+    n, C, Zt, Yt, Xt = shape
+    if n * C * Zt * Yt * Xt >= 2 ** 62 or max(shape) >= 2 ** 31 or idx.numel() >= 2 ** 31:
+        raise ValueError("patch_gather_scaled: sizes exceed the kernel's index range")
+    if Xt > L.PGS_MAX_XT:
+        raise ValueError(f"patch_gather_scaled: Xt={Xt}, the kernel holds x tables of at most {L.PGS_MAX_XT} entries")
+    words = n * L.PGS_DESC
+    both = torch.empty(words + (idx.numel() + 1) // 2, dtype=torch.int64, pin_memory=True)  # descriptors, then the int32 tables
+    both[:words] = desc.reshape(-1)
+    both[words:].view(torch.int32)[: idx.numel()] = idx
+    dev = both.to(f0.device, non_blocking=True)
+    out = torch.empty(shape, dtype=torch.float32, device=f0.device) if out is None else _typed(out, torch.float32, shape, "patch_gather_scaled: out")
+    check(lib().vsx_patch_gather_scaled(ptr(dev), ptr(dev[words:]), ptr(out), n, C, Zt, Yt, Xt, PATCH_GATHER_DTYPES[f0.dtype], stream()),
+          "patch_gather_scaled")
     return out
