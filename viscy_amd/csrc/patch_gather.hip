@@ -10,55 +10,46 @@
 // body take the widest form the OUTPUT address of the row allows (16 / 8 / 4 bytes; Xp is even, so rows start 8-byte aligned,
 // and the head shifts that by its own length), decided once per row.
 // float32 sources travel as 32-bit integers: NaN payloads, signed zeros and denormals arrive bit for bit.
-#include "vsx_common.h"
-#include "../../include/vsx.h"
+#include "src_frame.h"
 
+// raw: the type a source element is loaded as;  bits(v): its fp32 bit pattern;  unpack(w, f): the 16 / sizeof(T) elements of one vector
 template <typename T>
-struct PgSrc;  // bits(v): the fp32 bit pattern of source element v;  unpack(w, f): the 16 / sizeof(T) elements of one vector
-template <>
-struct PgSrc<float> {
-  typedef uint32_t raw;
-  static __device__ __forceinline__ uint32_t bits(uint32_t v) { return v; }
-  static __device__ __forceinline__ void unpack(const uint4& w, uint32_t* f) { f[0] = w.x; f[1] = w.y; f[2] = w.z; f[3] = w.w; }
+struct PgSrc {
+  typedef typename vsx_src_raw<T>::type raw;
+  static __device__ __forceinline__ uint32_t bits(raw v) { return vsx_src_bits(v); }
+  static __device__ __forceinline__ void unpack(const uint4& w, uint32_t* f);
 };
 template <>
-struct PgSrc<uint16_t> {
-  typedef uint16_t raw;
-  static __device__ __forceinline__ uint32_t bits(uint16_t v) { return __float_as_uint((float)v); }
-  static __device__ __forceinline__ void unpack(const uint4& w, uint32_t* f) {
-    const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+__device__ __forceinline__ void PgSrc<float>::unpack(const uint4& w, uint32_t* f) { f[0] = w.x; f[1] = w.y; f[2] = w.z; f[3] = w.w; }
+template <>
+__device__ __forceinline__ void PgSrc<uint16_t>::unpack(const uint4& w, uint32_t* f) {
+  const uint32_t d[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __float_as_uint((float)(d[i] & 0xffffu));
-      f[2 * i + 1] = __float_as_uint((float)(d[i] >> 16));
-    }
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = __float_as_uint((float)(d[i] & 0xffffu));
+    f[2 * i + 1] = __float_as_uint((float)(d[i] >> 16));
   }
-};
+}
 template <>
-struct PgSrc<int16_t> {
-  typedef int16_t raw;
-  static __device__ __forceinline__ uint32_t bits(int16_t v) { return __float_as_uint((float)v); }
-  static __device__ __forceinline__ void unpack(const uint4& w, uint32_t* f) {
-    const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+__device__ __forceinline__ void PgSrc<int16_t>::unpack(const uint4& w, uint32_t* f) {
+  const uint32_t d[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __float_as_uint((float)(int16_t)(d[i] & 0xffffu));
-      f[2 * i + 1] = __float_as_uint((float)(int16_t)(d[i] >> 16));
-    }
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = __float_as_uint((float)(int16_t)(d[i] & 0xffffu));
+    f[2 * i + 1] = __float_as_uint((float)(int16_t)(d[i] >> 16));
   }
-};
+}
 template <>
-struct PgSrc<uint8_t> {
-  typedef uint8_t raw;
-  static __device__ __forceinline__ uint32_t bits(uint8_t v) { return __float_as_uint((float)v); }
-  static __device__ __forceinline__ void unpack(const uint4& w, uint32_t* f) {
-    const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+__device__ __forceinline__ void PgSrc<uint8_t>::unpack(const uint4& w, uint32_t* f) {
+  const uint32_t d[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) f[4 * i + j] = __float_as_uint((float)((d[i] >> (8 * j)) & 0xffu));
-  }
-};
+    for (int j = 0; j < 4; ++j) f[4 * i + j] = __float_as_uint((float)((d[i] >> (8 * j)) & 0xffu));
+}
+
+// lanes per row: enough for the row's `vecs` 16-byte vectors in one sweep, at most a wave
+static inline int pg_lanes_per_row(int vecs) { return vecs <= 16 ? 16 : (vecs <= 32 ? 32 : 64); }
 
 // desc: VSX_PG_DESC int64 per patch {frame base address, stride c, stride z, stride y (elements), y0, x0}
 template <typename T>
@@ -106,24 +97,16 @@ extern "C" int32_t vsx_patch_gather(const int64_t* desc, float* out, int32_t n, 
                                     int32_t src_dtype, vsx_stream_t stream) {
   VSX_CHECK(desc && out && n > 0 && C > 0 && Z > 0 && Yp > 0 && Xp > 0, "vsx_patch_gather: bad arguments");
   VSX_CHECK(((uintptr_t)out & 15) == 0 && ((uintptr_t)desc & 7) == 0, "vsx_patch_gather: out must be 16-byte aligned, desc 8-byte aligned");
-  VSX_CHECK(src_dtype >= VSX_PG_F32 && src_dtype <= VSX_PG_U8, "vsx_patch_gather: unknown source dtype code %d", src_dtype);
-  const int ve = src_dtype == VSX_PG_F32 ? 4 : (src_dtype == VSX_PG_U8 ? 16 : 8);
-  // lanes per row: enough for the row's whole vectors in one sweep, at most a wave
-  const int vecs = vsx_cdiv(Xp, ve);
-  const int lpr = vecs <= 16 ? 16 : (vecs <= 32 ? 32 : 64);
+  VSX_CHECK_SRC("vsx_patch_gather", src_dtype);
+  const int lpr = pg_lanes_per_row(vsx_cdiv(Xp, vsx_src_vec_elems(src_dtype)));
   const long rows = (long)n * C * Z * Yp;
-  long g = (rows + 256 / lpr - 1) / (256 / lpr);
-  const long cap = (long)vsx_cu_count() * 8;  // eight 256-thread workgroups per CU fill every wave slot; the rest loops
-  if (g > cap) g = cap;
-  uint32_t* o = reinterpret_cast<uint32_t*>(out);
-  const dim3 grid((unsigned)g), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  switch (src_dtype) {
-    case VSX_PG_F32: hipLaunchKernelGGL(patch_gather_kernel<float>, grid, block, 0, s, desc, o, rows, C, Z, Yp, Xp, lpr); break;
-    case VSX_PG_U16: hipLaunchKernelGGL(patch_gather_kernel<uint16_t>, grid, block, 0, s, desc, o, rows, C, Z, Yp, Xp, lpr); break;
-    case VSX_PG_I16: hipLaunchKernelGGL(patch_gather_kernel<int16_t>, grid, block, 0, s, desc, o, rows, C, Z, Yp, Xp, lpr); break;
-    default: hipLaunchKernelGGL(patch_gather_kernel<uint8_t>, grid, block, 0, s, desc, o, rows, C, Z, Yp, Xp, lpr); break;
-  }
+  const dim3 grid(vsx_capped_grid(rows, 256 / lpr, 8)), block(256);
+  vsx_by_src(src_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(patch_gather_kernel<T>, grid, block, 0, (hipStream_t)stream, desc, reinterpret_cast<uint32_t*>(out), rows, C, Z, Yp,
+                       Xp, lpr);
+    return 0;
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }
@@ -204,30 +187,21 @@ extern "C" int32_t vsx_patch_gather_scaled(const int64_t* desc, const int32_t* i
   VSX_CHECK(desc && idx && out && n > 0 && C > 0 && Zt > 0 && Yt > 0 && Xt > 0, "vsx_patch_gather_scaled: bad arguments");
   VSX_CHECK(((uintptr_t)out & 15) == 0 && ((uintptr_t)desc & 7) == 0 && ((uintptr_t)idx & 3) == 0,
             "vsx_patch_gather_scaled: out must be 16-byte aligned, desc 8-byte, idx 4-byte");
-  VSX_CHECK(src_dtype >= VSX_PG_F32 && src_dtype <= VSX_PG_U8, "vsx_patch_gather_scaled: unknown source dtype code %d", src_dtype);
+  VSX_CHECK_SRC("vsx_patch_gather_scaled", src_dtype);
   VSX_CHECK(Xt <= VSX_PGS_MAX_XT, "vsx_patch_gather_scaled: Xt=%d, the x table in LDS holds %d", Xt, VSX_PGS_MAX_XT);
-  // lanes per row: enough for the row's 16-byte output vectors in one sweep, at most a wave; a unit gives each group four rows
-  const int vecs = vsx_cdiv(Xt, 4);
-  const int lpr = vecs <= 16 ? 16 : (vecs <= 32 ? 32 : 64);
+  // a row's vectors are the 16-byte vectors of the OUTPUT; a unit gives each group of lanes VSX_PGS_ROWS_PER_GROUP rows
+  const int lpr = pg_lanes_per_row(vsx_cdiv(Xt, 4));
   const int rb = (256 / lpr) * VSX_PGS_ROWS_PER_GROUP;
   const int yblocks = vsx_cdiv(Yt, rb);
   const long units = (long)n * C * Zt * yblocks;
-  long g = units;
-  const long cap = (long)vsx_cu_count() * 8;  // eight 256-thread workgroups per CU fill every wave slot; the rest loops
-  if (g > cap) g = cap;
-  uint32_t* o = reinterpret_cast<uint32_t*>(out);
-  const dim3 grid((unsigned)g), block(256);
+  const dim3 grid(vsx_capped_grid(units, 1, 8)), block(256);
   const size_t lds = (size_t)Xt * sizeof(int32_t);
-  hipStream_t s = (hipStream_t)stream;
-#define VSX_PGS_LAUNCH(T) \
-  hipLaunchKernelGGL(patch_gather_scaled_kernel<T>, grid, block, lds, s, desc, idx, o, units, C, Zt, Yt, Xt, lpr, rb, yblocks)
-  switch (src_dtype) {
-    case VSX_PG_F32: VSX_PGS_LAUNCH(float); break;
-    case VSX_PG_U16: VSX_PGS_LAUNCH(uint16_t); break;
-    case VSX_PG_I16: VSX_PGS_LAUNCH(int16_t); break;
-    default: VSX_PGS_LAUNCH(uint8_t); break;
-  }
-#undef VSX_PGS_LAUNCH
+  vsx_by_src(src_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(patch_gather_scaled_kernel<T>, grid, block, lds, (hipStream_t)stream, desc, idx, reinterpret_cast<uint32_t*>(out),
+                       units, C, Zt, Yt, Xt, lpr, rb, yblocks);
+    return 0;
+  });
   VSX_LAUNCH_CHECK();
   return 0;
 }

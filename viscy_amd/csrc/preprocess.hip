@@ -14,8 +14,7 @@
 // No floating-point atomics.  The sums are per-chunk partials written by plain stores (every word is written before it is read: the
 // workspace needs no initialisation) and folded in a fixed order; the histograms add integers.  Every output is bit-identical from
 // run to run.  No allocation, synchronisation or device-to-host copy; every check runs before any launch.
-#include "vsx_common.h"
-#include "../../include/vsx.h"
+#include "src_frame.h"
 
 #define MED_COLS VSX_MEDIAN_COLS        // output columns of a wave: lanes 1 .. 62 of the 64 loaded columns
 #define MED_ROWS VSX_MEDIAN_ROWS        // output rows a wave walks down before it moves to its next strip
@@ -24,27 +23,6 @@
 #define HIST_LDS_BINS VSX_HIST_LDS_BINS
 static_assert(MED_COLS == 62, "a wave loads 64 columns: its outputs and one halo column on each side");
 static_assert(MOM_CHUNK % 1024 == 0, "256 threads take float4 vectors round by round");
-
-template <typename T>
-__device__ __forceinline__ float pp_value(T v) { return (float)v; }  // exact for the integer types; the identity for float
-template <typename T>
-__device__ __forceinline__ uint32_t pp_bits(const T* p) { return __float_as_uint((float)*p); }
-template <>
-__device__ __forceinline__ uint32_t pp_bits<float>(const float* p) { return *reinterpret_cast<const uint32_t*>(p); }
-
-// runtime source dtype code -> element type, as vsx_by_dtype does for the compute dtypes
-template <class F>
-static __forceinline__ auto pp_by_src(int code, F&& f) -> decltype(f(vsx_type<float>{})) {
-  if (code == VSX_PG_U16) return f(vsx_type<uint16_t>{});
-  if (code == VSX_PG_I16) return f(vsx_type<int16_t>{});
-  if (code == VSX_PG_U8) return f(vsx_type<uint8_t>{});
-  return f(vsx_type<float>{});
-}
-static inline unsigned pp_grid(long items, long per_block, int blocks_per_cu) {
-  long g = (items + per_block - 1) / per_block;
-  const long cap = (long)vsx_cu_count() * blocks_per_cu;
-  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
 
 // ------------------------------------------------------------------ grid sample
 template <typename T>
@@ -55,19 +33,19 @@ __global__ __launch_bounds__(256) void grid_sample_kernel(const T* __restrict__ 
     const long r = i / wo;
     const int y = (int)(r % ho);
     const long z = r / ho;
-    out[i] = pp_bits<T>(src + z * sz + (long)y * g * sy + (long)x * g);  // y g <= H - 1, x g <= W - 1
+    out[i] = vsx_src_bits_at<T>(src + z * sz + (long)y * g * sy + (long)x * g);  // y g <= H - 1, x g <= W - 1
   }
 }
 
 extern "C" int32_t vsx_grid_sample(const void* src, int32_t src_dtype, int64_t z_stride, int64_t y_stride, int32_t Z, int32_t H, int32_t W,
                                    int32_t g, float* out, vsx_stream_t stream) {
   VSX_CHECK(src && out && Z > 0 && H > 0 && W > 0 && g >= 1, "vsx_grid_sample: bad arguments");
-  VSX_CHECK(src_dtype >= VSX_PG_F32 && src_dtype <= VSX_PG_U8, "vsx_grid_sample: unknown source dtype code %d", src_dtype);
+  VSX_CHECK_SRC("vsx_grid_sample", src_dtype);
   VSX_CHECK(y_stride >= W && z_stride >= 0, "vsx_grid_sample: y_stride %ld < W or z_stride %ld < 0", (long)y_stride, (long)z_stride);
   const int ho = (H + g - 1) / g, wo = (W + g - 1) / g;
   const long total = (long)Z * ho * wo;
-  const dim3 grid(pp_grid(total, 256, 8)), block(256);
-  pp_by_src(src_dtype, [&](auto tag) {
+  const dim3 grid(vsx_capped_grid(total, 256, 8)), block(256);
+  vsx_by_src(src_dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL(grid_sample_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)src, (long)z_stride, (long)y_stride, ho, wo, g,
                        total, reinterpret_cast<uint32_t*>(out));
@@ -100,10 +78,10 @@ __global__ __launch_bounds__(256) void median3x3_kernel(const T* __restrict__ sr
     const int cc = min(max(c, 0), W - 1);  // every load stays inside its row
     const T* col = src + z * sz + cc;
     const bool writes = lane >= 1 && lane <= MED_COLS && c < W;
-    float a = pp_value(col[(long)max(y0 - 1, 0) * sy]);
-    float b = pp_value(col[(long)y0 * sy]);
+    float a = vsx_src_value(col[(long)max(y0 - 1, 0) * sy]);
+    float b = vsx_src_value(col[(long)y0 * sy]);
     for (int y = y0; y < y1; ++y) {
-      const float d = pp_value(col[(long)min(y + 1, H - 1) * sy]);
+      const float d = vsx_src_value(col[(long)min(y + 1, H - 1) * sy]);
       const float lo = fminf(fminf(a, b), d), hi = fmaxf(fmaxf(a, b), d), mid = pp_med3(a, b, d);
       const float lo_l = __shfl_up(lo, 1, 64), lo_r = __shfl_down(lo, 1, 64);
       const float mid_l = __shfl_up(mid, 1, 64), mid_r = __shfl_down(mid, 1, 64);
@@ -123,18 +101,18 @@ extern "C" int32_t vsx_median3x3(const void* src, int32_t src_dtype, int64_t z_s
                                  float* out, uint8_t* mask, float thr, vsx_stream_t stream) {
   VSX_CHECK(src && Z > 0 && H > 0 && W > 0, "vsx_median3x3: bad arguments");
   VSX_CHECK((out != nullptr) != (mask != nullptr), "vsx_median3x3: exactly one of out (fp32 median) and mask (uint8 median >= thr)");
-  VSX_CHECK(src_dtype >= VSX_PG_F32 && src_dtype <= VSX_PG_U8, "vsx_median3x3: unknown source dtype code %d", src_dtype);
+  VSX_CHECK_SRC("vsx_median3x3", src_dtype);
   VSX_CHECK(out == nullptr || src_dtype == VSX_PG_F32, "vsx_median3x3: the fp32 epilogue takes an fp32 source");
   VSX_CHECK(y_stride >= W && z_stride >= 0, "vsx_median3x3: y_stride %ld < W or z_stride %ld < 0", (long)y_stride, (long)z_stride);
   const int sx = vsx_cdiv(W, MED_COLS), sr = vsx_cdiv(H, MED_ROWS);
   const long strips = (long)Z * sx * sr;
-  const dim3 grid(pp_grid(strips, 4, 16)), block(256);
+  const dim3 grid(vsx_capped_grid(strips, 4, 16)), block(256);
   hipStream_t s = (hipStream_t)stream;
   if (out) {
     hipLaunchKernelGGL((median3x3_kernel<float, false>), grid, block, 0, s, (const float*)src, (long)z_stride, (long)y_stride, H, W, sx, sr,
                        strips, thr, out, (uint8_t*)nullptr);
   } else {
-    pp_by_src(src_dtype, [&](auto tag) {
+    vsx_by_src(src_dtype, [&](auto tag) {
       using T = typename decltype(tag)::type;
       hipLaunchKernelGGL((median3x3_kernel<T, true>), grid, block, 0, s, (const T*)src, (long)z_stride, (long)y_stride, H, W, sx, sr, strips,
                          thr, (float*)nullptr, mask);
@@ -340,7 +318,7 @@ __global__ __launch_bounds__(256) void hist_int_kernel(const float* __restrict__
 }
 
 static inline unsigned hist_grid(long n) {
-  unsigned g = pp_grid(n, 256 * 16, 4);
+  unsigned g = vsx_capped_grid(n, 256 * 16, 4);
   const long need = (n + HIST_WG_MAX - 1) / HIST_WG_MAX;  // grid-stride: a workgroup sees at most ceil(n / g) + 256 values
   return (unsigned)(g < need ? need : g);
 }

@@ -4,11 +4,11 @@ packages/viscy-data/src/viscy_data/{sampler,channel_dropout,channel_utils}.py), 
 
 The reference reads one native box per cell and view through tensorstore, resamples each on the host with
 ``F.interpolate(mode="nearest-exact")``, stacks and uploads.  Here the time-point frames stay resident in device memory
-(``FrameCache`` of ``triplet.py``) and ONE ``vsx_patch_gather_scaled`` launch forms anchor and positive together: every patch
-names its channels and its source planes, rows and columns through index tables, and the tables ARE the resampling
-(``nearest_exact_index`` takes the map from CPU torch itself, per ``(in, out)`` pair, so the kernel restates no formula).  A frame
-the budget cannot hold is gathered on the host through the same tables and joins the same launch as a packed block.  Without a
-HIP device everything goes through ``host_gather``, which is what the CPU tests compare against the reference's recorded patches.
+(``feed.FrameCache``) and ONE ``vsx_patch_gather_scaled`` launch forms anchor and positive together (``feed.PatchCutter``, which
+also serves the frames the budget cannot hold): every patch names its channels and its source planes, rows and columns through
+index tables, and the tables ARE the resampling (``nearest_exact_index`` takes the map from CPU torch itself, per ``(in, out)``
+pair, so the kernel restates no formula).  Without a HIP device everything goes through ``host_gather`` with the same tables,
+which is what the CPU tests compare against the reference's recorded patches.
 
 Host table work is pandas / numpy in the reference's order; ``FlexibleBatchSampler`` draws what the reference draws for a seed.
 
@@ -40,9 +40,11 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 from torch.utils.data import DataLoader, Dataset, Sampler
 
+from .. import ops
+from .feed import FrameCache, PatchCutter, check_storage_dtype, default_device, identity, transform_channel_wise
 from .hcs import Compose, read_norm_meta
 from .ome_zarr import open_ome_zarr
-from .triplet import MAX_READ_THREADS, STORAGE_DTYPES, ULTRACK_INDEX_COLUMNS, FrameCache
+from .triplet import ULTRACK_INDEX_COLUMNS
 
 try:  # pragma: no cover
     from lightning.pytorch import LightningDataModule as _DMBase
@@ -863,14 +865,13 @@ class MultiExperimentTripletDataset(Dataset):
         if self.fit:
             self._build_match_lookup()
         self._build_anchor_cache()
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device = torch.device(device)
+        self.device = default_device(device)
         self.cache = None
         if self.device.type == "cuda":
             if device_cache_bytes is None:
                 device_cache_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
             self.cache = FrameCache(self._load_frame, self._frame_nbytes, self.device, int(device_cache_bytes))
+        self._cutter = PatchCutter(self.device, self.cache, self._load_frame)
 
     # ------------------------------------------------------------------ lookups (dataset.py:265-382)
     def _build_match_lookup(self) -> None:
@@ -1055,9 +1056,7 @@ class MultiExperimentTripletDataset(Dataset):
         image = self._image_cache.get(key)
         if image is None:
             image = self._image_cache[key] = self._get_position(store_path, fov_name)["0"]
-            if np.dtype(image.dtype) not in STORAGE_DTYPES:
-                raise NotImplementedError(f"{store_path}/{fov_name}: images stored as {np.dtype(image.dtype)} are not built "
-                                          "(float32, uint16, int16 and uint8 are)")
+            check_storage_dtype(image.dtype, f"{store_path}/{fov_name}")
         return image
 
     def _frame_nbytes(self, key) -> int:
@@ -1068,14 +1067,6 @@ class MultiExperimentTripletDataset(Dataset):
         """the (C, Z, H, W) block of time point ``t`` of a FOV, every channel and plane: rows of one frame name different channels"""
         image = self._image(key[0], key[1])
         return image.oindex[int(key[2]), list(range(image.channels)), slice(0, image.slices)][0]
-
-    def _read_frames(self, keys: list) -> dict:
-        from concurrent.futures import ThreadPoolExecutor
-
-        if len(keys) <= 1:
-            return {k: self._load_frame(k) for k in keys}
-        with ThreadPoolExecutor(max_workers=min(len(keys), MAX_READ_THREADS)) as pool:
-            return dict(zip(keys, pool.map(self._load_frame, keys)))
 
     # ------------------------------------------------------------------ boxes and norm meta (dataset.py:694-854)
     def _build_norm_meta(self, arrays: dict, idx: int, forced_channel_names):
@@ -1179,87 +1170,14 @@ class MultiExperimentTripletDataset(Dataset):
                                "different channel counts. Set channels_per_sample=1 (bag-of-channels) "
                                "or channels_per_sample=[...] (fixed channel list).")
         C, size = channel_counts.pop(), shapes.pop()
-        kinds = [np.dtype(self._image(b.key[0], b.key[1]).dtype) for b in boxes]
-        distinct = list(dict.fromkeys(kinds))
-        keys = [b.key for b in boxes]
-        resident = self.cache.begin_batch(keys) if self.cache is not None else dict.fromkeys(keys)
-        if len(distinct) == 1:
-            return self._cut_one_dtype(boxes, tables, C, size, resident)
-        out = None  # stores of different dtypes in one batch: one launch per dtype, each into its rows of the batch
-        for kind in distinct:
-            rows = [i for i, k in enumerate(kinds) if k == kind]
-            part = self._cut_one_dtype([boxes[i] for i in rows], [tables[i] for i in rows], C, size, resident)
-            if out is None:
-                out = torch.empty((len(boxes), C, *size), dtype=torch.float32, device=part.device)
-            out[torch.tensor(rows, device=part.device)] = part
-        return out
-
-    def _cut_one_dtype(self, boxes: list, tables: list, C: int, size: tuple, resident: dict) -> Tensor:
-        host = list(dict.fromkeys(b for b in boxes if resident[b.key] is None))  # distinct boxes: gathered and sent once
-        slot = {b: i for i, b in enumerate(host)}
-        on_device = self.device.type == "cuda"
-        packed = None
-        if host:
-            frames = self._read_frames(list(dict.fromkeys(b.key for b in host)))
-            first = frames[host[0].key]
-            packed = torch.empty((len(host), C, *size), dtype=STORAGE_DTYPES[first.dtype], pin_memory=on_device)
-            view = packed.numpy()
-            for i, b in enumerate(host):
-                view[i] = host_gather(frames[b.key], *self._tables(b))
-        if not on_device:
-            return torch.from_numpy(view[[slot[b] for b in boxes]].astype(np.float32))
-        from .. import ops
-
-        plain = None
-        if packed is not None:
-            packed = packed.to(self.device, non_blocking=True)  # one copy for every host-gathered patch of the batch
-            plain = tuple(np.arange(s, dtype=np.int64) for s in packed.shape[1:])
-        sources, chans, zs, ys, xs = [], [], [], [], []
-        for b, ts in zip(boxes, tables):
-            frame = resident[b.key]
-            if frame is None:
-                frame, ts = packed[slot[b]], plain
-            sources.append(frame)
-            chans.append(ts[0]); zs.append(ts[1]); ys.append(ts[2]); xs.append(ts[3])
-        return ops.patch_gather_scaled(sources, chans, zs, ys, xs)
+        return self._cutter.cut(boxes, [b.key for b in boxes], tables,
+                                host_patch=lambda frame, b: host_gather(frame, *self._tables(b)),
+                                plain=lambda: tuple(np.arange(s, dtype=np.int64) for s in (C, *size)),
+                                launch=lambda sources, ts: ops.patch_gather_scaled(sources, *zip(*ts)),
+                                kinds=[np.dtype(self._image(b.key[0], b.key[1]).dtype) for b in boxes])
 
 
 # ------------------------------------------------------------------------------------------------ module (datamodule.py)
-def _identity(batch):
-    return batch
-
-
-def _tree_to(tree, device):
-    if isinstance(tree, dict):
-        return {k: _tree_to(v, device) for k, v in tree.items()}
-    return tree.to(device) if torch.is_tensor(tree) else tree
-
-
-def _collate_norm_meta(norm_metas: list) -> dict:
-    """per-sample ``{channel: {level: {stat: 0-d tensor}}}`` -> the same tree of (B,) tensors (_utils.py:174-191)"""
-    out = {}
-    for ch, levels in norm_metas[0].items():
-        out[ch] = {}
-        for level, stats in levels.items():
-            out[ch][level] = None if stats is None else {st: torch.stack([m[ch][level][st] for m in norm_metas]) for st in stats}
-    return out
-
-
-def _transform_channel_wise(transform, channel_names: list[str], patch: Tensor, norm_meta: list | None, extra: dict | None = None) -> Tensor:
-    """_utils.py:194-229 with ``extra``: channels go into a dict under their names (B, 1, Z, Y, X) with the collated statistics
-    (moved to the patch's device) and the extra entries (the ``_is_labelfree`` mask), through the dict transform, and back
-    together in the dict's order without the extras"""
-    channels = {name: patch[:, c : c + 1].contiguous() for name, c in zip(channel_names, range(patch.shape[1]))}
-    if norm_meta is not None:
-        channels["norm_meta"] = _tree_to(_collate_norm_meta(norm_meta), patch.device)
-    if extra is not None:
-        channels.update(extra)
-    channels = transform(channels)
-    for k in ("norm_meta",) + tuple(extra or ()):
-        channels.pop(k, None)
-    return torch.cat(list(channels.values()), dim=1)
-
-
 class MultiExperimentDataModule(_DMBase):
     """``dynaclr.data.datamodule.MultiExperimentDataModule``: every constructor keyword of the reference.  ``num_workers``,
     ``pin_memory``, ``prefetch_factor``, ``buffer_size``, ``cache_pool_bytes``, ``recheck_cached_data`` and ``file_io_concurrency`` are
@@ -1437,16 +1355,16 @@ class MultiExperimentDataModule(_DMBase):
 
     def train_dataloader(self):
         return DataLoader(self.train_dataset, batch_sampler=self._sampler(self.train_dataset, self.temporal_enrichment),
-                          num_workers=0, collate_fn=_identity)
+                          num_workers=0, collate_fn=identity)
 
     def val_dataloader(self):
         if self.val_dataset is None:
             return None
-        return DataLoader(self.val_dataset, batch_sampler=self._sampler(self.val_dataset, False), num_workers=0, collate_fn=_identity)
+        return DataLoader(self.val_dataset, batch_sampler=self._sampler(self.val_dataset, False), num_workers=0, collate_fn=identity)
 
     def predict_dataloader(self):
         return DataLoader(self.predict_dataset, batch_size=self.batch_size, num_workers=0, shuffle=False, drop_last=False,
-                          collate_fn=_identity)
+                          collate_fn=identity)
 
     # ------------------------------------------------------------------ transforms (datamodule.py:721-824)
     def _train_final_crop(self):
@@ -1479,7 +1397,7 @@ class MultiExperimentDataModule(_DMBase):
             return batch
         if self.trainer is not None and getattr(self.trainer, "predicting", False):
             norm_meta = self._all_or_none(batch.get("anchor_norm_meta"), "Mixed None/non-None norm_meta in predict batch.")
-            batch["anchor"] = _transform_channel_wise(self._predict_transform, self._channel_names, batch["anchor"], norm_meta,
+            batch["anchor"] = transform_channel_wise(self._predict_transform, self._channel_names, batch["anchor"], norm_meta,
                                                       self._labelfree_mask(batch, "anchor"))
             batch.pop("anchor_norm_meta", None)
             batch.pop("anchor_meta", None)
@@ -1489,7 +1407,7 @@ class MultiExperimentDataModule(_DMBase):
                 norm_meta_key = f"{key}_norm_meta"
                 norm_meta = self._all_or_none(batch.get(norm_meta_key), f"Mixed None/non-None norm_meta in batch for '{key}'. "
                                               "All FOVs must have normalization metadata or none of them.")
-                batch[key] = _transform_channel_wise(self._augmentation_transform, self._channel_names, batch[key], norm_meta,
+                batch[key] = transform_channel_wise(self._augmentation_transform, self._channel_names, batch[key], norm_meta,
                                                      self._labelfree_mask(batch, key))
                 if norm_meta_key in batch:
                     del batch[norm_meta_key]

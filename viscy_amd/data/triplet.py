@@ -2,26 +2,23 @@
 (packages/viscy-data/src/viscy_data/triplet.py:53-588), with the patches cut on the device.
 
 The reference reads every patch through tensorstore on the host, one read per cell and view, and uploads the stack.  Here the
-time-point frames the patches come from are staged once into device memory (``FrameCache``: least recently used, bounded by
+time-point frames the patches come from are staged once into device memory (``feed.FrameCache``, bounded by
 ``device_cache_bytes``) and ONE ``vsx_patch_gather`` launch cuts a whole batch (anchor, positive and negative together) out of
-them as float32 ``[n, C, Z, Yp, Xp]``.  A frame the budget cannot hold is cut on the host instead; its patches travel packed in
-one pinned buffer and are described to the same launch, so the device has one code path and both sources give the same bits.
-Without a HIP device everything is cut on the host (``host_cut``), which is what the CPU tests compare against.
+them as float32 ``[n, C, Z, Yp, Xp]`` (``feed.PatchCutter``, which also serves the frames the budget cannot hold).  Without a HIP
+device everything is cut on the host (``host_cut``), which is what the CPU tests compare against.
 
 Host table work (filtering, anchors, positives, negative draws) is pandas, call for call in the reference's order, so that a
 seeded run (``numpy.random.seed``) draws the same cells.
 
 Beyond the reference: ``device_cache_bytes``.  Not built here: fusing ``NormalizeSampled`` into the gather.
-``MultiExperimentDataModule`` sits on ``FrameCache`` in ``multi_experiment.py``.
+``MultiExperimentDataModule`` sits on the same feed in ``multi_experiment.py``.
 """
 
 from __future__ import annotations
 
 import warnings
-from collections import OrderedDict
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Callable, Hashable, Literal, Sequence
+from typing import Literal, Sequence
 
 import numpy as np
 import torch
@@ -29,16 +26,13 @@ from torch import Tensor
 from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
+from .. import ops
+from .feed import (MAX_READ_THREADS, STORAGE_DTYPES, FrameCache, PatchCutter, check_storage_dtype, default_device,  # noqa: F401
+                   identity, transform_channel_wise, tree_to)
 from .hcs import Compose, HCSDataModule, read_norm_meta
 from .ome_zarr import open_ome_zarr
 
 ULTRACK_INDEX_COLUMNS = ["fov_name", "track_id", "t", "id", "parent_track_id", "parent_id", "z", "y", "x"]
-# storage dtypes vsx_patch_gather reads (each converts to float32 exactly)
-STORAGE_DTYPES = {np.dtype(np.float32): torch.float32, np.dtype(np.uint16): torch.uint16, np.dtype(np.int16): torch.int16,
-                  np.dtype(np.uint8): torch.uint8}
-MAX_READ_THREADS = 16
-
-
 def patch_extent(center: int, size: int) -> tuple[int, int]:
     """(start, length) of ``slice(c - s // 2, c + s // 2)``: ``2 * (s // 2)`` wide, one less than ``s`` for odd ``s``"""
     half = int(size) // 2
@@ -53,75 +47,6 @@ def host_cut(frame: np.ndarray, y0: int, x0: int, yp: int, xp: int) -> np.ndarra
     if x0 < 0 or x0 + xp > W:
         raise ValueError(f"patch columns [{x0}, {x0 + xp}) leave the frame's [0, {W})")
     return frame[:, :, y0 : y0 + yp, x0 : x0 + xp]
-
-
-def _tree_to(tree, device):
-    """the statistics of a normalisation tree on ``device`` (the batch is born there; the trainer's transfer then moves nothing)"""
-    if isinstance(tree, dict):
-        return {k: _tree_to(v, device) for k, v in tree.items()}
-    return tree.to(device) if torch.is_tensor(tree) else tree
-
-
-class FrameCache:
-    """Time-point frames resident on ``device``: key -> (C, Z, H, W) tensor in its storage dtype, at most ``budget_bytes`` in all.
-
-    ``begin_batch(keys)`` answers, per distinct key, the resident tensor or ``None`` (cut that frame's patches on the host).  A
-    missing frame is staged through pinned memory when it fits after evicting least recently used frames that the batch does
-    NOT need; a frame the batch needs is never evicted, so what ``begin_batch`` hands out stays valid for the whole batch.
-    ``load(key)`` reads a frame as a numpy array, ``nbytes(key)`` tells its size without reading it.  Pure host policy over
-    torch tensors: ``device`` may be the CPU."""
-
-    def __init__(self, load: Callable[[Hashable], np.ndarray], nbytes: Callable[[Hashable], int], device, budget_bytes: int):
-        self._load, self._nbytes = load, nbytes
-        self.device, self.budget_bytes = torch.device(device), max(int(budget_bytes), 0)
-        self._frames: OrderedDict = OrderedDict()  # least recently used first
-        self._sizes: dict = {}
-        self.bytes_used = 0
-        self.uploads = self.hits = self.evictions = self.refused = 0
-
-    def keys(self) -> list:
-        """resident keys, least recently used first"""
-        return list(self._frames)
-
-    def __contains__(self, key) -> bool:
-        return key in self._frames
-
-    def _stage(self, key) -> Tensor:
-        host = torch.from_numpy(np.ascontiguousarray(self._load(key)))
-        if self.device.type != "cuda":
-            return host
-        pinned = torch.empty(host.shape, dtype=host.dtype, pin_memory=True)
-        pinned.copy_(host)
-        return pinned.to(self.device, non_blocking=True)
-
-    def begin_batch(self, keys: Sequence[Hashable]) -> dict:
-        needed = list(dict.fromkeys(keys))
-        pinned = set(needed)
-        out = {}
-        for key in needed:
-            if key in self._frames:
-                self._frames.move_to_end(key)
-                self.hits += 1
-                out[key] = self._frames[key]
-                continue
-            size = int(self._nbytes(key))
-            evictable = sum(self._sizes[k] for k in self._frames if k not in pinned)
-            if self.bytes_used - evictable + size > self.budget_bytes:
-                self.refused += 1
-                out[key] = None
-                continue
-            for victim in [k for k in self._frames if k not in pinned]:
-                if self.bytes_used + size <= self.budget_bytes:
-                    break
-                del self._frames[victim]
-                self.bytes_used -= self._sizes.pop(victim)
-                self.evictions += 1
-            frame = self._stage(key)
-            self._frames[key], self._sizes[key] = frame, size
-            self.bytes_used += size
-            self.uploads += 1
-            out[key] = frame
-        return out
 
 
 class TripletDataset(Dataset):
@@ -147,9 +72,7 @@ class TripletDataset(Dataset):
         self.include_fov_names = include_fov_names or []
         self.include_track_ids = include_track_ids or []
         self.time_interval = time_interval
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device = torch.device(device)
+        self.device = default_device(device)
         self._images, self._norm_meta, self._norm_resolved = {}, {}, {}
         self.tracks = self._filter_tracks(tracks_tables)
         self.tracks = self._specific_cells(self.tracks) if self.predict_cells else self.tracks
@@ -158,6 +81,7 @@ class TripletDataset(Dataset):
         self.cache = None
         if self.device.type == "cuda":
             self.cache = FrameCache(self._load_frame, self._frame_nbytes, self.device, self._budget(device_cache_bytes))
+        self._cutter = PatchCutter(self.device, self.cache, self._load_frame)
 
     # ------------------------------------------------------------------ tables (triplet.py:138-222)
     def _filter_tracks(self, tracks_tables):
@@ -171,12 +95,10 @@ class TripletDataset(Dataset):
             tracks["fov_name"] = name
             tracks["global_track_id"] = tracks["fov_name"].str.cat(tracks["track_id"].astype(str), sep="_")
             image = pos["0"]
-            if np.dtype(image.dtype) not in STORAGE_DTYPES:
-                raise NotImplementedError(f"{name}: images stored as {np.dtype(image.dtype)} are not built "
-                                          "(float32, uint16, int16 and uint8 are)")
+            check_storage_dtype(image.dtype, name)
             if self.z_range.stop > image.slices:
                 raise ValueError(f"Z range {self.z_range} exceeds image with Z={image.slices}")
-            self._images[name], self._norm_meta[name] = image, _tree_to(read_norm_meta(pos), self.device)  # once, not per batch
+            self._images[name], self._norm_meta[name] = image, tree_to(read_norm_meta(pos), self.device)  # once, not per batch
             y_range = (y_exclude, image.height - y_exclude)
             x_range = (x_exclude, image.width - x_exclude)
             filtered.append(tracks[tracks["y"].between(*y_range, inclusive="neither") & tracks["x"].between(*x_range, inclusive="neither")])
@@ -261,45 +183,12 @@ class TripletDataset(Dataset):
                 for ch, levels in meta.items()}
         return got
 
-    def _read_frames(self, keys: list) -> dict:
-        """host reads of distinct frames, at most MAX_READ_THREADS at a time"""
-        if len(keys) <= 1:
-            return {k: self._load_frame(k) for k in keys}
-        with ThreadPoolExecutor(max_workers=min(len(keys), MAX_READ_THREADS)) as pool:
-            return dict(zip(keys, pool.map(self._load_frame, keys)))
-
     def _cut(self, specs: list) -> Tensor:
         """float32 (n, C, Z, Yp, Xp) on ``self.device`` for ``specs``: one launch over resident frames and packed host cuts"""
-        yp, xp = 2 * (self.yx_patch_size[0] // 2), 2 * (self.yx_patch_size[1] // 2)
-        keys = [s[0] for s in specs]
-        resident = self.cache.begin_batch(keys) if self.cache is not None else dict.fromkeys(keys)
-        host_specs = list(dict.fromkeys(s for s in specs if resident[s[0]] is None))  # distinct (frame, y0, x0): cut and sent once
-        index = {s: i for i, s in enumerate(host_specs)}
-        on_device = self.device.type == "cuda"
-        packed = None
-        if host_specs:
-            frames = self._read_frames(list(dict.fromkeys(s[0] for s in host_specs)))
-            first = frames[host_specs[0][0]]
-            packed = torch.empty((len(host_specs), *first.shape[:2], yp, xp), dtype=STORAGE_DTYPES[first.dtype], pin_memory=on_device)
-            view = packed.numpy()
-            for i, (key, y0, x0) in enumerate(host_specs):
-                view[i] = host_cut(frames[key], y0, x0, yp, xp)
-        if not on_device:
-            return torch.from_numpy(view[[index[s] for s in specs]].astype(np.float32))
-        from .. import ops
-
-        if packed is not None:
-            packed = packed.to(self.device, non_blocking=True)  # one copy for every host-cut patch of the batch
-        sources, origins = [], []
-        for s in specs:
-            frame = resident[s[0]]
-            if frame is None:
-                sources.append(packed[index[s]])
-                origins.append((0, 0))
-            else:
-                sources.append(frame)
-                origins.append((s[1], s[2]))
-        return ops.patch_gather(sources, origins, (yp, xp))
+        size = 2 * (self.yx_patch_size[0] // 2), 2 * (self.yx_patch_size[1] // 2)
+        return self._cutter.cut(specs, [s[0] for s in specs], [(s[1], s[2]) for s in specs],
+                                host_patch=lambda frame, s: host_cut(frame, s[1], s[2], *size), plain=lambda: (0, 0),
+                                launch=lambda sources, origins: ops.patch_gather(sources, origins, size))
 
     # ------------------------------------------------------------------ batches (triplet.py:255-287)
     def __getitems__(self, indices: list[int]) -> dict:
@@ -342,32 +231,6 @@ class TripletDataset(Dataset):
 
     def __getitem__(self, index: int) -> dict:
         return self.__getitems__([index])
-
-
-def _identity(batch):
-    return batch
-
-
-def _collate_norm_meta(norm_metas: list) -> dict:
-    """per-sample ``{channel: {level: {stat: 0-d tensor}}}`` -> the same tree of (B,) tensors (_utils.py:174-191)"""
-    ref = norm_metas[0]
-    out = {}
-    for ch, levels in ref.items():
-        out[ch] = {}
-        for level, stats in levels.items():
-            out[ch][level] = None if stats is None else {st: torch.stack([m[ch][level][st] for m in norm_metas]) for st in stats}
-    return out
-
-
-def _transform_channel_wise(transform, channel_names: list[str], patch: Tensor, norm_meta: list | None) -> Tensor:
-    """_utils.py:194-229: channels go into a dict under their names (B, 1, Z, Y, X) with the collated statistics, through the
-    dict transform, and back together in the dict's order"""
-    channels = {name: patch[:, c : c + 1].contiguous() for c, name in zip(range(patch.shape[1]), channel_names)}
-    if norm_meta is not None:
-        channels["norm_meta"] = _collate_norm_meta(norm_meta)
-    channels = transform(channels)
-    channels.pop("norm_meta", None)
-    return torch.cat(list(channels.values()), dim=1)
 
 
 class TripletDataModule(HCSDataModule):
@@ -459,7 +322,7 @@ class TripletDataModule(HCSDataModule):
             sampler = DistributedSampler(ds, shuffle=shuffle, seed=self.seed, drop_last=drop_last)
             shuffle = False
         return DataLoader(ds, batch_size=batch_size, num_workers=0, shuffle=shuffle, sampler=sampler, drop_last=drop_last,
-                          collate_fn=_identity)
+                          collate_fn=identity)
 
     def train_dataloader(self):
         return self._loader(self.train_dataset, self.batch_size, shuffle=True, drop_last=True)
@@ -494,7 +357,7 @@ class TripletDataModule(HCSDataModule):
                 norm_meta = batch.get(norm_meta_key)
                 if isinstance(norm_meta, list) and all(m is None for m in norm_meta):
                     norm_meta = None
-                batch[key] = _transform_channel_wise(self._find_transform(key), self.source_channel, batch[key], norm_meta)
+                batch[key] = transform_channel_wise(self._find_transform(key), self.source_channel, batch[key], norm_meta)
                 if norm_meta_key in batch:
                     del batch[norm_meta_key]
                 actual_spatial = tuple(batch[key].shape[2:])

@@ -1634,8 +1634,44 @@ def dbscan_finish(adj: Tensor, core: Tensor, labels: Tensor, cid: Tensor, out: T
     return out
 
 
-# ------------------------------------------------------------------------------------------------ patch gather (DynaCLR data feed)
-PATCH_GATHER_DTYPES = {torch.float32: L.PG_F32, torch.uint16: L.PG_U16, torch.int16: L.PG_I16, torch.uint8: L.PG_U8}
+# ------------------------------------------------------------------------------------------------ stored frames: patch gathers (DynaCLR data feeds)
+# the storage dtypes the frame kernels read, each converting to float32 exactly: (numpy dtype, torch dtype, VSX_PG_* code)
+FRAME_DTYPES = ((np.dtype(np.float32), torch.float32, L.PG_F32), (np.dtype(np.uint16), torch.uint16, L.PG_U16),
+                (np.dtype(np.int16), torch.int16, L.PG_I16), (np.dtype(np.uint8), torch.uint8, L.PG_U8))
+PATCH_GATHER_DTYPES = {t: code for _, t, code in FRAME_DTYPES}
+STORAGE_DTYPES = {n: t for n, t, _ in FRAME_DTYPES}
+
+
+def frame_dtype_code(dtype: torch.dtype, who: str) -> int:
+    """the ``VSX_PG_*`` code of a frame's storage dtype; one the kernels do not read raises ``NotImplementedError``"""
+    code = PATCH_GATHER_DTYPES.get(dtype)
+    if code is None:
+        raise NotImplementedError(f"{who}: frames stored as {dtype} are not built (float32, uint16, int16, uint8 are)")
+    return code
+
+
+def _frame_info(who: str, i: int, f: Tensor, f0: Tensor, seen: dict, same_cz: bool = False) -> tuple:
+    """``(data_ptr, stride c, stride z, stride y), shape, f`` of frame ``i`` of a launch whose frame 0 is ``f0``: a (C, Z, H, W) tensor
+    (any view whose last axis is contiguous) of frame 0's dtype and device and, with ``same_cz``, its C and Z.  A frame serves many
+    patches of a batch and is inspected once per object: ``seen`` maps ``id`` to the answer, which holds the object (a temporary must
+    not hand its address to the next one), and the loops ask it first: ``seen.get(id(f)) or _frame_info(...)``."""
+    if f.ndim != 4 or f.dtype != f0.dtype or f.device != f0.device or (same_cz and tuple(f.shape[:2]) != tuple(f0.shape[:2])):
+        raise ValueError(f"{who}: frame {i} is {tuple(f.shape)} {f.dtype} on {f.device}, frame 0 is {tuple(f0.shape)} {f0.dtype} on "
+                         f"{f0.device}: one launch serves (C, Z, H, W) frames of one dtype" + (", C and Z" if same_cz else " and device"))
+    sc, sz, sy, sx = f.stride()
+    if (sx != 1 and f.shape[3] > 1) or min(sc, sz, sy) < 0:
+        raise ValueError(f"{who}: frame {i} has strides {f.stride()}: x must be contiguous, the others >= 0")
+    info = seen[id(f)] = ((f.data_ptr(), sc, sz, sy), tuple(f.shape), f)
+    return info
+
+
+def _gather_out(who: str, f0: Tensor, host_path: str, shape: tuple, out: Tensor | None, table_words: int = 0) -> Tensor:
+    """the checks a gather makes once its tables stand, and its float32 output"""
+    if not f0.is_cuda:
+        raise RuntimeError(f"viscy_amd: {who} runs on the HIP device only (host patches: {host_path})")
+    if shape[0] * shape[1] * shape[2] * shape[3] * shape[4] >= 2 ** 62 or max(shape) >= 2 ** 31 or table_words >= 2 ** 31:
+        raise ValueError(f"{who}: sizes exceed the kernel's index range")
+    return torch.empty(shape, dtype=torch.float32, device=f0.device) if out is None else _typed(out, torch.float32, shape, f"{who}: out")
 
 
 def patch_descriptors(frames: Sequence[Tensor], origins: Sequence[Sequence[int]], size: Sequence[int]) -> Tensor:
@@ -1649,25 +1685,16 @@ def patch_descriptors(frames: Sequence[Tensor], origins: Sequence[Sequence[int]]
     if yp <= 0 or xp <= 0:
         raise ValueError(f"patch_gather: patch size {(yp, xp)} must be positive")
     f0 = frames[0]
-    if f0.dtype not in PATCH_GATHER_DTYPES:
-        raise NotImplementedError(f"patch_gather: frames stored as {f0.dtype} are not built (float32, uint16, int16, uint8 are)")
-    rows, seen = [], {}  # seen: a frame serves many patches of a batch and is inspected once
+    frame_dtype_code(f0.dtype, "patch_gather")
+    rows, seen = [], {}
     for i, (f, (y0, x0)) in enumerate(zip(frames, origins)):
-        info = seen.get(id(f))
-        if info is None:
-            if f.ndim != 4 or f.dtype != f0.dtype or f.device != f0.device or tuple(f.shape[:2]) != tuple(f0.shape[:2]):
-                raise ValueError(f"patch_gather: frame {i} is {tuple(f.shape)} {f.dtype} on {f.device}, frame 0 is {tuple(f0.shape)} "
-                                 f"{f0.dtype} on {f0.device}: one launch serves (C, Z, H, W) frames of one dtype, C and Z")
-            sc, sz, sy, sx = f.stride()
-            if (sx != 1 and f.shape[3] > 1) or min(sc, sz, sy) < 0:
-                raise ValueError(f"patch_gather: frame {i} has strides {f.stride()}: x must be contiguous, the others >= 0")
-            info = seen[id(f)] = (f.data_ptr(), sc, sz, sy, f.shape[2], f.shape[3])
-        y0, x0, H, W = int(y0), int(x0), info[4], info[5]
+        desc, (_, _, H, W), _ = seen.get(id(f)) or _frame_info("patch_gather", i, f, f0, seen, same_cz=True)
+        y0, x0 = int(y0), int(x0)
         if y0 < 0 or y0 + yp > H:
             raise ValueError(f"patch_gather: patch {i} rows [{y0}, {y0 + yp}) leave the frame's [0, {H})")
         if x0 < 0 or x0 + xp > W:
             raise ValueError(f"patch_gather: patch {i} columns [{x0}, {x0 + xp}) leave the frame's [0, {W})")
-        rows.append(info[:4] + (y0, x0))
+        rows.append(desc + (y0, x0))
     return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), L.PG_DESC)
 
 
@@ -1677,14 +1704,9 @@ def patch_gather(frames: Sequence[Tensor], origins: Sequence[Sequence[int]], siz
     on the current stream, which the caller's references guarantee."""
     table = patch_descriptors(frames, origins, size)
     f0 = frames[0]
-    if not f0.is_cuda:
-        raise RuntimeError("viscy_amd: patch_gather runs on the HIP device only (host patches: viscy_amd.data.triplet.host_cut)")
     n, (C, Z), (yp, xp) = len(frames), f0.shape[:2], (int(v) for v in size)
-    if n * C * Z * yp * xp >= 2 ** 62 or max(n, C, Z, yp, xp) >= 2 ** 31:
-        raise ValueError("patch_gather: sizes exceed the kernel's index range")
+    out = _gather_out("patch_gather", f0, "viscy_amd.data.triplet.host_cut", (n, C, Z, yp, xp), out)
     dev_table = table.pin_memory().to(f0.device, non_blocking=True)
-    shape = (n, C, Z, yp, xp)
-    out = torch.empty(shape, dtype=torch.float32, device=f0.device) if out is None else _typed(out, torch.float32, shape, "patch_gather: out")
     check(lib().vsx_patch_gather(ptr(dev_table), ptr(out), n, C, Z, yp, xp, PATCH_GATHER_DTYPES[f0.dtype], stream()), "patch_gather")
     return out
 
@@ -1703,23 +1725,12 @@ def patch_tables(frames: Sequence[Tensor], channels: Sequence, zs: Sequence, ys:
     if n == 0 or not (len(channels) == len(zs) == len(ys) == len(xs) == n):
         raise ValueError(f"patch_gather_scaled: {n} frames for {len(channels)} / {len(zs)} / {len(ys)} / {len(xs)} tables")
     f0 = frames[0]
-    if f0.dtype not in PATCH_GATHER_DTYPES:
-        raise NotImplementedError(f"patch_gather_scaled: frames stored as {f0.dtype} are not built (float32, uint16, int16, uint8 are)")
+    frame_dtype_code(f0.dtype, "patch_gather_scaled")
     segs, seg_of, seg = [], {}, np.empty((n, 4), dtype=np.int64)  # distinct tables, id -> position in segs, per patch and axis
-    held = []  # every object whose id() is a key: a temporary (a row of a 2-D array) must not hand its address to the next one
+    held = []  # every table whose id() is a key: a temporary (a row of a 2-D array) must not hand its address to the next one
     rows, dims, seen = np.empty((n, 4), dtype=np.int64), np.empty((n, 4), dtype=np.int64), {}
     for i, f in enumerate(frames):
-        info = seen.get(id(f))
-        if info is None:
-            if f.ndim != 4 or f.dtype != f0.dtype or f.device != f0.device:
-                raise ValueError(f"patch_gather_scaled: frame {i} is {tuple(f.shape)} {f.dtype} on {f.device}, frame 0 is "
-                                 f"{f0.dtype} on {f0.device}: one launch serves (C, Z, H, W) frames of one dtype and device")
-            sc, sz, sy, sx = f.stride()
-            if (sx != 1 and f.shape[3] > 1) or min(sc, sz, sy) < 0:
-                raise ValueError(f"patch_gather_scaled: frame {i} has strides {f.stride()}: x must be contiguous, the others >= 0")
-            info = seen[id(f)] = ((f.data_ptr(), sc, sz, sy), tuple(f.shape))
-            held.append(f)
-        rows[i], dims[i] = info
+        rows[i], dims[i], _ = seen.get(id(f)) or _frame_info("patch_gather_scaled", i, f, f0, seen)
         for a, t in enumerate((channels[i], zs[i], ys[i], xs[i])):
             k = seg_of.get(id(t))
             if k is None:
@@ -1757,20 +1768,15 @@ def patch_gather_scaled(frames: Sequence[Tensor], channels: Sequence, zs: Sequen
     the launch has been issued on the current stream, which the caller's references guarantee."""
     desc, idx, shape = patch_tables(frames, channels, zs, ys, xs)
     f0 = frames[0]
-    if not f0.is_cuda:
-        raise RuntimeError("viscy_amd: patch_gather_scaled runs on the HIP device only (host patches: "
-                           "viscy_amd.data.multi_experiment.host_gather)")
     n, C, Zt, Yt, Xt = shape
-    if n * C * Zt * Yt * Xt >= 2 ** 62 or max(shape) >= 2 ** 31 or idx.numel() >= 2 ** 31:
-        raise ValueError("patch_gather_scaled: sizes exceed the kernel's index range")
     if Xt > L.PGS_MAX_XT:
         raise ValueError(f"patch_gather_scaled: Xt={Xt}, the kernel holds x tables of at most {L.PGS_MAX_XT} entries")
+    out = _gather_out("patch_gather_scaled", f0, "viscy_amd.data.multi_experiment.host_gather", shape, out, idx.numel())
     words = n * L.PGS_DESC
     both = torch.empty(words + (idx.numel() + 1) // 2, dtype=torch.int64, pin_memory=True)  # descriptors, then the int32 tables
     both[:words] = desc.reshape(-1)
     both[words:].view(torch.int32)[: idx.numel()] = idx
     dev = both.to(f0.device, non_blocking=True)
-    out = torch.empty(shape, dtype=torch.float32, device=f0.device) if out is None else _typed(out, torch.float32, shape, "patch_gather_scaled: out")
     check(lib().vsx_patch_gather_scaled(ptr(dev), ptr(dev[words:]), ptr(out), n, C, Zt, Yt, Xt, PATCH_GATHER_DTYPES[f0.dtype], stream()),
           "patch_gather_scaled")
     return out

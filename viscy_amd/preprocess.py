@@ -30,6 +30,7 @@ from torch import Tensor
 
 from ._lib import check, lib, ptr, stream
 from .data.ome_zarr import open_ome_zarr
+from .ops import frame_dtype_code
 
 PERCENTILES = (1, 5, 25, 50, 75, 95, 99)
 STAT_KEYS = ("min", "max", "mean", "std", "median", "iqr", "p5", "p95", "p95_p5", "p1", "p99", "p99_p1")
@@ -115,24 +116,16 @@ def _device(who: str) -> torch.device:
     return device_of(who=who)
 
 
-def _src_dtypes() -> dict:
-    from .ops import PATCH_GATHER_DTYPES
-
-    return PATCH_GATHER_DTYPES
-
-
 def _planes(src: Tensor, who: str) -> tuple[int, int, int, int, int, int]:
     """(dtype code, z stride, y stride, Z, H, W) of a [Z, H, W] device view the kernels read as it is"""
-    codes = _src_dtypes()
     if not (torch.is_tensor(src) and src.is_cuda and src.ndim == 3 and src.numel() > 0):
         raise RuntimeError(f"{who} needs a non-empty [Z, H, W] tensor on the HIP device (no CPU fallback)")
-    if src.dtype not in codes:
-        raise NotImplementedError(f"{who}: frames stored as {src.dtype} are not built (float32, uint16, int16, uint8 are)")
+    code = frame_dtype_code(src.dtype, who)
     Z, H, W = src.shape
     sz, sy, sx = src.stride()
     if (W > 1 and sx != 1) or sz < 0 or (H > 1 and sy < W) or (H == 1 and sy < 0):
         raise ValueError(f"{who}: strides {src.stride()} of a {tuple(src.shape)} view: x must be contiguous, rows must not overlap")
-    return codes[src.dtype], sz, max(sy, W), Z, H, W
+    return code, sz, max(sy, W), Z, H, W
 
 
 def _out(out: Tensor | None, shape, dtype, dev, who: str) -> Tensor:
